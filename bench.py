@@ -13,14 +13,21 @@ barcodes x 100 k tags, 100 bp reads, 219 B/record = 43.8 GB).
   --scaling strong ONE library byte-sharded over the N GPUs (each shard counted with its true
                    first line index), the same single all-reduce
   --config 2|4|5   the other BASELINE index shapes (parity-test cases; not the headline line)
+  --dump-outputs DIR  after the timed steps, the count matrix of the last step as DIR/<name>.npy (float64)
+  --full           everything beyond the headline (see below); a plain run only sets up, warms up,
+                   times the steps, dumps if asked and prints the line
 
 Rank 0 prints ONE JSON line (see the driver contract in the task statement).
 The `roofline` object prices the count kernel against HBM bandwidth using
 ALGORITHMIC bytes = 219 B x reads per launch and the kernel's own duration
-from HIP events on the launch stream; `cpu_baseline` times the oracle (the
-reference-equivalent Python restatement, and its C port beside it) on a bounded
-prefix of the same stream on this box's host cores; `tiers` reports the
-PCIe- and file-inclusive rates (never `value`).
+from HIP events on the launch stream.  With --full the line also holds: the
+checks of what is timed (`check`: the whole matrix against the generator's
+expectation, a sample against the C oracle), `roofline.traffic` (rocprofv3
+counter passes of their own), the other scaling and the all-reduce alone
+(N > 1), `progress_windows`, `count_and_trim` (config 5), `cpu_baseline` (the
+oracle -- the reference-equivalent Python restatement, and its C port beside
+it -- timed on a bounded prefix of the same stream on the host cores),
+`other_configs` and `tiers` (the PCIe- and file-inclusive rates; never `value`).
 """
 import argparse
 import json
@@ -40,6 +47,10 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks, counter passes, other configs, CPU baselines and tiers (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's count matrix (row / column sums, a seeded sample of cells) as DIR/<name>.npy")
     ap.add_argument("--config", type=int, default=3, choices=(2, 3, 4, 5),
                     help="BASELINE config whose index shape and seed to use (3 = the one the metric is quoted on)")
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"))
@@ -52,18 +63,18 @@ def parse_args(argv=None):
     ap.add_argument("--skew", type=float, default=0.0, help="Zipf exponent of the hit distribution over tags and barcodes (0 = uniform)")
     ap.add_argument("--tile-kb", type=int, default=0)
     ap.add_argument("--blocks-per-cu", type=int, default=0)
-    ap.add_argument("--cpu-sample", type=int, default=20_000_000, help="reads in the C port's cpu_baseline sample (0 = skip cpu_baseline)")
+    ap.add_argument("--cpu-sample", type=int, default=20_000_000, help="--full: reads in the C port's cpu_baseline sample (0 = skip cpu_baseline)")
     ap.add_argument("--cpu-python-sample", type=int, default=400_000,
-                    help="reads for the pure-Python restatement's timing (cpu_baseline.value; 0 = skip)")
+                    help="--full: reads for the pure-Python restatement's timing (cpu_baseline.value; 0 = skip)")
     ap.add_argument("--oracle-sample", type=int, default=2_000_000,
-                    help="reads of the resident stream counted by the C oracle and compared with a GPU pass over the same bytes (0 = skip)")
-    ap.add_argument("--tier-reads", type=int, default=16_000_000, help="reads in the T2/T3 tier measurements (0 = skip)")
+                    help="--full: reads of the resident stream counted by the C oracle and compared with a GPU pass over the same bytes (0 = skip)")
+    ap.add_argument("--tier-reads", type=int, default=16_000_000, help="--full: reads in the T2/T3 tier measurements (0 = skip)")
     ap.add_argument("--other-configs", default="auto",
-                    help="BASELINE configs measured after the headline at N=1 (3 steps each, full read count, bit-exact check); "
+                    help="--full: BASELINE configs measured after the headline at N=1 (3 steps each, full read count, bit-exact check); "
                          "auto = 2,4,5 with the default workload, none otherwise; '' = skip")
     ap.add_argument("--other-reads", type=int, default=0, help="reads of those passes (0 = each config's own count)")
     ap.add_argument("--traffic", default="auto", choices=("auto", "off"),
-                    help="roofline.traffic: 'auto' = two rocprofv3 --pmc child runs of this script (FETCH_SIZE, WRITE_SIZE) when "
+                    help="--full: roofline.traffic: 'auto' = two rocprofv3 --pmc child runs of this script (FETCH_SIZE, WRITE_SIZE) when "
                          "rocprofv3 is on PATH, else null")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)      # (the counter passes' run: launches only)
     ap.add_argument("--no-check", action="store_true")
@@ -199,7 +210,7 @@ def main():
     default_workload = is_default_workload(args)
     # the counter passes come first: their children must be started by a process that has not initialised HIP
     traffic = None
-    if world == 1 and default_workload and args.traffic == "auto" and not args.pmc_child:
+    if args.full and world == 1 and default_workload and args.traffic == "auto" and not args.pmc_child:
         traffic = measure_traffic(args)
 
     import numpy as np
@@ -312,7 +323,7 @@ def main():
 
         # ---- correctness of what is being timed (rank-local shard, before any all-reduce)
         check = None
-        if not args.no_check:
+        if args.full and not args.no_check:
             # (1) the whole matrix against the one the generator's own choices imply (built on the device from
             # the shared spec include/td_synth_spec.h; nothing is parsed, nothing of oracle/ is involved)
             counts.zero_()
@@ -369,18 +380,18 @@ def main():
             t = torch.tensor([elapsed, kms], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed, kms = float(t[0]), float(t[1])
+        if dist_on and check is not None:           # (None on every rank alike: the same arguments)
             # every rank now holds the same summed matrix: its total must equal the sum of all shards' hits
             tot = torch.tensor([int(last.to(torch.int64).sum())], dtype=torch.int64, device=dev)
-            mine = torch.tensor([check["tag"] if check else 0], dtype=torch.int64, device=dev)
+            mine = torch.tensor([check["tag"]], dtype=torch.int64, device=dev)
             dist.all_reduce(mine)
-            if check:
-                check["reduced_total_equals_sum_of_shard_hits"] = int(tot[0]) == int(mine[0])
-                if int(tot[0]) != int(mine[0]):
-                    print("bench.py: all-reduced matrix total %d != sum of shard hits %d" % (int(tot[0]), int(mine[0])),
-                          file=sys.stderr)
-                    sys.exit(3)
+            check["reduced_total_equals_sum_of_shard_hits"] = int(tot[0]) == int(mine[0])
+            if int(tot[0]) != int(mine[0]):
+                print("bench.py: all-reduced matrix total %d != sum of shard hits %d" % (int(tot[0]), int(mine[0])),
+                      file=sys.stderr)
+                sys.exit(3)
         return {"scaling": scaling, "my_reads": my_reads, "nbytes": nbytes, "first_line": first_line, "job_reads": job_reads,
-                "elapsed": elapsed, "kms": kms, "ktimes": ktimes, "fixups": fixups, "check": check, "step": step}
+                "elapsed": elapsed, "kms": kms, "ktimes": ktimes, "fixups": fixups, "check": check, "step": step, "last": last}
 
     def allreduce_alone():
         """the path's one exchange by itself: the int32 [barcodes x tags] matrix, in place, median of 5 (max over ranks)"""
@@ -397,10 +408,13 @@ def main():
         return float(t[0]) * 1e3
 
     main_run = run_scaling(args.scaling)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main_run["last"], len(cfg.barcodes), len(cfg.tags))
+    main_run["last"] = None
     strong_run = None
-    if world > 1 and args.scaling == "weak" and not args.pmc_child:
+    if args.full and world > 1 and args.scaling == "weak" and not args.pmc_child:
         strong_run = run_scaling("strong")                 # (the metric's literal reading: ONE library over the N GPUs)
-    allreduce_ms = allreduce_alone() if dist_on else None
+    allreduce_ms = allreduce_alone() if dist_on and args.full else None
     R = main_run
     my_reads, nbytes, first_line, kms, ktimes = R["my_reads"], R["nbytes"], R["first_line"], R["kms"], R["ktimes"]
     step = R["step"]
@@ -424,7 +438,7 @@ def main():
             "metric": metric,
             "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": R["elapsed"] / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "BASELINE configs[%d] shape, device-resident (tier T1): %d reads x %d barcodes x %d tags "
                                    "per GPU, 100 bp reads, %d B/record, cut site %s%s, %s"
                                    % (args.config - 1, my_reads, len(cfg.barcodes), len(cfg.tags), cfg.record_bytes, cfg.cutsite,
@@ -460,7 +474,7 @@ def main():
                              "allreduce_ms": allreduce_ms,
                              "what": "ONE library byte-sharded over the GPUs, each shard counted with its true first line index, "
                                      "the same all-reduce per pass (overlapped with the next pass)"}
-        if world == 1 and not args.debug_ablate:
+        if args.full and world == 1 and not args.debug_ablate:
             # the same pass with the reference's progress counters kept per window of 50 000 reads (find_tags_fastq's
             # default here, reference :268-271) -- untimed above, reported beside it
             # Passes with and without the counters ALTERNATE in one loop (after one untimed pass of the recording kernel, whose
@@ -487,13 +501,13 @@ def main():
                                        "what": "medians of 4 + 4 alternating passes; the headline is measured without the counters"}
             eng.set_option("timing", 0)
             eng.set_option("progress", 0)
-        if world == 1 and args.config == 5 and not args.debug_ablate:
+        if args.full and world == 1 and args.config == 5 and not args.debug_ablate:
             out["count_and_trim"] = count_and_trim(eng, cfg, fastq, nbytes, first_line, my_reads, stream)
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(cfg, min(args.cpu_sample, my_reads), min(args.cpu_python_sample, my_reads))
             note("cpu_baseline")
         others = ("2,4,5" if default_workload else "") if args.other_configs == "auto" else args.other_configs
-        if world == 1 and others and not args.debug_ablate:
+        if args.full and world == 1 and others and not args.debug_ablate:
             del fastq
             R = main_run = None
             eng.bind_counts(0)
@@ -504,7 +518,7 @@ def main():
                 out["other_configs"]["c%d" % cid] = other_config(eng, args, cid, dev, stream)
                 note("other_configs")
             fastq = None
-        if world == 1 and args.tier_reads > 0 and not args.debug_ablate:
+        if args.full and world == 1 and args.tier_reads > 0 and not args.debug_ablate:
             fastq = None
             R = main_run = None
             torch.cuda.empty_cache()
@@ -516,6 +530,29 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     eng.close()
+
+
+DUMP_SAMPLE_CELLS = 1 << 21      # (2 M cells: values and their indices, 16 MB each as float64)
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(directory, mat, nbar, ntags):
+    """--dump-outputs: the int32 [barcodes x tags] count matrix the last timed step left (what a caller of the path
+    receives), as float64 (exact for every int32): its row and column sums in full, and the cells themselves -- all of
+    them when there are at most DUMP_SAMPLE_CELLS, else a fixed seeded sample with their flat indices.  Same arguments,
+    same inputs: two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    m = mat.cpu().numpy().view(np.int32).reshape(nbar, ntags)
+    np.save(os.path.join(directory, "counts_row_sums.npy"), m.sum(axis=1, dtype=np.int64).astype(np.float64))
+    np.save(os.path.join(directory, "counts_col_sums.npy"), m.sum(axis=0, dtype=np.int64).astype(np.float64))
+    flat = m.reshape(-1)
+    if flat.size <= DUMP_SAMPLE_CELLS:
+        np.save(os.path.join(directory, "counts.npy"), m.astype(np.float64))
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, DUMP_SAMPLE_CELLS, replace=False))
+        np.save(os.path.join(directory, "counts_sample.npy"), flat[idx].astype(np.float64))
+        np.save(os.path.join(directory, "counts_sample_index.npy"), idx.astype(np.float64))
 
 
 def other_config(eng, args, cid, dev, stream, steps=3):

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd /tmp
 echo "[profile] the default bench"
-python3 "$ROOT/bench.py" > "$OUT/bench_default.log" 2> "$OUT/bench_default.err" || exit 1
+python3 "$ROOT/bench.py" --full > "$OUT/bench_default.log" 2> "$OUT/bench_default.err" || exit 1
 echo "[profile] kernel trace of the default bench"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --traffic off --tier-reads 0 --cpu-sample 0 --other-configs= > "$OUT/bench_traced.log" 2> "$OUT/bench_traced.err" || exit 1
 f=$(find "$OUT/stats" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT/kernel_stats.csv"
