@@ -239,6 +239,54 @@ int td_split_file(td_handle *h, const char *in_path, const char *const *out_path
  * window w (50 000 consecutive reads); *nwindows = ceil(reads / 50 000).  Running sums are the printed numbers. */
 int td_split_progress(td_handle *h, uint64_t *out, uint64_t cap, uint64_t *nwindows);
 
+/* ---- expected fragment sizes (the reference's exp_frag_size.py; tagdigger_amd/exp_frag_size.py drives these) -----
+ *
+ * td_fasta_frame_device: K1, the genome reading of exp_frag_size.py:152-189 over ONE genome file in device memory.
+ * The reference reads the file in text mode (universal newlines: \n, \r\n and a lone \r end a line); a line whose first
+ * character is '>' is a header (:164), and every other line contributes line.strip().upper() to the sequence (:189).
+ * This writes exactly those bytes, concatenated, to d_out[0 .. *n_out) (*n_out <= nbytes) and one row per header line,
+ * in file order, to rec_out[3 r .. 3 r + 2]: the input offsets [lo, hi) of the header's name line[1:].strip() (:166)
+ * and the number of sequence bytes written before that header (where the record that precedes it ends).
+ *   d_text     16-byte aligned, readable up to nbytes rounded up to 16
+ *   d_out      any alignment; room for nbytes bytes
+ *   rec_cap    rows rec_out can hold (the file's count of '>' bytes always suffices); TD_E_LIMIT if fewer
+ *   *n_rec     header lines in the file
+ *   *nonascii  1: the file holds a byte >= 0x80, which the reference decodes with the locale's codec -- nothing is written
+ *              (*n_out = 0) and the caller reads the file on the host
+ *   ms         optional: device time of the three kernels
+ * Python's strip() set is ASCII \t \n \v \f \r, 0x1c-0x1f and space; upper() changes a-z only.  Synchronous. */
+int td_fasta_frame_device(td_handle *h, const void *d_text, uint64_t nbytes, void *d_out, uint64_t *n_out,
+                          uint64_t *rec_out, uint64_t rec_cap, uint64_t *n_rec, int *nonascii, double *ms);
+
+/* One search of exp_frag_size.py:174-194 -- one tag in one record.  [lo, hi) is the window in the device sequence:
+ * sequence[pos-1 : pos+3000] forward (:178), sequence[max(0, pos-3000) : pos] reverse (:181-182), both resolved by the
+ * caller with Python's slice rules (slice(a, b).indices(len)); `reverse` != 0 searches reverseComplement of the window
+ * (tagdigger_fun.py:1203-1206: A, C, G, T complemented, every other byte kept) without materialising it.  tagsize is
+ * len(fields[9]) of the tag's SAM line (any value above the window's length + 64 behaves like that bound). */
+typedef struct td_frag_job {
+    uint64_t lo, hi;
+    int32_t tagsize, reverse;
+    uint64_t reserved;
+} td_frag_job;
+
+enum {
+    TD_FRAG_MAX_SITES = 16,       /* non-empty cut sites per search; more: TD_E_LIMIT                         */
+    TD_FRAG_MAX_SITE_LEN = 64,    /* bytes per cut site; longer: TD_E_LIMIT                                   */
+    TD_FRAG_MAX_WINDOW = 3072     /* hi - lo; the reference's windows hold at most 3 001 bytes                */
+};
+
+/* K2: out[4 j .. 4 j + 3] = {size, G + C, N, 0} for jobs[j].  size is min over the sites of subseq.find(cs,
+ * tagsize - len(cs)) + len(cs) over the hits (:186-189), -1 for "NA"; G + C and N are counted over subseq[:size]
+ * (:192-194; the caller divides).  sites: nsites non-empty strings (an empty cut site needs no search: str.find
+ * returns its start, and the caller decides it).  ms optional (device time).  Synchronous. */
+int td_frag_search_device(td_handle *h, const void *d_seq, uint64_t seq_bytes, const td_frag_job *jobs, uint64_t njobs,
+                          const char *const *sites, uint32_t nsites, int32_t *out, double *ms);
+
+/* K3: subseq[:sizes[j]] of every job (:191), reverse-complemented for reverse jobs, packed in job order into host
+ * memory out[0 .. *n_out) (sizes <= 0 contribute nothing); TD_E_LIMIT if that exceeds out_cap.  Synchronous. */
+int td_frag_gather_device(td_handle *h, const void *d_seq, uint64_t seq_bytes, const td_frag_job *jobs,
+                          const int32_t *sizes, uint64_t njobs, void *out, uint64_t out_cap, uint64_t *n_out, double *ms);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */

@@ -137,6 +137,10 @@ def load():
     sig("td_device_sync", i32, vp)
     sig("td_synth_fill_device", i32, vp, vp, u64, u64, C.c_char_p, vp, C.c_char_p, C.c_char_p, vp, vp, vp)
     sig("td_synth_expected_device", i32, vp, vp, u64, u64, vp, C.POINTER(u64), vp)
+    dp = C.POINTER(C.c_double)
+    sig("td_fasta_frame_device", i32, vp, vp, u64, vp, C.POINTER(u64), vp, u64, C.POINTER(u64), C.POINTER(C.c_int), dp)
+    sig("td_frag_search_device", i32, vp, vp, u64, vp, u64, C.POINTER(C.c_char_p), u32, vp, dp)
+    sig("td_frag_gather_device", i32, vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), dp)
     _lib = L
     return L
 
@@ -151,6 +155,7 @@ EXPORTS = [
     "td_count_lines_device", "td_load_file_range", "td_bgzf_index", "td_bgzf_inflate_range", "td_gunzip_file", "td_gzip_check", "td_gunzip_file_gpu", "td_last_gz_route", "td_gz_shard_open", "td_gz_shard_decode", "td_gz_shard_resolve", "td_crc32_join", "td_set_splitter", "td_split_device", "td_count_and_split_device", "td_split_file", "td_fold_rows", "td_inflate_raw_host", "td_format_csv_row", "td_get_counts", "td_get_stats", "td_get_progress", "td_split_progress", "td_set_option",
     "td_kernel_time_ms", "td_kernel_times_ms", "td_debug_counters", "td_dev_alloc", "td_dev_free", "td_memcpy_h2d", "td_memcpy_d2h",
     "td_device_sync", "td_synth_fill_device", "td_synth_expected_device",
+    "td_fasta_frame_device", "td_frag_search_device", "td_frag_gather_device",
 ]
 
 

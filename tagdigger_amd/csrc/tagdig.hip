@@ -677,6 +677,9 @@ int build_barcode_blob(const std::vector<std::pair<std::string, uint32_t>> &entr
 extern "C" {
 
 const char *td_last_error(void) { return g_err.c_str(); }
+// for the library's other translation units (csrc/fragsize.hip); hidden: not part of the C-ABI
+__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg) { return fail(code, msg); }
+__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h) { return h->device; }
 uint32_t td_last_bad_index(void) { return g_bad; }
 
 }  // extern "C"

@@ -47,6 +47,12 @@ def effective_maxreads(maxreads):
     return max(1, int(math.ceil(maxreads)))
 
 
+def frag_job_dtype():
+    """numpy layout of td_frag_job (include/tagdig.h)."""
+    import numpy as np
+    return np.dtype([("lo", "<u8"), ("hi", "<u8"), ("tagsize", "<i4"), ("reverse", "<i4"), ("reserved", "<u8")])
+
+
 def _c_strings(strings):
     arr = (C.c_char_p * max(1, len(strings)))()
     for i, s in enumerate(strings):
@@ -290,6 +296,54 @@ class Engine:
         without host lists."""
         arr = (C.c_uint32 * max(1, self.barnum))(*rows)
         B.check(self._L.td_fold_rows(self._h, arr, n_dst_rows, C.c_void_p(d_dst), C.c_void_p(stream) if stream else None))
+
+    # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
+    def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):
+        """K1 over one genome file in device memory (td_fasta_frame_device): the reference's line.strip().upper()
+        of every sequence line, concatenated, lands at d_out.  Returns (bytes written, numpy uint64 [headers, 3]
+        rows: name offsets [lo, hi) in the input and the sequence bytes before the header, holds a byte >= 0x80,
+        device ms)."""
+        import numpy as np
+        n_out, n_rec, nonascii, ms = C.c_uint64(0), C.c_uint64(0), C.c_int(0), C.c_double(0)
+        for _ in range(2):        # a second time with the table the file needs (the first call reports its headers)
+            rec = np.zeros((max(1, rec_cap), 3), dtype=np.uint64)
+            rc = self._L.td_fasta_frame_device(self._h, C.c_void_p(d_text), int(nbytes), C.c_void_p(d_out), C.byref(n_out),
+                                               rec.ctypes.data_as(C.c_void_p), int(rec_cap), C.byref(n_rec),
+                                               C.byref(nonascii), C.byref(ms))
+            if rc == -7 and n_rec.value > rec_cap:
+                rec_cap = n_rec.value
+                continue
+            B.check(rc)
+            break
+        if nonascii.value:
+            return 0, rec[:0], True, ms.value
+        return n_out.value, rec[:n_rec.value], False, ms.value
+
+    def frag_search_device(self, d_seq, seq_bytes, jobs, sites):
+        """K2 (td_frag_search_device): jobs is a numpy frag_job_dtype() array; returns (int32 [njobs, 4] = size or -1,
+        G + C, N, 0; device ms)."""
+        import numpy as np
+        jobs = np.ascontiguousarray(jobs, dtype=frag_job_dtype())
+        out = np.zeros((max(1, len(jobs)), 4), dtype=np.int32)
+        arr = (C.c_char_p * max(1, len(sites)))(*[x.encode("ascii") for x in sites])
+        ms = C.c_double(0)
+        B.check(self._L.td_frag_search_device(self._h, C.c_void_p(d_seq), int(seq_bytes), jobs.ctypes.data_as(C.c_void_p),
+                                              len(jobs), arr, len(sites), out.ctypes.data_as(C.c_void_p), C.byref(ms)))
+        return out[:len(jobs)], ms.value
+
+    def frag_gather_device(self, d_seq, seq_bytes, jobs, sizes):
+        """K3 (td_frag_gather_device): the fragments subseq[:size] of the jobs, packed in job order; returns
+        (bytes, device ms)."""
+        import numpy as np
+        jobs = np.ascontiguousarray(jobs, dtype=frag_job_dtype())
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+        cap = int(np.clip(sizes, 0, None).sum())
+        buf = np.zeros(max(1, cap), dtype=np.uint8)
+        n, ms = C.c_uint64(0), C.c_double(0)
+        B.check(self._L.td_frag_gather_device(self._h, C.c_void_p(d_seq), int(seq_bytes), jobs.ctypes.data_as(C.c_void_p),
+                                              sizes.ctypes.data_as(C.c_void_p), len(jobs), buf.ctypes.data_as(C.c_void_p),
+                                              cap, C.byref(n), C.byref(ms)))
+        return buf[:n.value].tobytes(), ms.value
 
     # ------------------------------------------------------------------ results
     def stats(self):
