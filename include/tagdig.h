@@ -287,6 +287,43 @@ int td_frag_search_device(td_handle *h, const void *d_seq, uint64_t seq_bytes, c
 int td_frag_gather_device(td_handle *h, const void *d_seq, uint64_t seq_bytes, const td_frag_job *jobs,
                           const int32_t *sizes, uint64_t njobs, void *out, uint64_t out_cap, uint64_t *n_out, double *ms);
 
+/* ---- Tag Manager (the reference's tag_manager.py; tagdigger_amd/tagdigger_fun.py drives these) --------------------
+ *
+ * Tags are passed as ASCII bytes seqs[offs[i] .. offs[i + 1]), i < n (offs has n + 1 entries, not decreasing).  The
+ * device takes tags of at most TD_TAGSET_MAX_LEN bases: a longer one is TD_E_LIMIT, a byte outside ACGT TD_E_ALPHABET
+ * (in both cases nothing is kept and the caller runs its host restatement).  ms (optional) reports device time.
+ *
+ * td_tagset_load: K1 packs the tags (2 bits per base, A-padded, plus the length), K2 sorts them on the device with a
+ * stable LSD radix sort by (sequence, then the position in `order`), and the sorted set stays resident in *out until
+ * td_tagset_free.  `order` (NULL: 0 .. n - 1) is the tags sorted by name in code-point order, so perm_out -- the input
+ * index of every sorted position -- is the order of Python's sorted(zip(seqs, names)).  passes (optional): the radix
+ * passes run (a digit every key shares is skipped).  ms[0] K1, ms[1] K2 (2 entries). */
+typedef struct td_tagset td_tagset;
+enum {
+    TD_TAGSET_MAX_LEN = 256,
+    TD_TAGSET_MAX_TAGS = 1 << 30
+};
+int td_tagset_load(td_handle *h, const char *seqs, const uint64_t *offs, uint32_t n, const uint32_t *order,
+                   td_tagset **out, uint32_t *perm_out, uint32_t *passes, double *ms);
+int td_tagset_free(td_handle *h, td_tagset *s);
+
+/* K3: for every query tag q (nq of them, same layout), the walk of lookupMarkerByTag (tagdigger_fun.py:1674-1706) in
+ * the sorted set, as sorted positions out[4 k .. 4 k + 3] = {f, a, b, c}: f the tag whose marker is added first (-1:
+ * nothing found; then a = b = c = -1), a where the forward walk starts, b where it ends, c where the backward walk
+ * ends.  The markers are added in the order f, a + 1 .. b, b - 1 down to c.  allow_diff_lengths as the reference's
+ * allowDiffLengths.  Each walk costs at most len(q) + 4 binary searches.  Synchronous. */
+int td_tagset_lookup(td_handle *h, const td_tagset *s, const char *seqs, const uint64_t *offs, uint32_t nq,
+                     int allow_diff_lengths, int32_t *out, double *ms);
+
+/* K4: compareTags (tagdigger_fun.py:376-393) for ngroups groups of tags; group g holds the tags idx[goff[g] ..
+ * goff[g + 1]) (goff[0] = 0, no group empty).  mask_out[4 g .. 4 g + 3] gets bit c of column c that compareTags
+ * reports (trim != 0: columns below the shortest tag; trim == 0: a column where two tags long enough to reach it
+ * differ), nonacgt_out[g] = 1 when a tag of the group holds a byte outside ACGT (compareTags' AssertionError; the
+ * group's mask then means nothing).  Synchronous. */
+int td_tagset_varsites(td_handle *h, const char *seqs, const uint64_t *offs, uint32_t ntags, const uint32_t *idx,
+                       const uint64_t *goff, uint32_t ngroups, int trim, uint64_t *mask_out, uint8_t *nonacgt_out,
+                       double *ms);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */

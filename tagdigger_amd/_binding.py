@@ -141,6 +141,10 @@ def load():
     sig("td_fasta_frame_device", i32, vp, vp, u64, vp, C.POINTER(u64), vp, u64, C.POINTER(u64), C.POINTER(C.c_int), dp)
     sig("td_frag_search_device", i32, vp, vp, u64, vp, u64, C.POINTER(C.c_char_p), u32, vp, dp)
     sig("td_frag_gather_device", i32, vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), dp)
+    sig("td_tagset_load", i32, vp, vp, vp, u32, vp, C.POINTER(vp), vp, C.POINTER(u32), dp)
+    sig("td_tagset_free", i32, vp, vp)
+    sig("td_tagset_lookup", i32, vp, vp, vp, vp, u32, i32, vp, dp)
+    sig("td_tagset_varsites", i32, vp, vp, vp, u32, vp, vp, u32, i32, vp, vp, dp)
     _lib = L
     return L
 
@@ -156,6 +160,7 @@ EXPORTS = [
     "td_kernel_time_ms", "td_kernel_times_ms", "td_debug_counters", "td_dev_alloc", "td_dev_free", "td_memcpy_h2d", "td_memcpy_d2h",
     "td_device_sync", "td_synth_fill_device", "td_synth_expected_device",
     "td_fasta_frame_device", "td_frag_search_device", "td_frag_gather_device",
+    "td_tagset_load", "td_tagset_free", "td_tagset_lookup", "td_tagset_varsites",
 ]
 
 

@@ -1,0 +1,610 @@
+// Tag Manager on the GPU (include/tagdig.h: td_tagset_load, td_tagset_lookup, td_tagset_varsites, td_tagset_free).
+//
+// K1 k_tag_pack: one thread per tag turns its ASCII bases into W = ceil(maxlen / 32) 64-bit words, 2 bits per base
+//    (A 0, C 1, G 2, T 3), first base in the top bits, padded with A; plus the length.  With the length as a tie-break
+//    the order of (words, length) is Python's str order on ACGT strings ("AC" < "ACA" < "ACAA").  A byte outside ACGT
+//    is flagged, not packed.  Keys are word-major (key[w * n + i]) so a lane's reads of one word coalesce.
+// K2 the stable LSD radix sort of the tag permutation by (words, length), 8 bits per pass.  The permutation starts in
+//    the names' code-point order (the host ranks the names), so stability gives sorted(zip(seqs, names)).  One pass:
+//    k_rs_hist (per-tile histograms, digit-major), k_rs_scan (one workgroup, exclusive scan), k_rs_scatter (per tile:
+//    a wave ranks its 64 elements by digit with eight ballots, waves and iterations in index order keep it stable).
+//    k_rs_same first marks the digit positions where some key differs from key 0; the others are skipped.
+//    k_rs_gather then lays the keys out in sorted order for K3.
+// K3 k_tag_lookup: one thread per query, the reference's lookupMarkerByTag walk (tagdigger_fun.py:1674-1706) as four
+//    indices f, a, b, c (see the header).  Every block the walk crosses is contiguous in the sorted set (a run of
+//    duplicates, the strings that start with q, each run of prefixes of q), so each is one binary search: at most
+//    len(q) + 4 searches of log2(n) steps, whatever the duplicates.
+// K4 k_tag_varsites: one wave per group of tags; lane l owns columns l, l + 64, l + 128, l + 192 and ORs a one-hot of
+//    the base each tag has there; a column is variable when two bits are set.  Ballots make the 4 x 64-bit mask.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/tagdig.h"
+
+// tagdig.hip (not exported): the library's error slot and the handle's device
+extern "C" {
+__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
+__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
+}
+
+struct td_tagset {
+    int device;
+    uint32_t n, W;
+    uint64_t *key;     // W * n words, sorted order, word-major
+    uint16_t *len;     // n, sorted order
+};
+
+namespace {
+
+#define TSCHK(call)                                                                          \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+
+constexpr int TS_MAXW = TD_TAGSET_MAX_LEN / 32;   // 8 words
+constexpr int RS_THREADS = 256;
+constexpr int RS_ITEMS = 16;
+constexpr int RS_TILE = RS_THREADS * RS_ITEMS;     // 4 096 elements per workgroup
+constexpr int RS_SCAN_THREADS = 1024;
+
+template <typename T> struct TsBuf {
+    T *p = nullptr;
+    ~TsBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)); }
+};
+
+struct TsEvents {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~TsEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// ------------------------------------------------------------------ K1
+__device__ __forceinline__ uint32_t ts_code(uint32_t c, bool *bad) {
+    const uint32_t v = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+    if (v == 4u) *bad = true;
+    return v & 3u;
+}
+
+__global__ __launch_bounds__(256) void k_tag_pack(const uint8_t *seqs, const uint64_t *offs, uint32_t n, uint32_t W,
+                                                  uint64_t *key, uint16_t *len, uint32_t *bad_first) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t s = offs[i], e = offs[i + 1];
+    const uint32_t L = (uint32_t)(e - s);          // <= 32 W, checked by the host
+    bool bad = false;
+    for (uint32_t w = 0; w < W; ++w) {
+        uint64_t v = 0;
+        const uint32_t b0 = w * 32;
+        for (uint32_t k = 0; k < 32; ++k) {
+            const uint32_t p = b0 + k;
+            const uint64_t c = p < L ? ts_code(seqs[s + p], &bad) : 0u;
+            v |= c << (62 - 2 * k);
+        }
+        key[(uint64_t)w * n + i] = v;
+    }
+    len[i] = (uint16_t)L;
+    if (bad) atomicMin(bad_first, i);
+}
+
+// ------------------------------------------------------------------ K2
+// digit position p: 0, 1 the length's bytes; 2 + 8 r + k byte k of word W - 1 - r (least significant first)
+__device__ __forceinline__ uint32_t rs_digit(const uint64_t *key, const uint16_t *len, uint32_t n, uint32_t W, uint32_t idx,
+                                             uint32_t p) {
+    if (p < 2) return (len[idx] >> (8 * p)) & 255u;
+    const uint32_t r = (p - 2) >> 3, k = (p - 2) & 7;
+    return (uint32_t)(key[(uint64_t)(W - 1 - r) * n + idx] >> (8 * k)) & 255u;
+}
+
+__global__ __launch_bounds__(256) void k_rs_same(const uint64_t *key, const uint16_t *len, uint32_t n, uint32_t W,
+                                                 uint32_t *differ) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t npos = 2 + 8 * W;
+    uint32_t m[3] = {0, 0, 0};
+    if (i < n) {
+        if (len[i] != len[0]) m[0] |= ((len[i] ^ len[0]) & 255u ? 1u : 0u) | ((len[i] ^ len[0]) >> 8 ? 2u : 0u);
+        for (uint32_t w = 0; w < W; ++w) {
+            const uint64_t x = key[(uint64_t)w * n + i] ^ key[(uint64_t)w * n];
+            if (!x) continue;
+            const uint32_t r = W - 1 - w;
+            for (uint32_t k = 0; k < 8; ++k)
+                if ((x >> (8 * k)) & 255u) {
+                    const uint32_t p = 2 + 8 * r + k;
+                    if (p < npos) m[p >> 5] |= 1u << (p & 31);
+                }
+        }
+    }
+    for (int q = 0; q < 3; ++q) {
+        uint32_t v = m[q];
+        for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d, 64);
+        if ((threadIdx.x & 63) == 0 && v) atomicOr(&differ[q], v);
+    }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const uint64_t *key, const uint16_t *len, const uint32_t *perm,
+                                                        uint32_t n, uint32_t W, uint32_t p, uint32_t nblocks, uint32_t *hist) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * RS_TILE;
+    for (int it = 0; it < RS_ITEMS; ++it) {
+        const uint64_t j = base + (uint64_t)it * RS_THREADS + threadIdx.x;
+        if (j < n) atomicAdd(&h[rs_digit(key, len, n, W, perm[j], p)], 1u);
+    }
+    __syncthreads();
+    hist[(uint64_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+}
+
+// exclusive scan of m entries in place, one workgroup
+__global__ __launch_bounds__(RS_SCAN_THREADS) void k_rs_scan(uint32_t *a, uint64_t m) {
+    __shared__ uint32_t part[RS_SCAN_THREADS];
+    const uint64_t chunk = (m + RS_SCAN_THREADS - 1) / RS_SCAN_THREADS;
+    const uint64_t lo0 = (uint64_t)threadIdx.x * chunk, lo = lo0 < m ? lo0 : m, hi = lo + chunk < m ? lo + chunk : m;
+    uint32_t s = 0;
+    for (uint64_t i = lo; i < hi; ++i) s += a[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < RS_SCAN_THREADS; d <<= 1) {
+        const uint32_t v = threadIdx.x >= (uint32_t)d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[threadIdx.x] - s;
+    for (uint64_t i = lo; i < hi; ++i) {
+        const uint32_t v = a[i];
+        a[i] = run;
+        run += v;
+    }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const uint64_t *key, const uint16_t *len, const uint32_t *perm_in,
+                                                           uint32_t *perm_out, uint32_t n, uint32_t W, uint32_t p,
+                                                           uint32_t nblocks, const uint32_t *hist) {
+    __shared__ uint32_t boff[256];
+    __shared__ uint32_t wcnt[RS_THREADS / 64][256];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    boff[threadIdx.x] = hist[(uint64_t)threadIdx.x * nblocks + blockIdx.x];
+    for (int w = 0; w < RS_THREADS / 64; ++w) wcnt[w][threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * RS_TILE;
+    const uint64_t lt = (1ull << lane) - 1ull;
+    for (int it = 0; it < RS_ITEMS; ++it) {
+        const uint64_t j = base + (uint64_t)it * RS_THREADS + threadIdx.x;
+        const bool valid = j < n;
+        uint32_t v = 0, d = 0;
+        if (valid) {
+            v = perm_in[j];
+            d = rs_digit(key, len, n, W, v, p);
+        }
+        uint64_t peers = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const uint64_t bb = __ballot(valid && bit);
+            peers &= bit ? bb : ~bb;
+        }
+        const uint32_t rank = (uint32_t)__popcll(peers & lt);
+        if (valid && (peers >> lane) == 1ull) wcnt[wv][d] = (uint32_t)__popcll(peers);   // the highest peer
+        __syncthreads();
+        if (valid) {
+            uint32_t dst = boff[d] + rank;
+            for (int w = 0; w < wv; ++w) dst += wcnt[w][d];
+            perm_out[dst] = v;
+        }
+        __syncthreads();
+        uint32_t add = 0;
+        for (int w = 0; w < RS_THREADS / 64; ++w) {
+            add += wcnt[w][threadIdx.x];
+            wcnt[w][threadIdx.x] = 0;
+        }
+        boff[threadIdx.x] += add;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rs_gather(const uint64_t *key, const uint16_t *len, const uint32_t *perm, uint32_t n,
+                                                   uint32_t W, uint64_t *skey, uint16_t *slen) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = perm[i];
+    for (uint32_t w = 0; w < W; ++w) skey[(uint64_t)w * n + i] = key[(uint64_t)w * n + v];
+    slen[i] = len[v];
+}
+
+// ------------------------------------------------------------------ K3
+struct Query {
+    uint64_t w[TS_MAXW];
+    uint32_t L, W;
+};
+
+struct SetView {
+    const uint64_t *key;
+    const uint16_t *len;
+    uint32_t n, W;
+    __device__ __forceinline__ uint64_t word(uint32_t j, uint32_t w) const { return w < W ? key[(uint64_t)w * n + j] : 0ull; }
+};
+
+// the first L bases of S[j] and q agree (both are at least L long: the caller checks)
+__device__ __forceinline__ bool pre_eq(const SetView &S, uint32_t j, const Query &q, uint32_t L) {
+#pragma unroll
+    for (int w = 0; w < TS_MAXW; ++w) {
+        const uint32_t b0 = 32u * w;
+        if (b0 >= L) break;
+        const uint64_t x = S.word(j, w) ^ q.w[w];
+        const uint32_t k = L - b0;
+        const uint64_t m = k >= 32 ? ~0ull : ~0ull << (64 - 2 * k);
+        if (x & m) return false;
+    }
+    return true;
+}
+// S[j] compared with q: -1, 0, 1
+__device__ __forceinline__ int cmp_q(const SetView &S, uint32_t j, const Query &q) {
+    const uint32_t W = S.W > q.W ? S.W : q.W;
+#pragma unroll
+    for (int w = 0; w < TS_MAXW; ++w) {
+        if ((uint32_t)w >= W) break;
+        const uint64_t a = S.word(j, w), b = q.w[w];
+        if (a != b) return a < b ? -1 : 1;
+    }
+    const uint32_t l = S.len[j];
+    return l < q.L ? -1 : l > q.L ? 1 : 0;
+}
+__device__ __forceinline__ bool eq_q(const SetView &S, uint32_t j, const Query &q) {
+    return S.len[j] == q.L && pre_eq(S, j, q, q.L);
+}
+__device__ __forceinline__ bool starts_q(const SetView &S, uint32_t j, const Query &q) {   // S[j].startswith(q)
+    return S.len[j] >= q.L && pre_eq(S, j, q, q.L);
+}
+__device__ __forceinline__ bool q_starts(const SetView &S, uint32_t j, const Query &q) {   // q.startswith(S[j])
+    const uint32_t l = S.len[j];
+    return l <= q.L && pre_eq(S, j, q, l);
+}
+__device__ __forceinline__ bool set_eq(const SetView &S, uint32_t i, uint32_t j) {
+    if (S.len[i] != S.len[j]) return false;
+    for (uint32_t w = 0; w < S.W; ++w)
+        if (S.key[(uint64_t)w * S.n + i] != S.key[(uint64_t)w * S.n + j]) return false;
+    return true;
+}
+// first index of the run of duplicates that ends at t (S[j] == S[t] is false, then true, on [0, t])
+__device__ __forceinline__ uint32_t run_first(const SetView &S, uint32_t t) {
+    uint32_t lo = 0, hi = t;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (set_eq(S, mid, t)) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_tag_lookup(const uint64_t *skey, const uint16_t *slen, uint32_t n, uint32_t W,
+                                                    const uint64_t *qkey, const uint16_t *qlen, uint32_t nq, uint32_t Wq,
+                                                    int adl, int4 *out) {
+    const uint32_t qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= nq) return;
+    const SetView S{skey, slen, n, W};
+    Query q;
+    q.L = qlen[qi];
+    q.W = Wq;
+#pragma unroll
+    for (int w = 0; w < TS_MAXW; ++w) q.w[w] = (uint32_t)w < Wq ? qkey[(uint64_t)w * nq + qi] : 0ull;
+
+    // lo = bisect_left(S, q)
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (cmp_q(S, mid, q) < 0) lo = mid + 1; else hi = mid;
+    }
+    int32_t f = -1;
+    uint32_t a = lo;
+    if (lo < n && eq_q(S, lo, q)) {
+        f = (int32_t)lo;
+    } else if (adl) {
+        if (lo > 0 && q_starts(S, lo - 1, q)) {          // the prefix branch: f the last duplicate, a the first
+            f = (int32_t)(lo - 1);
+            a = run_first(S, lo - 1);
+        }
+        // "more than one tag starts with q" looks at S[a + 1] only, and only when S[a] != S[a + 1]
+        if (a < n && starts_q(S, a, q) &&
+            !(a + 1 < n && !set_eq(S, a, a + 1) && starts_q(S, a + 1, q)))
+            f = (int32_t)a;
+    }
+    if (f < 0) {
+        out[qi] = make_int4(-1, -1, -1, -1);
+        return;
+    }
+    // forward: duplicates of S[a], then (allowDiffLengths) the block of strings that start with q
+    uint32_t b;
+    if (!adl) {
+        uint32_t l2 = a, h2 = n;                          // first index past the run of q
+        while (l2 < h2) {
+            const uint32_t mid = l2 + (h2 - l2) / 2;
+            if (eq_q(S, mid, q)) l2 = mid + 1; else h2 = mid;
+        }
+        b = l2 - 1;
+    } else if (lo < n && starts_q(S, lo, q)) {
+        uint32_t l2 = lo, h2 = n;                         // first index past the block that starts with q
+        while (l2 < h2) {
+            const uint32_t mid = l2 + (h2 - l2) / 2;
+            if (starts_q(S, mid, q)) l2 = mid + 1; else h2 = mid;
+        }
+        b = l2 - 1;
+    } else {
+        b = lo - 1;                                       // the prefix branch's run ends right before lo
+    }
+    // backward from b (allowDiffLengths): each run of prefixes of q, one binary search per run
+    uint32_t c = b;
+    if (adl) {
+        for (uint32_t guard = 0; c > 0 && guard <= q.L + 1; ++guard) {
+            if (!q_starts(S, c - 1, q)) break;
+            c = run_first(S, c - 1);
+        }
+    }
+    out[qi] = make_int4(f, (int32_t)a, (int32_t)b, (int32_t)c);
+}
+
+// ------------------------------------------------------------------ K4
+__global__ __launch_bounds__(256) void k_tag_varsites(const uint8_t *seqs, const uint64_t *offs, const uint32_t *idx,
+                                                      const uint64_t *goff, uint32_t ngroups, uint32_t ntags, int trim,
+                                                      uint64_t *mask, uint8_t *nonacgt) {
+    const uint32_t g = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (g >= ngroups) return;                            // wave-uniform
+    const uint64_t t0 = goff[g], t1 = goff[g + 1];
+    uint32_t minlen = 0xffffffffu;
+    for (uint64_t t = t0; t < t1; ++t) {
+        const uint32_t k = idx[t];
+        const uint32_t L = k < ntags ? (uint32_t)(offs[k + 1] - offs[k]) : 0u;
+        minlen = L < minlen ? L : minlen;
+    }
+    uint32_t seen[4] = {0, 0, 0, 0};                       // one-hot of A C G T per owned column
+    bool bad = false;
+    for (uint64_t t = t0; t < t1; ++t) {
+        const uint32_t k = idx[t];
+        if (k >= ntags) { bad = true; continue; }
+        const uint64_t s = offs[k];
+        const uint32_t L = (uint32_t)(offs[k + 1] - s);
+        const uint32_t lim = trim ? minlen : L;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const uint32_t col = lane + 64 * r;
+            if (col < L) {
+                const uint32_t ch = seqs[s + col];
+                const uint32_t v = ch == 'A' ? 1u : ch == 'C' ? 2u : ch == 'G' ? 4u : ch == 'T' ? 8u : 0u;
+                if (!v) bad = true;
+                if (col < lim) seen[r] |= v;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const uint64_t m = __ballot(__popc(seen[r]) > 1);
+        if (lane == 0) mask[4ull * g + r] = m;
+    }
+    const uint64_t anybad = __ballot(bad);
+    if (lane == 0) nonacgt[g] = anybad ? 1 : 0;
+}
+
+int ts_check_tags(const uint64_t *offs, uint32_t n, uint32_t *maxlen) {
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (offs[i + 1] < offs[i]) return td_fail_internal(TD_E_ARG, "offsets must not decrease");
+        const uint64_t L = offs[i + 1] - offs[i];
+        if (L > TD_TAGSET_MAX_LEN)
+            return td_fail_internal(TD_E_LIMIT, ("tag " + std::to_string(i) + " is longer than 256 bases").c_str());
+        m = std::max<uint32_t>(m, (uint32_t)L);
+    }
+    *maxlen = m;
+    return TD_OK;
+}
+
+// upload n tags and pack them (K1); W words per key
+int ts_pack(const char *seqs, const uint64_t *offs, uint32_t n, uint32_t W, TsBuf<uint8_t> &dseq, TsBuf<uint64_t> &doff,
+            TsBuf<uint64_t> &key, TsBuf<uint16_t> &len, TsBuf<uint32_t> &bad) {
+    const uint64_t nbytes = offs[n] - offs[0];
+    TSCHK(dseq.alloc(nbytes));
+    TSCHK(doff.alloc(n + 1ull));
+    TSCHK(key.alloc((uint64_t)W * n));
+    TSCHK(len.alloc(n));
+    TSCHK(bad.alloc(1));
+    if (nbytes) TSCHK(hipMemcpy(dseq.p, seqs + offs[0], nbytes, hipMemcpyHostToDevice));
+    std::vector<uint64_t> rel(n + 1ull);
+    for (uint64_t i = 0; i <= n; ++i) rel[i] = offs[i] - offs[0];
+    TSCHK(hipMemcpy(doff.p, rel.data(), (n + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TSCHK(hipMemset(bad.p, 0xff, sizeof(uint32_t)));
+    if (n) hipLaunchKernelGGL(k_tag_pack, dim3((n + 255) / 256), dim3(256), 0, 0, dseq.p, doff.p, n, W, key.p, len.p, bad.p);
+    TSCHK(hipGetLastError());
+    return TD_OK;
+}
+
+int ts_bad(const TsBuf<uint32_t> &bad) {
+    uint32_t b = 0;
+    TSCHK(hipMemcpy(&b, bad.p, sizeof b, hipMemcpyDeviceToHost));
+    if (b != 0xffffffffu)
+        return td_fail_internal(TD_E_ALPHABET, ("tag " + std::to_string(b) + " holds a byte outside ACGT").c_str());
+    return TD_OK;
+}
+
+float ts_elapsed(hipEvent_t a, hipEvent_t b) {
+    float f = 0;
+    return hipEventElapsedTime(&f, a, b) == hipSuccess ? f : 0.0f;
+}
+
+}  // namespace
+
+extern "C" int td_tagset_load(td_handle *h, const char *seqs, const uint64_t *offs, uint32_t n, const uint32_t *order,
+                              td_tagset **out, uint32_t *perm_out, uint32_t *passes, double *ms) {
+    if (!h || !offs || !out || (n && (!seqs || !perm_out))) return td_fail_internal(TD_E_ARG, "NULL argument");
+    *out = nullptr;
+    if (passes) *passes = 0;
+    if (ms) ms[0] = ms[1] = 0;
+    if (n > TD_TAGSET_MAX_TAGS) return td_fail_internal(TD_E_LIMIT, "more than 2^30 tags");
+    uint32_t maxlen = 0;
+    int rc = ts_check_tags(offs, n, &maxlen);
+    if (rc) return rc;
+    if (order) {
+        std::vector<uint8_t> seen(n, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (order[i] >= n || seen[order[i]]) return td_fail_internal(TD_E_ARG, "order is not a permutation");
+            seen[order[i]] = 1;
+        }
+    }
+    const uint32_t W = std::max<uint32_t>(1, (maxlen + 31) / 32);
+    TSCHK(hipSetDevice(td_handle_device(h)));
+    TsEvents ev;
+    for (auto &e : ev.e) TSCHK(hipEventCreate(&e));
+    TsBuf<uint8_t> dseq;
+    TsBuf<uint64_t> doff, key;
+    TsBuf<uint16_t> len;
+    TsBuf<uint32_t> bad, perm0, perm1, differ, hist;
+    TSCHK(hipEventRecord(ev.e[0], 0));
+    if ((rc = ts_pack(seqs, offs, n, W, dseq, doff, key, len, bad))) return rc;
+    TSCHK(hipEventRecord(ev.e[1], 0));
+    if ((rc = ts_bad(bad))) return rc;
+
+    TSCHK(perm0.alloc(n));
+    TSCHK(perm1.alloc(n));
+    TSCHK(differ.alloc(3));
+    std::vector<uint32_t> init(n);
+    for (uint32_t i = 0; i < n; ++i) init[i] = order ? order[i] : i;
+    if (n) TSCHK(hipMemcpy(perm0.p, init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TSCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
+    TSCHK(hipEventRecord(ev.e[2], 0));
+    const uint32_t nblocks = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
+    uint32_t npass = 0;
+    if (n > 1) {
+        hipLaunchKernelGGL(k_rs_same, dim3((n + 255) / 256), dim3(256), 0, 0, key.p, len.p, n, W, differ.p);
+        TSCHK(hipGetLastError());
+        uint32_t dif[3];
+        TSCHK(hipMemcpy(dif, differ.p, sizeof dif, hipMemcpyDeviceToHost));
+        TSCHK(hist.alloc(256ull * nblocks));
+        for (uint32_t p = 0; p < 2 + 8 * W; ++p) {
+            if (!((dif[p >> 5] >> (p & 31)) & 1u)) continue;
+            hipLaunchKernelGGL(k_rs_hist, dim3(nblocks), dim3(RS_THREADS), 0, 0, key.p, len.p, perm0.p, n, W, p, nblocks, hist.p);
+            hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(RS_SCAN_THREADS), 0, 0, hist.p, 256ull * nblocks);
+            hipLaunchKernelGGL(k_rs_scatter, dim3(nblocks), dim3(RS_THREADS), 0, 0, key.p, len.p, perm0.p, perm1.p, n, W, p,
+                               nblocks, hist.p);
+            TSCHK(hipGetLastError());
+            std::swap(perm0.p, perm1.p);
+            ++npass;
+        }
+    }
+    td_tagset *s = new td_tagset{td_handle_device(h), n, W, nullptr, nullptr};
+    hipError_t e1 = hipMalloc(&s->key, std::max<size_t>(1, (size_t)W * n) * sizeof(uint64_t));
+    hipError_t e2 = hipMalloc(&s->len, std::max<size_t>(1, n) * sizeof(uint16_t));
+    if (e1 != hipSuccess || e2 != hipSuccess) {
+        td_tagset_free(h, s);
+        return td_fail_internal(TD_E_HIP, "hipMalloc of the sorted set failed");
+    }
+    if (n) hipLaunchKernelGGL(k_rs_gather, dim3((n + 255) / 256), dim3(256), 0, 0, key.p, len.p, perm0.p, n, W, s->key, s->len);
+    hipError_t e3 = hipGetLastError();
+    if (e3 == hipSuccess) e3 = hipEventRecord(ev.e[3], 0);
+    if (e3 == hipSuccess) e3 = hipEventSynchronize(ev.e[3]);
+    if (e3 == hipSuccess && n) e3 = hipMemcpy(perm_out, perm0.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e3 != hipSuccess) {
+        td_tagset_free(h, s);
+        return td_fail_internal(TD_E_HIP, (std::string("td_tagset_load: ") + hipGetErrorString(e3)).c_str());
+    }
+    if (ms) {
+        ms[0] = ts_elapsed(ev.e[0], ev.e[1]);
+        ms[1] = ts_elapsed(ev.e[2], ev.e[3]);
+    }
+    if (passes) *passes = npass;
+    *out = s;
+    return TD_OK;
+}
+
+extern "C" int td_tagset_free(td_handle *h, td_tagset *s) {
+    (void)h;
+    if (!s) return TD_OK;
+    (void)hipSetDevice(s->device);
+    if (s->key) (void)hipFree(s->key);
+    if (s->len) (void)hipFree(s->len);
+    delete s;
+    return TD_OK;
+}
+
+extern "C" int td_tagset_lookup(td_handle *h, const td_tagset *s, const char *seqs, const uint64_t *offs, uint32_t nq,
+                                int allow_diff_lengths, int32_t *out, double *ms) {
+    if (!h || !s || !offs || (nq && (!seqs || !out))) return td_fail_internal(TD_E_ARG, "NULL argument");
+    if (ms) *ms = 0;
+    if (nq > TD_TAGSET_MAX_TAGS) return td_fail_internal(TD_E_LIMIT, "more than 2^30 queries");
+    uint32_t maxlen = 0;
+    int rc = ts_check_tags(offs, nq, &maxlen);
+    if (rc) return rc;
+    if (!nq) return TD_OK;
+    const uint32_t Wq = std::max<uint32_t>(1, (maxlen + 31) / 32);
+    TSCHK(hipSetDevice(s->device));
+    TsEvents ev;
+    for (auto &e : ev.e) TSCHK(hipEventCreate(&e));
+    TsBuf<uint8_t> dseq;
+    TsBuf<uint64_t> doff, key;
+    TsBuf<uint16_t> len;
+    TsBuf<uint32_t> bad;
+    TsBuf<int4> dout;
+    if ((rc = ts_pack(seqs, offs, nq, Wq, dseq, doff, key, len, bad))) return rc;
+    if ((rc = ts_bad(bad))) return rc;
+    TSCHK(dout.alloc(nq));
+    TSCHK(hipEventRecord(ev.e[0], 0));
+    hipLaunchKernelGGL(k_tag_lookup, dim3((nq + 255) / 256), dim3(256), 0, 0, s->key, s->len, s->n, s->W, key.p, len.p, nq, Wq,
+                       allow_diff_lengths ? 1 : 0, dout.p);
+    TSCHK(hipGetLastError());
+    TSCHK(hipEventRecord(ev.e[1], 0));
+    TSCHK(hipEventSynchronize(ev.e[1]));
+    if (ms) *ms = ts_elapsed(ev.e[0], ev.e[1]);
+    TSCHK(hipMemcpy(out, dout.p, nq * sizeof(int4), hipMemcpyDeviceToHost));
+    return TD_OK;
+}
+
+extern "C" int td_tagset_varsites(td_handle *h, const char *seqs, const uint64_t *offs, uint32_t ntags, const uint32_t *idx,
+                                  const uint64_t *goff, uint32_t ngroups, int trim, uint64_t *mask_out, uint8_t *nonacgt_out,
+                                  double *ms) {
+    if (!h || !offs || !goff || (ngroups && (!mask_out || !nonacgt_out)) || (ntags && !seqs))
+        return td_fail_internal(TD_E_ARG, "NULL argument");
+    if (ms) *ms = 0;
+    uint32_t maxlen = 0;
+    int rc = ts_check_tags(offs, ntags, &maxlen);
+    if (rc) return rc;
+    if (!ngroups) return TD_OK;
+    if (goff[0] != 0) return td_fail_internal(TD_E_ARG, "group offsets must start at 0");
+    for (uint32_t g = 0; g < ngroups; ++g)
+        if (goff[g + 1] <= goff[g]) return td_fail_internal(TD_E_ARG, "every group needs a tag");
+    const uint64_t nidx = goff[ngroups];
+    if (!idx) return td_fail_internal(TD_E_ARG, "NULL argument");
+    for (uint64_t t = 0; t < nidx; ++t)
+        if (idx[t] >= ntags) return td_fail_internal(TD_E_ARG, "tag index out of range");
+    TSCHK(hipSetDevice(td_handle_device(h)));
+    TsEvents ev;
+    for (int i = 0; i < 2; ++i) TSCHK(hipEventCreate(&ev.e[i]));
+    const uint64_t nbytes = offs[ntags] - offs[0];
+    TsBuf<uint8_t> dseq, dbad;
+    TsBuf<uint64_t> doff, dgoff, dmask;
+    TsBuf<uint32_t> didx;
+    TSCHK(dseq.alloc(nbytes));
+    TSCHK(doff.alloc(ntags + 1ull));
+    TSCHK(didx.alloc(nidx));
+    TSCHK(dgoff.alloc(ngroups + 1ull));
+    TSCHK(dmask.alloc(4ull * ngroups));
+    TSCHK(dbad.alloc(ngroups));
+    if (nbytes) TSCHK(hipMemcpy(dseq.p, seqs + offs[0], nbytes, hipMemcpyHostToDevice));
+    std::vector<uint64_t> rel(ntags + 1ull);
+    for (uint64_t i = 0; i <= ntags; ++i) rel[i] = offs[i] - offs[0];
+    TSCHK(hipMemcpy(doff.p, rel.data(), (ntags + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TSCHK(hipMemcpy(didx.p, idx, nidx * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TSCHK(hipMemcpy(dgoff.p, goff, (ngroups + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TSCHK(hipEventRecord(ev.e[0], 0));
+    const uint32_t grid = (ngroups + 3) / 4;
+    hipLaunchKernelGGL(k_tag_varsites, dim3(grid), dim3(256), 0, 0, dseq.p, doff.p, didx.p, dgoff.p, ngroups, ntags, trim ? 1 : 0,
+                       dmask.p, dbad.p);
+    TSCHK(hipGetLastError());
+    TSCHK(hipEventRecord(ev.e[1], 0));
+    TSCHK(hipEventSynchronize(ev.e[1]));
+    if (ms) *ms = ts_elapsed(ev.e[0], ev.e[1]);
+    TSCHK(hipMemcpy(mask_out, dmask.p, 4ull * ngroups * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    TSCHK(hipMemcpy(nonacgt_out, dbad.p, ngroups, hipMemcpyDeviceToHost));
+    return TD_OK;
+}

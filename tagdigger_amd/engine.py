@@ -60,6 +60,24 @@ def _c_strings(strings):
     return arr
 
 
+class TagSet:
+    """A sorted tag set resident on the device (td_tagset_load); freed by close() or when collected."""
+
+    def __init__(self, eng, ptr, n):
+        self._eng, self.ptr, self.n = eng, ptr, n
+
+    def close(self):
+        if self.ptr and self.ptr.value and getattr(self._eng, "_h", None):
+            self._eng._L.td_tagset_free(self._eng._h, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """Owns a td_handle on one GPU."""
 
@@ -344,6 +362,55 @@ class Engine:
                                               sizes.ctypes.data_as(C.c_void_p), len(jobs), buf.ctypes.data_as(C.c_void_p),
                                               cap, C.byref(n), C.byref(ms)))
         return buf[:n.value].tobytes(), ms.value
+
+    # ------------------------------------------------------------------ Tag Manager (tag sets)
+    def tagset_load(self, seqs, offs, order=None):
+        """K1 + K2 (td_tagset_load): seqs is the tags' ASCII bytes, offs their uint64 offsets (n + 1), order the tags
+        sorted by name (None: as given).  Returns (TagSet resident on the device, uint32 sorted position -> input
+        index, radix passes run, (K1 ms, K2 ms))."""
+        import numpy as np
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = len(offs) - 1
+        buf = np.frombuffer(seqs, dtype=np.uint8) if len(seqs) else np.zeros(1, dtype=np.uint8)
+        ordp = None
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            ordp = order.ctypes.data_as(C.c_void_p)
+        perm = np.zeros(max(1, n), dtype=np.uint32)
+        out, passes, ms = C.c_void_p(), C.c_uint32(0), (C.c_double * 2)()
+        B.check(self._L.td_tagset_load(self._h, buf.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), n, ordp,
+                                       C.byref(out), perm.ctypes.data_as(C.c_void_p), C.byref(passes), ms))
+        return TagSet(self, out, n), perm[:n], passes.value, (ms[0], ms[1])
+
+    def tagset_lookup(self, tagset, seqs, offs, allow_diff_lengths):
+        """K3 (td_tagset_lookup): int32 [nq, 4] = f, a, b, c per query (sorted positions, -1: nothing found), device ms."""
+        import numpy as np
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        nq = len(offs) - 1
+        buf = np.frombuffer(seqs, dtype=np.uint8) if len(seqs) else np.zeros(1, dtype=np.uint8)
+        out = np.zeros((max(1, nq), 4), dtype=np.int32)
+        ms = C.c_double(0)
+        B.check(self._L.td_tagset_lookup(self._h, tagset.ptr, buf.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                         nq, 1 if allow_diff_lengths else 0, out.ctypes.data_as(C.c_void_p), C.byref(ms)))
+        return out[:nq], ms.value
+
+    def tagset_varsites(self, seqs, offs, idx, goff, trim):
+        """K4 (td_tagset_varsites): uint64 [groups, 4] column masks, uint8 [groups] non-ACGT flags, device ms."""
+        import numpy as np
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        goff = np.ascontiguousarray(goff, dtype=np.uint64)
+        ng = len(goff) - 1
+        buf = np.frombuffer(seqs, dtype=np.uint8) if len(seqs) else np.zeros(1, dtype=np.uint8)
+        idxb = idx if len(idx) else np.zeros(1, dtype=np.uint32)
+        mask = np.zeros((max(1, ng), 4), dtype=np.uint64)
+        bad = np.zeros(max(1, ng), dtype=np.uint8)
+        ms = C.c_double(0)
+        B.check(self._L.td_tagset_varsites(self._h, buf.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                           len(offs) - 1, idxb.ctypes.data_as(C.c_void_p), goff.ctypes.data_as(C.c_void_p),
+                                           ng, 1 if trim else 0, mask.ctypes.data_as(C.c_void_p),
+                                           bad.ctypes.data_as(C.c_void_p), C.byref(ms)))
+        return mask[:ng], bad[:ng], ms.value
 
     # ------------------------------------------------------------------ results
     def stats(self):
