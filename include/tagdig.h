@@ -324,6 +324,23 @@ int td_tagset_varsites(td_handle *h, const char *seqs, const uint64_t *offs, uin
                        const uint64_t *goff, uint32_t ngroups, int trim, uint64_t *mask_out, uint8_t *nonacgt_out,
                        double *ms);
 
+/* ---- MD5 sums of many messages (writeMD5sums, tagdigger_fun.py:1370-1386; csrc/md5.hip) -----------------------------
+ *
+ * One lane per message (k_md5_update): a message's 64-byte blocks are one dependent chain, the messages are
+ * independent.
+ *
+ * MD5 (RFC 1321) of n messages that lie whole in device memory: message i is d_data[offs[i] .. offs[i+1]) (offs: host
+ * memory, n + 1 entries, not decreasing; any alignment).  digests[16 i .. 16 i + 15] = the digest's bytes in the order
+ * hexdigest() prints them.  ms (optional): device time. */
+int td_md5_device(td_handle *h, const void *d_data, const uint64_t *offs, uint32_t n, uint8_t *digests, double *ms);
+
+/* The same for n files read from disk, of any size, streamed (writeMD5sums, tagdigger_fun.py:1376-1384): rounds of one
+ * piece per unfinished file through two pinned slots, the reading of a round overlapping copy and kernel of the round
+ * before.  A piece is 1 MiB (less when that would make a round exceed 384 MiB; option "md5_piece" sets it for tests).
+ * TD_E_IO names the first file (lowest index) that cannot be opened or read; *bad_index (optional) receives it.
+ * ms (optional): [0] reading into the slots, [1] waiting for the GPU, [2] kernel time. */
+int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, uint8_t *digests, uint32_t *bad_index, double ms[3]);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */
@@ -401,6 +418,7 @@ int64_t td_format_csv_row(const int64_t *vals, uint64_t n, char *out, uint64_t c
  *   "gpu_inflate"    1 (default): BGZF members are inflated on the GPU; 0: on host threads
  *   "gpu_inflate_crc" 1 (default): every member's CRC-32 is checked on the device
  *   "zb_members"     BGZF members per GPU batch (tests; the built-in 49 152 is also the maximum)
+ *   "md5_piece"      td_md5_files: bytes a file contributes per round (tests; a multiple of 64, 0 = the built-in size)
  *   "debug_ablate"   timing-only ablation bits -- the counts are WRONG when non-zero
  * Returns TD_E_ARG for unknown names. */
 int td_set_option(td_handle *h, const char *name, int64_t value);

@@ -145,6 +145,8 @@ def load():
     sig("td_tagset_free", i32, vp, vp)
     sig("td_tagset_lookup", i32, vp, vp, vp, vp, u32, i32, vp, dp)
     sig("td_tagset_varsites", i32, vp, vp, vp, u32, vp, vp, u32, i32, vp, vp, dp)
+    sig("td_md5_device", i32, vp, vp, vp, u32, vp, dp)
+    sig("td_md5_files", i32, vp, pp, u32, vp, C.POINTER(u32), dp)
     _lib = L
     return L
 
@@ -161,6 +163,7 @@ EXPORTS = [
     "td_device_sync", "td_synth_fill_device", "td_synth_expected_device",
     "td_fasta_frame_device", "td_frag_search_device", "td_frag_gather_device",
     "td_tagset_load", "td_tagset_free", "td_tagset_lookup", "td_tagset_varsites",
+    "td_md5_device", "td_md5_files",
 ]
 
 

@@ -232,6 +232,7 @@ struct td_handle {
     int last_gz_route = 0;                    // how the last .gz file was decoded: 1 Huffman + LZ77 on the GPU, 0 otherwise
     int gpu_huffman = 1;                      // ordinary gzip: Huffman decoding on the GPU too (0: host threads decode, the GPU resolves)
     uint64_t gz_gpu_min = (uint64_t)8 << 20;  // ... for files of this many compressed bytes and more
+    uint64_t md5_piece = 0;                   // (tests) td_md5_files: bytes a file contributes per round; 0 = the built-in 1 MiB
     uint32_t gz_gpu_terr_kb = 128;            // ... one chunk per this much compressed data
     int gz_gpu_verify = 0;                    // ... the block search decodes a block before it believes its header
     uint32_t gz_gpu_seg_kb = 1u << 20, gz_gpu_margin_kb = 16384;      // ... a segment of compressed data (1 GiB), and how far its last chunk may run past it
@@ -683,6 +684,10 @@ __attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h) {
 uint32_t td_last_bad_index(void) { return g_bad; }
 
 }  // extern "C"
+namespace { inline int stage_threads(); }
+// for csrc/md5.hip (hidden): the "md5_piece" option and the number of staging threads
+extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h) { return h->md5_piece; }
+extern "C" __attribute__((visibility("hidden"))) int td_stage_thread_count(void) { return stage_threads(); }
 namespace { void handle_born(); void handle_gone(); }   // (the pinned pool of the gzip decoder follows the handles' lives: below)
 extern "C" {
 int td_create(td_handle **out, int device_id) {
@@ -2638,6 +2643,7 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
     else if (n == "split_kernel") h->split_kernel = value == 1 ? 1 : 2;
     else if (n == "gpu_huffman") h->gpu_huffman = value ? 1 : 0;
     else if (n == "gz_gpu_min") h->gz_gpu_min = (uint64_t)std::max<long long>(0, value);
+    else if (n == "md5_piece") { if (value < 0 || value % 64) return fail(TD_E_ARG, "md5_piece: a multiple of 64, or 0"); h->md5_piece = (uint64_t)value; }
     else if (n == "gz_gpu_terr_kb") { if (value < 16 || value > 4096) return fail(TD_E_ARG, "gz_gpu_terr_kb: 16..4096"); h->gz_gpu_terr_kb = (uint32_t)value; }
     else if (n == "gz_gpu_release") { h->gzgpu.release(); }
     else if (n == "gz_gpu_verify") h->gz_gpu_verify = value ? 1 : 0;

@@ -412,6 +412,36 @@ class Engine:
                                            bad.ctypes.data_as(C.c_void_p), C.byref(ms)))
         return mask[:ng], bad[:ng], ms.value
 
+    # ------------------------------------------------------------------ MD5 sums (csrc/md5.hip)
+    def md5_device(self, d_ptr, offs):
+        """td_md5_device: MD5 of the messages d_ptr[offs[i] .. offs[i + 1]) in device memory, one per lane.
+        Returns (list of 16-byte digests, device ms)."""
+        import numpy as np
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = len(offs) - 1
+        out = np.zeros((max(1, n), 16), dtype=np.uint8)
+        ms = C.c_double(0)
+        B.check(self._L.td_md5_device(self._h, d_ptr, offs.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p),
+                                      C.byref(ms)))
+        return [out[i].tobytes() for i in range(n)], ms.value
+
+    def md5_files(self, paths):
+        """td_md5_files: MD5 of every file, streamed through the device, one file per lane.  Returns (list of 16-byte
+        digests, (ms reading, ms waiting for the GPU, ms in the kernel)); a file that cannot be opened or read raises
+        TagdigError (TD_E_IO) with the file's position in `bad_index`."""
+        import numpy as np
+        n = len(paths)
+        arr = (C.c_char_p * max(1, n))(*[os.fsencode(p) for p in paths])
+        out = np.zeros((max(1, n), 16), dtype=np.uint8)
+        bad, ms = C.c_uint32(0), (C.c_double * 3)()
+        rc = self._L.td_md5_files(self._h, arr, n, out.ctypes.data_as(C.c_void_p), C.byref(bad), ms)
+        if rc == -11:
+            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err.bad_index = bad.value
+            raise err
+        B.check(rc)
+        return [out[i].tobytes() for i in range(n)], (ms[0], ms[1], ms[2])
+
     # ------------------------------------------------------------------ results
     def stats(self):
         st = (C.c_uint64 * B.TD_STAT_NSTATS)()

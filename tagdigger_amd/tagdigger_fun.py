@@ -1520,3 +1520,88 @@ def set_directory_interactive():
     for entry in _os.listdir('.'):
         print(entry)
     return None
+
+
+# ------------------------------------------------------------------ MD5 sums of the split files (reference :1370-1386)
+# Shortest file list that backend="gpu" hashes on the device (one file per lane, csrc/md5.hip); None: no list is.
+# Measured (profiles/md5/bench_mi355x.txt) at 1, 8, 64, 96 and 384 files of 16.6 MB: 384 is the shortest list at which
+# the device route beat the host's 16 threads by more than the spread between rounds (0.30 against 0.43 s, spread 6 %);
+# at 96 files it lost (0.21 against 0.11 s): a lane hashes 0.1 GB/s, so the lanes must outnumber the cores' lead.
+_MD5_DEVICE_MIN_FILES = 384
+_MD5_HOST_THREADS = 16
+
+
+def _md5_file_host(path):
+    import hashlib
+    m = hashlib.md5()
+    with open(path, 'rb') as con:
+        while True:
+            chunk = con.read(8 * 1048576)
+            if chunk == b'':
+                break
+            m.update(chunk)
+    return m.hexdigest()
+
+
+def _md5_on_device(backend, nfiles):
+    return backend == "gpu" and _MD5_DEVICE_MIN_FILES is not None and nfiles >= _MD5_DEVICE_MIN_FILES
+
+
+def _md5_hex(filelist, device, on_device):
+    """(hexdigest of every file in front of the first one that cannot be read, that file's index or None)."""
+    if not filelist:
+        return [], None
+    if on_device:
+        from ._binding import TagdigError
+        try:
+            digests, _ = default_engine(device).md5_files(filelist)
+        except TagdigError as err:
+            if err.code != -11:
+                raise
+            bad = err.bad_index
+            done, earlier = _md5_hex(filelist[:bad], device, True)
+            return done, bad if earlier is None else earlier
+        return [d.hex() for d in digests], None
+    from concurrent.futures import ThreadPoolExecutor     # (hashlib releases the GIL while it hashes)
+
+    def job(path):
+        try:
+            return _md5_file_host(path)
+        except OSError as err:
+            return err
+    with ThreadPoolExecutor(max_workers=min(_MD5_HOST_THREADS, len(filelist))) as pool:
+        results = list(pool.map(job, filelist))
+    for k, r in enumerate(results):
+        if not isinstance(r, str):
+            return results[:k], k
+    return results, None
+
+
+def writeMD5sums(filelist, outfile, device=0, backend="gpu"):
+    """CSV of file names and MD5 checksums, and one right-aligned line per file on stdout (reference :1370-1386).
+    backend="gpu" hashes a list of _MD5_DEVICE_MIN_FILES files or more on the device, one file per lane
+    (td_md5_files); a shorter list, and backend="host", on a pool of host threads.  A file that cannot be opened raises
+    what the reference's open() raises, after the rows and lines of the files in front of it."""
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    maxfilelen = max([len(f) for f in filelist])
+    with open(outfile, mode='w', newline='') as csvcon:
+        cw = _csv.writer(csvcon)
+        cw.writerow(["File name", "MD5 sum"])
+        sums, failed = _md5_hex(list(filelist), device, _md5_on_device(backend, len(filelist)))
+        for f, digest in zip(filelist, sums):
+            cw.writerow([f, digest])
+            print("{:>{width}} {}".format(f, digest, width=maxfilelen))
+        if failed is not None:
+            open(filelist[failed], 'rb').close()
+            raise OSError("cannot read {}".format(filelist[failed]))
+    return None
+
+
+def remove_monomorphic_loci(namelist, seqlist, verbose=False):
+    """[names, sequences] of the tags whose marker has more than one tag, marker by marker (reference :1907-1924)."""
+    assert len(namelist) == len(seqlist)
+    keep = [i for _, indices in extractMarkers(namelist)[1] if len(indices) > 1 for i in indices]
+    if verbose:
+        print("{} tags removed belonging to monomorphic loci".format(len(seqlist) - len(keep)))
+    return [[namelist[i] for i in keep], [seqlist[i] for i in keep]]
