@@ -341,6 +341,49 @@ int td_md5_device(td_handle *h, const void *d_data, const uint64_t *offs, uint32
  * ms (optional): [0] reading into the slots, [1] waiting for the GPU, [2] kernel time. */
 int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, uint8_t *digests, uint32_t *bad_index, double ms[3]);
 
+/* ---- tag census (csrc/census.hip; tagdigger_amd/tagdigger_fun.py tag_census drives these) ---------------------------
+ *
+ * Which sequences follow the barcodes of a library, and how often: for every read with a barcode + cut site (the
+ * counter's rule, tagdigger_fun.py:250-259) the window line1[len(barcode) : len(barcode) + taglen] -- from the cut
+ * site's first base on -- is counted in a table in device memory.  A window the line is too short for counts as
+ * `short`, one that holds anything but ACGT as `ambiguous`.  Census state is independent of the count index
+ * (td_set_index): one handle can hold both.
+ *
+ * td_census_begin: the barcode + cut-site index by td_set_index's rules, from the same list (barcut[n_barcut], entry k
+ *   belongs to barcode k % barnum; TD_E_OVERLAP / TD_E_EMPTY / TD_E_ROOTLEAF / TD_E_ALPHABET / TD_E_LIMIT and
+ *   td_last_bad_index as there); baroff[barnum] = len(barcode), at most 32; taglen 1 .. TD_CENSUS_MAX_TAGLEN.  The table
+ *   gets `slots` slots (a power of two, 1024 .. 2^32; 0: 2^22) of 16 bytes (taglen <= 32) or 32 bytes, zeroed, and takes
+ *   3/4 of them in distinct windows.  A census begun before is dropped.
+ * td_census_device: one pass over a resident buffer (arguments as td_count_device's).  Asynchronous, accumulates; ONE
+ *   stream in flight per handle.  What a kernel flags is reported by the calls below.
+ * td_census_file: a whole file, plain, gzip or BGZF, through td_count_file's readers.  Synchronous, accumulates.
+ * td_census_stats: out[TD_CENSUS_*], cumulative since td_census_begin.  Synchronises.
+ * td_census_fetch: the windows with count >= min_count (0 counts as 1), ordered by count descending, then sequence
+ *   ascending (A < C < G < T): window k as taglen characters at seqs_out[k * taglen] (no terminator) and its count in
+ *   counts_out[k], for k < capacity; *n_out = how many there are, whatever capacity holds.  Synchronises.
+ * td_census_end: frees the census.
+ * Errors: TD_E_NONASCII as the counter's; TD_E_LIMIT when the table is full (the message names slots and the keys
+ *   placed); TD_E_INTERNAL when a bounded wait ran out.  After any of them, and after a td_census_file that failed
+ *   part-way, every call answers with that error until td_census_begin: a partly right census is never handed out. */
+enum {
+    TD_CENSUS_READS = 0,      /* read lines looked at (readscount of :255)                              */
+    TD_CENSUS_BARCUT = 1,     /* ... with barcode + cut site: TD_STAT_BARCUT of a count pass            */
+    TD_CENSUS_SHORT = 2,      /* ... whose line ends inside the window                                  */
+    TD_CENSUS_AMBIGUOUS = 3,  /* ... whose window holds a character outside ACGT                        */
+    TD_CENSUS_COUNTED = 4,    /* barcut - short - ambiguous                                             */
+    TD_CENSUS_DISTINCT = 5,   /* distinct windows in the table                                          */
+    TD_CENSUS_SLOTS = 6,      /* the table's slots                                                      */
+    TD_CENSUS_MAX_KEYS = 7,   /* distinct windows it takes                                              */
+    TD_CENSUS_MAX_TAGLEN = 64
+};
+int td_census_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *baroff,
+                    uint32_t taglen, uint64_t slots);
+int td_census_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream);
+int td_census_file(td_handle *h, const char *path, uint64_t max_reads);
+int td_census_stats(td_handle *h, uint64_t out[8]);
+int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *counts_out, uint64_t capacity, uint64_t *n_out);
+int td_census_end(td_handle *h);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */
@@ -383,7 +426,8 @@ int64_t td_format_csv_row(const int64_t *vals, uint64_t n, char *out, uint64_t c
  * TAGDIG_ZLIB             set: ordinary gzip through zlib's gzread, BGZF members through zlib's inflate
  * TAGDIG_SPLIT_THREADS    writer threads of td_split_file (default 16, at most the host's cores and the number of barcodes)
  * TAGDIG_SPLIT_TIMING     set: td_split_file reports where its wall time went, on stderr
- * TAGDIG_SPLIT_DISCARD    set: td_split_file assembles the records but writes nothing (timing only) */
+ * TAGDIG_SPLIT_DISCARD    set: td_split_file assembles the records but writes nothing (timing only)
+ * TAGDIG_CENSUS_COMBINE   0: the census kernel sends every window to the table by itself (measurements; read at td_census_begin) */
 
 /* ---- tuning / introspection ------------------------------------------------ */
 /* Defaults are the measured best; every setting gives the same counts.  name:

@@ -147,6 +147,12 @@ def load():
     sig("td_tagset_varsites", i32, vp, vp, vp, u32, vp, vp, u32, i32, vp, vp, dp)
     sig("td_md5_device", i32, vp, vp, vp, u32, vp, dp)
     sig("td_md5_files", i32, vp, pp, u32, vp, C.POINTER(u32), dp)
+    sig("td_census_begin", i32, vp, pp, u32, u32, C.POINTER(u32), u32, u64)
+    sig("td_census_device", i32, vp, vp, u64, u64, u64, vp)
+    sig("td_census_file", i32, vp, C.c_char_p, u64)
+    sig("td_census_stats", i32, vp, C.POINTER(u64))
+    sig("td_census_fetch", i32, vp, u64, vp, vp, u64, C.POINTER(u64))
+    sig("td_census_end", i32, vp)
     _lib = L
     return L
 
@@ -164,6 +170,7 @@ EXPORTS = [
     "td_fasta_frame_device", "td_frag_search_device", "td_frag_gather_device",
     "td_tagset_load", "td_tagset_free", "td_tagset_lookup", "td_tagset_varsites",
     "td_md5_device", "td_md5_files",
+    "td_census_begin", "td_census_device", "td_census_file", "td_census_stats", "td_census_fetch", "td_census_end",
 ]
 
 

@@ -109,19 +109,8 @@ __device__ __forceinline__ int2 split_line(const SplitParams &p, const unsigned 
     if (nvalid > len) nvalid = (uint32_t)len;
     // (bases past the valid ones must not take part: the index compares whole prefixes)
     const unsigned long long K = nvalid >= 32 ? Kfull : nvalid == 0 ? 0ull : Kfull & (~0ull << (64 - 2 * nvalid));
-    uint32_t ci = L_bdir[(uint32_t)(K >> (64 - 2 * BDIR_BASES))];
     uint32_t meta = 0;
-    bool hit = false;
-    if (ci != 0xFFFFu) {
-        for (;;) {
-            const uint32_t m = L_bmeta[ci];
-            const uint32_t l = m & 63u;
-            if (l <= nvalid && ((K ^ L_bval[ci]) >> (64u - 2u * l)) == 0) { meta = m; hit = true; break; }
-            if (m & BMETA_LAST) break;
-            ci++;
-        }
-    }
-    if (!hit) return make_int2(-1, 999);
+    if (!barcode_lookup(L_bval, L_bmeta, L_bdir, K, nvalid, meta)) return make_int2(-1, 999);
     const uint32_t bar = meta >> 16;
     const uint64_t start = ((meta >> 6) & 63u) + p.cutlen;           // searchstart = len(barcode) + len(cutsite)
 

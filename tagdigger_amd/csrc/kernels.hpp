@@ -347,6 +347,24 @@ struct TileCtx {
 #endif
 };
 
+// sequence_index_lookup on the barcode + cut site index (reference :257): K = the read's first 32 bases, packed, the
+// first base in the top bits; nvalid = how many of its leading bytes are bases.  An entry matches when all of its
+// bases are the read's first ones; the survivors of the index build are prefix-free, so at most one does.
+// meta: that entry's bmeta word (length | tag offset << 6 | row << 16).  (match_stream below keeps its own copy of this
+// walk: the main pass's instruction schedule was tuned around it.)
+__device__ __forceinline__ bool barcode_lookup(const unsigned long long *L_bval, const uint32_t *L_bmeta, const uint16_t *L_bdir,
+                                               uint64_t K, uint32_t nvalid, uint32_t &meta) {
+    uint32_t ci = L_bdir[(uint32_t)(K >> (64 - 2 * BDIR_BASES))];     // entries of a bucket are contiguous
+    if (ci == 0xFFFFu) return false;
+    for (;;) {
+        const uint32_t m = L_bmeta[ci];
+        const uint32_t len = m & 63u;
+        if (len <= nvalid && ((K ^ L_bval[ci]) >> (64u - 2u * len)) == 0) { meta = m; return true; }
+        if (m & BMETA_LAST) return false;
+        ci++;
+    }
+}
+
 // gpos: absolute position of the line's first byte; srel: the same relative to the tile (fast mode).
 // Fast mode reads packed chunks from LDS; slow mode re-reads raw bytes from global memory (leading
 // blanks to strip, :256, or a window beyond what is staged).  Returns R_NONE (no barcode+site),

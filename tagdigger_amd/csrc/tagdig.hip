@@ -33,6 +33,7 @@
 #include "gpu_inflate.hpp"
 #include "gz_resolve.hpp"
 #include "gz_gpu.hpp"
+#include "piece_sink.hpp"
 
 namespace {
 
@@ -148,6 +149,8 @@ constexpr size_t STATS_SLOTS = 32;           // TD_STAT_NSTATS public + diagnost
 
 struct td_handle {
     int device = 0;
+    const td_piece_sink *sink = nullptr;
+    void *census = nullptr;                   // csrc/census.hip's state (td_census_begin .. td_census_end)
     int num_cu = 256;
     hipStream_t copy_stream = nullptr, work_stream = nullptr;
     // (one copy engine moves 22-30 GB/s out of pinned memory that lies on the far socket, two or three together 50: large
@@ -421,6 +424,7 @@ int flush_counts(td_handle *h) {
 int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads,
                  int weights, hipStream_t stream, const unsigned long long *cursor_in = nullptr,
                  unsigned long long *cursor_out = nullptr, uint64_t first_line_ub = 0) {
+    if (h->sink) return h->sink->piece(h->sink->ctx, d_fastq, nbytes, first_line, max_reads, stream, cursor_in, cursor_out);
     if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
     if (((uintptr_t)d_fastq & 15) != 0) return fail(TD_E_ARG, "device FASTQ pointer must be 16-byte aligned");
     if (nbytes == 0) return TD_OK;
@@ -688,6 +692,44 @@ namespace { inline int stage_threads(); }
 // for csrc/md5.hip (hidden): the "md5_piece" option and the number of staging threads
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h) { return h->md5_piece; }
 extern "C" __attribute__((visibility("hidden"))) int td_stage_thread_count(void) { return stage_threads(); }
+// for csrc/census.hip (hidden): its state's place on the handle, the work stream, the CU count; the barcode + cut-site
+// index by td_set_index's rules; the handle's line counting and tile scan
+extern "C" __attribute__((visibility("hidden"))) void **td_handle_census(td_handle *h) { return &h->census; }
+extern "C" __attribute__((visibility("hidden"))) void *td_handle_work_stream(const td_handle *h) { return (void *)h->work_stream; }
+extern "C" __attribute__((visibility("hidden"))) int td_handle_num_cu(const td_handle *h) { return h->num_cu; }
+extern "C" __attribute__((visibility("hidden"))) void td_census_release(td_handle *h);     // (census.hip)
+extern "C" __attribute__((visibility("hidden"))) int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
+                                                                    uint8_t **blob_out, uint32_t *bytes, uint32_t *off_bmeta, uint32_t *off_bdir) {
+    std::vector<std::string> bs(n_barcut);
+    for (uint32_t i = 0; i < n_barcut; i++) bs[i] = barcut[i];
+    Resolver rb(bs, barnum);
+    int rc = rb.run();
+    if (rc) { g_bad = rb.bad; return fail(rc, rc == TD_E_OVERLAP ? "overlapping barcode+cutsite sequences" : "barcode index build failed"); }
+    std::vector<uint8_t> blob;
+    uint32_t max_off = 0;
+    rc = build_barcode_blob(rb.out, barnum, tagoff, blob, *off_bmeta, *off_bdir, max_off);
+    if (rc) return rc;
+    *blob_out = (uint8_t *)malloc(blob.size());
+    if (!*blob_out) return fail(TD_E_INTERNAL, "out of memory");
+    memcpy(*blob_out, blob.data(), blob.size());
+    *bytes = (uint32_t)blob.size();
+    return TD_OK;
+}
+// terminators before the end of every 16 KiB tile (k_count_lines<4>; census.hip asserts that its tile is this one) of the buffer -> *prefix (FLAG_INC | count; the handle's scratch, good
+// until its next launch), their total -> *d_total; asynchronous on `s`
+extern "C" __attribute__((visibility("hidden"))) int td_line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, void *s, const uint64_t **prefix,
+                                                                    unsigned long long *d_total) {
+    const uint64_t nt = (nbytes + 16383) / 16384;
+    if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
+    int rc = h->d_tilecounts.ensure(nt); if (rc) return rc;
+    rc = h->d_state.ensure(nt); if (rc) return rc;
+    const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
+    hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, (hipStream_t)s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
+    hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, (hipStream_t)s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, d_total);
+    HIPCHK(hipGetLastError());
+    *prefix = h->d_state.p;
+    return TD_OK;
+}
 namespace { void handle_born(); void handle_gone(); }   // (the pinned pool of the gzip decoder follows the handles' lives: below)
 extern "C" {
 int td_create(td_handle **out, int device_id) {
@@ -723,6 +765,7 @@ void td_destroy(td_handle *h) {
     handle_gone();
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
+    td_census_release(h);
     h->d_bblob.release(); h->d_slots.release(); h->d_shorts.release(); h->d_counts.release();
     if (h->pin_cursor) (void)hipHostFree(h->pin_cursor);
     h->d_win.release(); h->d_tilesums.release(); h->d_f4np.release(); h->d_sp_entries16.release(); h->d_sp_e8.release(); h->d_sp_pool2.release();
@@ -1935,7 +1978,7 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         if (last) break;
         if (h->pin_cursor[0] >= stop_line) break;                          // (the segments counted so far already hold read number max_reads)
     }
-    h->last_gz_route = 1;
+    if (!h->sink) h->last_gz_route = 1;       // (td_last_gz_route speaks of the files td_count_file counted only)
     if (zs.verbose)
         fprintf(stderr, "count_gzip_gpu: %lu segments in %.1f ms: upload %.1f, block search %.1f, Huffman decoding %.1f, symbols + windows + bytes + CRC %.1f ms\n",
                 (unsigned long)zs.segments, (tdhost::ParInflate::now() - t0) * 1e3, zs.t_up * 1e3, zs.t_find * 1e3, zs.t_tok * 1e3, zs.t_rest * 1e3);
@@ -1959,8 +2002,8 @@ int count_gz_by_reference_rules(td_handle *h, const char *path, uint64_t max_rea
     if (v.kind != tdhost::GZ_OK) return fail(gz_code(v.kind), v.message);
     if (!was_fresh)
         return fail(rc, refusal + " (the reference's loop ends before it meets this; the results were accumulating, so the file is not counted again)");
-    int rc2 = zero_results(h); if (rc2) return rc2;
-    if (h->bound_counts) {
+    int rc2 = h->sink ? h->sink->restart(h->sink->ctx) : zero_results(h); if (rc2) return rc2;
+    if (h->bound_counts && !h->sink) {
         HIPCHK(hipMemsetAsync(h->bound_counts, 0, (size_t)h->barnum * h->ntags * 4, h->work_stream));
         HIPCHK(hipStreamSynchronize(h->work_stream));
     }
@@ -2322,15 +2365,27 @@ static int gunzip_fast(const char *path, void *dst, uint64_t capacity, uint64_t 
     return TD_OK;
 }
 
+static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, int weights);
 int td_count_file(td_handle *h, const char *path, uint64_t max_reads, int weights) {
     if (!h || !path) return fail(TD_E_ARG, "NULL argument");
     if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
     HIPCHK(hipSetDevice(h->device));
+    return count_file_impl(h, path, max_reads, weights);
+}
+// for csrc/census.hip (hidden): the file through td_count_file's readers, its pieces handed to `sink`
+__attribute__((visibility("hidden"))) int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink) {
+    HIPCHK(hipSetDevice(h->device));
+    h->sink = sink;
+    const int rc = count_file_impl(h, path, max_reads, 0);
+    h->sink = nullptr;
+    return rc;
+}
+static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, int weights) {
     const size_t len = strlen(path);
     const bool gz = len >= 2 && (path[len - 2] == 'g' || path[len - 2] == 'G') && (path[len - 1] == 'z' || path[len - 1] == 'Z');
     if (gz) {
-        const bool was_fresh = !h->counted;
-        h->last_gz_route = 0;
+        const bool was_fresh = h->sink ? h->sink->fresh : !h->counted;
+        if (!h->sink) h->last_gz_route = 0;
         auto fast = [&]() -> int {
             {   // (an empty file: gzip.open reads it as no data at all)
                 struct stat sb0;

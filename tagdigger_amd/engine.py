@@ -38,6 +38,22 @@ def combine_barcode_and_cutsite(barcodes, cutsite):
     return [(barcode + cutsite).upper() for barcode in barcodes]
 
 
+def census_index(barcodes, cutsite):
+    """What a tag census hands to td_census_begin: the barcode + cut site list of find_tags_fastq
+    (tagdigger_fun.py:198-219: its asserts, every cut-site variant), the number of barcodes, and where
+    the window starts in a read -- behind the barcode, on the cut site's first base."""
+    assert all([set(barcode.upper()) <= set('ACGT') for barcode in barcodes]), "Non-ACGT barcode."
+    cutsite = cutsite.upper()
+    assert set(cutsite) <= set('ACGTNRYKMSWBDHV'), "Invalid cut site."
+    barcut = []
+    for cut in enumerate_cut_sites(cutsite):
+        barcut += combine_barcode_and_cutsite(barcodes, cut)
+    return barcut, len(barcodes), [len(x) for x in barcodes]
+
+
+CENSUS_STATS = ("reads", "barcut", "short", "ambiguous", "counted", "distinct", "slots", "max_keys")
+
+
 def effective_maxreads(maxreads):
     """The reference tests `readscount >= maxreads` after each read
     (tagdigger_fun.py:272-273): one read is always processed and a fractional
@@ -314,6 +330,52 @@ class Engine:
         without host lists."""
         arr = (C.c_uint32 * max(1, self.barnum))(*rows)
         B.check(self._L.td_fold_rows(self._h, arr, n_dst_rows, C.c_void_p(d_dst), C.c_void_p(stream) if stream else None))
+
+    # ------------------------------------------------------------------ tag census (td_census_*)
+    def census_begin(self, barcodes, cutsite="TGCAG", taglen=64, slots=0):
+        """A fresh census of the windows of `taglen` bases behind these barcodes (a power of two of slots; 0: 2^22)."""
+        barcut, barnum, baroff = census_index(barcodes, cutsite)
+        B.check(self._L.td_census_begin(self._h, _c_strings(barcut), len(barcut), barnum,
+                                        (C.c_uint32 * max(1, barnum))(*baroff), int(taglen), int(slots)))
+        self._census_taglen = int(taglen)
+
+    def census_device(self, d_ptr, nbytes, first_line=0, maxreads=5e9, stream=0):
+        """Enqueue one census pass over a FASTQ buffer already in HBM (asynchronous, accumulates)."""
+        B.check(self._L.td_census_device(self._h, C.c_void_p(d_ptr), nbytes, first_line, effective_maxreads(maxreads),
+                                         C.c_void_p(stream) if stream else None))
+
+    def census_file(self, path, maxreads=5e9):
+        """The census over a file, plain or gzip by name, through count_file's readers (accumulates)."""
+        open(path, 'rb').close()
+        B.check(self._L.td_census_file(self._h, os.fsencode(path), effective_maxreads(maxreads)))
+
+    def census_stats(self):
+        """{reads, barcut, short, ambiguous, counted, distinct, slots, max_keys}, cumulative since census_begin."""
+        st = (C.c_uint64 * 8)()
+        B.check(self._L.td_census_stats(self._h, st))
+        return dict(zip(CENSUS_STATS, (int(x) for x in st)))
+
+    def census_fetch(self, min_count=1, top=None):
+        """(windows, counts) with count >= min_count, by count descending, then sequence; `top`: the first N of them."""
+        L = getattr(self, "_census_taglen", 0)
+        n = C.c_uint64(0)
+        if top is None or not L:              # (how many there are; without a census: the library's TD_E_STATE)
+            B.check(self._L.td_census_fetch(self._h, int(min_count), None, None, 0, C.byref(n)))
+            want = n.value
+        else:
+            want = max(0, int(top))
+        if want == 0:
+            return [], []
+        seqs = C.create_string_buffer(want * L)
+        counts = (C.c_uint64 * want)()
+        B.check(self._L.td_census_fetch(self._h, int(min_count), seqs, counts, want, C.byref(n)))
+        want = min(want, n.value)
+        text = seqs.raw.decode("ascii")
+        return [text[k * L:(k + 1) * L] for k in range(want)], [int(x) for x in counts[:want]]
+
+    def census_end(self):
+        B.check(self._L.td_census_end(self._h))
+        self._census_taglen = 0
 
     # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
     def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):

@@ -11,7 +11,7 @@ kernels; a restatement of the two functions exists only as test infrastructure
 (the CPU checker beside the tests).
 """
 from .engine import (Engine, default_engine, enumerate_cut_sites,  # noqa: F401
-                     combine_barcode_and_cutsite, effective_maxreads)
+                     combine_barcode_and_cutsite, effective_maxreads, census_index)
 
 # restriction enzyme cut sites as they appear after the barcode (reference tagdigger_fun.py:19-20)
 enzymes = {'ApeKI': 'CWGC', 'EcoT22I': 'TGCAT', 'NcoI': 'CATGG',
@@ -89,6 +89,162 @@ def find_tags_fastq_many(files, barcodes, tags, cutsite="TGCAG", maxreads=5e9, t
         if exc is not None:
             raise exc
     return results
+
+
+class CensusResult(list):
+    """What tag_census returns: [seqs, counts] (or [seqs, counts, names]) with the statistics in `.stats`."""
+    stats = None
+
+
+CENSUS_MIN_SLOTS = 1024
+CENSUS_DEFAULT_SLOTS = 1 << 22
+CENSUS_MAX_TABLE_BYTES = 16 << 30
+
+
+def _census_host_index(barcodes, cutsite):
+    """The barcode + cut site index of find_tags_fastq (reference tagdigger_fun.py:209-219) as a dict of the
+    sequences its tree keeps -> barcode row, with the tree's failures (what td_set_index reports)."""
+    barcut, barnum, _ = census_index(barcodes, cutsite)
+    if not barcut:
+        raise IndexError("list index out of range")
+    if barnum == 1 and barcut == [""]:                 # (:109-110: a lone empty sequence matches every base)
+        return {b: 0 for b in "ACGT"}
+    if barcut[0] == "":
+        raise IndexError("string index out of range")
+    try:
+        kept = _trie_survivors(barcut)
+    except AssertionError as exc:
+        pos = int(str(exc).split(":")[1].split(".")[0])
+        raise AssertionError("Problematic sequence: {}.  Likely due to overlapping tags.".format(pos % barnum)) from None
+    return {seq: pos % barnum for seq, pos in kept}
+
+
+def _census_host(fqfile, barcodes, cutsite, taglen, maxreads):
+    """The census rule read by read over a dict: (window -> count, statistics)."""
+    from ._binding import NonAsciiSequence
+    index = _census_host_index(barcodes, cutsite)
+    lengths = sorted({len(s) for s in index})
+    bound = effective_maxreads(maxreads)
+    census = {}
+    st = dict.fromkeys(("reads", "barcut", "short", "ambiguous"), 0)
+    opener = _gzip.open if fqfile[-2:].lower() == 'gz' else open
+    with opener(fqfile, 'rt', encoding='latin-1') as fh:
+        for k, line in enumerate(fh):
+            if k % 4 != 1:
+                continue
+            st["reads"] += 1
+            if any(ch >= '\x80' for ch in line):
+                raise NonAsciiSequence("non-ASCII byte in a sequence line")
+            line1 = line.strip().upper()
+            b = -1
+            for n in lengths:
+                if line1[:n] in index and len(line1) >= n:
+                    b = index[line1[:n]]
+                    break
+            if b != -1:
+                st["barcut"] += 1
+                w = line1[len(barcodes[b]):len(barcodes[b]) + taglen]
+                if len(w) < taglen:
+                    st["short"] += 1
+                elif not set(w) <= _ACGT:
+                    st["ambiguous"] += 1
+                else:
+                    census[w] = census.get(w, 0) + 1
+            if st["reads"] >= bound:
+                break
+    st["counted"] = st["barcut"] - st["short"] - st["ambiguous"]
+    st["distinct"] = len(census)
+    return census, st
+
+
+def _census_known_names(seqs, known, cutsite):
+    """Names of the known tags each window belongs to, joined by ';' ('' when unknown).  The strip decision is
+    find_tags_fastq's (reference :222-231): tags that all begin with a cut-site variant are compared with the window,
+    others with the window behind the cut site; a tag matches when it is a prefix of that string or that string a
+    prefix of it.  On the host over the fetched entries: a bisect for the tags a window begins, one dict lookup per
+    distinct tag length for the tags that begin a window."""
+    names, tags = known[0], [t.upper() for t in known[1]]
+    cutsite = cutsite.upper()
+    cutlen = len(cutsite)
+    skip = 0 if set(t[:cutlen] for t in tags).issubset(set(enumerate_cut_sites(cutsite))) else cutlen
+    order = sorted(range(len(tags)), key=lambda i: tags[i])
+    sorted_tags = [tags[i] for i in order]
+    by_seq = {}
+    for i, t in enumerate(tags):
+        by_seq.setdefault(t, []).append(i)
+    lengths = sorted({len(t) for t in tags})
+    out = []
+    for w in seqs:
+        s = w[skip:]
+        lo = _bisect.bisect_left(sorted_tags, s)
+        hi = _bisect.bisect_left(sorted_tags, s + '\x7f')
+        hits = [order[k] for k in range(lo, hi)]                   # tags that begin with s (s itself among them)
+        for n in lengths:
+            if n >= len(s):
+                break
+            hits.extend(by_seq.get(s[:n], ()))                     # tags that s begins with
+        out.append(";".join(names[i] for i in sorted(hits)))
+    return out
+
+
+def tag_census(fqfile, barcodes, cutsite="TGCAG", taglen=64, maxreads=5e9, min_count=1, top=None, known=None,
+               device=0, backend="gpu", slots=0, max_table_bytes=CENSUS_MAX_TABLE_BYTES):
+    """The distinct sequences that follow the barcodes of one library (plain or .gz by name), and how often each occurs.
+
+    For every read with a barcode + cut site -- find_tags_fastq's rule up to there -- the window of `taglen` bases
+    (1..64) that starts on the cut site's first base is counted; a read too short for it counts as `short`, a window
+    with anything but ACGT as `ambiguous`.  Returns [seqs, counts] of the windows seen at least `min_count` times,
+    by count descending, then sequence ascending; `top=N` keeps the first N.  With `known=[names, seqs]` (what the
+    readTags_* functions return) a third list holds, per window, the names of the known tags it belongs to joined
+    by ';' ('' for an unknown one).  The statistics (reads, barcut, short, ambiguous, counted, distinct) are the
+    result's `.stats`.
+
+    backend="gpu": the table is filled on the device (csrc/census.hip).  A table that fills up is begun again with
+    four times the slots (from `slots`, default 2^22) and the file recounted, as long as the table stays within
+    `max_table_bytes` (default 16 GiB); beyond that the TD_E_LIMIT is raised.  backend="host": a dict over the same
+    rule.  Not done here: tassel_tagcount weights, per-sample rows, several GPUs, mismatch-tolerant grouping."""
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    taglen = int(taglen)
+    if not 1 <= taglen <= 64:
+        raise ValueError("taglen must be 1..64")
+    min_count = max(1, int(min_count))
+    if backend == "host":
+        census, stats = _census_host(fqfile, barcodes, cutsite, taglen, maxreads)
+        entries = sorted(((s, c) for s, c in census.items() if c >= min_count), key=lambda e: (-e[1], e[0]))
+        if top is not None:
+            entries = entries[:max(0, int(top))]
+        seqs, counts = [e[0] for e in entries], [e[1] for e in entries]
+    else:
+        from ._binding import TagdigError
+        eng = default_engine(device)
+        slots = int(slots) or CENSUS_DEFAULT_SLOTS
+        try:
+            while True:
+                eng.census_begin(barcodes, cutsite, taglen, slots)
+                try:
+                    eng.census_file(fqfile, maxreads)
+                    break
+                except TagdigError as exc:
+                    if exc.code != -7 or not exc.detail.startswith("census table full"):
+                        raise
+                    slots *= 4
+                    if slots * (32 if taglen > 32 else 16) > max_table_bytes:
+                        raise
+            stats = eng.census_stats()
+            seqs, counts = eng.census_fetch(min_count, top)
+        except BaseException:
+            try:
+                eng.census_end()
+            except Exception:      # noqa: BLE001 -- the error that brought us here is the one to report
+                pass
+            raise
+        eng.census_end()
+    out = CensusResult([seqs, counts])
+    if known is not None:
+        out.append(_census_known_names(seqs, known, cutsite))
+    out.stats = {k: stats[k] for k in ("reads", "barcut", "short", "ambiguous", "counted", "distinct")}
+    return out
 
 
 # =============================================================================
