@@ -384,6 +384,53 @@ int td_census_stats(td_handle *h, uint64_t out[8]);
 int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *counts_out, uint64_t capacity, uint64_t *n_out);
 int td_census_end(td_handle *h);
 
+/* ---- tag network (csrc/tagnet.hip; tagdigger_amd/tagdigger_fun.py tag_network and census_markers drive these) --------
+ *
+ * From a census to markers without a reference genome (the UNEAK network filter).  Input: n tags of one
+ * length taglen (1 .. TD_TAGNET_MAX_TAGLEN), upper-case ACGT, pairwise distinct, as n * taglen ASCII bytes in
+ * td_census_fetch's layout, and their counts.  The rule, in integers only:
+ *   edge       an unordered pair i < j whose sequences differ at exactly one position (no indels, no distance 2)
+ *   kept edge  min(c_i, c_j) * 1 000 000 >= ratio_ppm * max(c_i, c_j), exact as a 128-bit product
+ *   degree     kept edges at a tag
+ *   pair       a kept edge whose two ends both have degree 1
+ * Edges and pairs are delivered ascending by (i, j).  A tag has at most 3 * taglen neighbours, so there are at most
+ * 3 * taglen * n / 2 edges; nothing is ever sized by n^2.
+ *
+ * td_tagnet_build: packs, sorts twice, compares inside the runs and selects (the kernels are described in tagnet.hip);
+ *   the result stays in *out until td_tagnet_free.  stats[TD_TAGNET_*] (optional).  `compares` is the number of tag
+ *   comparisons the device makes: the sum of len * (len - 1) / 2 over the runs of both sorted orders, known before any
+ *   comparing.  ms (optional, 6 entries): device time of K1 pack, K2 the two sorts, K3 run boundaries, K4 compare,
+ *   K5 select, and the host's time for copying and ordering the results.  n = 0 and n = 1 give empty results.
+ *   Errors: TD_E_ARG (taglen outside 1..64, ratio_ppm > 1 000 000), TD_E_ALPHABET (a byte outside ACGT;
+ *   td_last_bad_index gives the tag), TD_E_OVERLAP (two equal tags; td_last_bad_index gives the later one),
+ *   TD_E_LIMIT (more than 2^30 tags; or compares above the cap -- the message names both numbers, stats[0] and
+ *   stats[TD_TAGNET_COMPARES] are set, and no comparing kernel has been launched).  The cap is
+ *   TD_TAGNET_DEFAULT_MAX_COMPARES unless the option "tagnet_max_compares" sets another.
+ * td_tagnet_edges / td_tagnet_pairs: ij_out[2 k], ij_out[2 k + 1] = i, j of entry k < capacity; *n_out = how many
+ *   there are, whatever capacity holds.  kept_only != 0 leaves the cut edges out.
+ * td_tagnet_degrees: deg_out[n]. */
+typedef struct td_tagnet td_tagnet;
+enum {
+    TD_TAGNET_TAGS = 0,       /* n                                                                        */
+    TD_TAGNET_EDGES = 1,      /* pairs of tags at distance 1                                              */
+    TD_TAGNET_KEPT = 2,       /* ... that pass the ratio                                                  */
+    TD_TAGNET_DEG0 = 3,       /* tags without a kept edge                                                 */
+    TD_TAGNET_DEG1 = 4,       /* tags with exactly one                                                    */
+    TD_TAGNET_HUBS = 5,       /* tags with two or more                                                    */
+    TD_TAGNET_PAIRS = 6,      /* kept edges between two tags of degree 1                                  */
+    TD_TAGNET_COMPARES = 7,   /* tag comparisons of the device path                                       */
+    TD_TAGNET_MAX_TAGLEN = 64,
+    TD_TAGNET_TILE = 256      /* rows and columns of a compare tile: a run longer than this spans several */
+};
+/* K4 at this many compares runs for about 2 s on an MI355X (NOT YET measured: see DESIGN.md 4.13) */
+#define TD_TAGNET_DEFAULT_MAX_COMPARES 2000000000000ull
+int td_tagnet_build(td_handle *h, const char *seqs, const uint64_t *counts, uint32_t n, uint32_t taglen, uint32_t ratio_ppm,
+                    td_tagnet **out, uint64_t stats[8], double *ms);
+int td_tagnet_edges(td_handle *h, const td_tagnet *net, int kept_only, uint32_t *ij_out, uint64_t capacity, uint64_t *n_out);
+int td_tagnet_pairs(td_handle *h, const td_tagnet *net, uint32_t *ij_out, uint64_t capacity, uint64_t *n_out);
+int td_tagnet_degrees(td_handle *h, const td_tagnet *net, uint32_t *deg_out);
+int td_tagnet_free(td_handle *h, td_tagnet *net);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */
@@ -463,6 +510,7 @@ int64_t td_format_csv_row(const int64_t *vals, uint64_t n, char *out, uint64_t c
  *   "gpu_inflate_crc" 1 (default): every member's CRC-32 is checked on the device
  *   "zb_members"     BGZF members per GPU batch (tests; the built-in 49 152 is also the maximum)
  *   "md5_piece"      td_md5_files: bytes a file contributes per round (tests; a multiple of 64, 0 = the built-in size)
+ *   "tagnet_max_compares"  td_tagnet_build: the compare cap (tests; 0 = TD_TAGNET_DEFAULT_MAX_COMPARES)
  *   "debug_ablate"   timing-only ablation bits -- the counts are WRONG when non-zero
  * Returns TD_E_ARG for unknown names. */
 int td_set_option(td_handle *h, const char *name, int64_t value);

@@ -236,6 +236,7 @@ struct td_handle {
     int gpu_huffman = 1;                      // ordinary gzip: Huffman decoding on the GPU too (0: host threads decode, the GPU resolves)
     uint64_t gz_gpu_min = (uint64_t)8 << 20;  // ... for files of this many compressed bytes and more
     uint64_t md5_piece = 0;                   // (tests) td_md5_files: bytes a file contributes per round; 0 = the built-in 1 MiB
+    uint64_t tagnet_max_compares = 0;         // (tests) td_tagnet_build: the compare cap; 0 = TD_TAGNET_DEFAULT_MAX_COMPARES
     uint32_t gz_gpu_terr_kb = 128;            // ... one chunk per this much compressed data
     int gz_gpu_verify = 0;                    // ... the block search decodes a block before it believes its header
     uint32_t gz_gpu_seg_kb = 1u << 20, gz_gpu_margin_kb = 16384;      // ... a segment of compressed data (1 GiB), and how far its last chunk may run past it
@@ -692,6 +693,9 @@ namespace { inline int stage_threads(); }
 // for csrc/md5.hip (hidden): the "md5_piece" option and the number of staging threads
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h) { return h->md5_piece; }
 extern "C" __attribute__((visibility("hidden"))) int td_stage_thread_count(void) { return stage_threads(); }
+// for csrc/tagnet.hip (hidden): the "tagnet_max_compares" option, and the index td_last_bad_index reports
+extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_compares(const td_handle *h) { return h->tagnet_max_compares; }
+extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx) { g_bad = idx; }
 // for csrc/census.hip (hidden): its state's place on the handle, the work stream, the CU count; the barcode + cut-site
 // index by td_set_index's rules; the handle's line counting and tile scan
 extern "C" __attribute__((visibility("hidden"))) void **td_handle_census(td_handle *h) { return &h->census; }
@@ -2699,6 +2703,7 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
     else if (n == "gpu_huffman") h->gpu_huffman = value ? 1 : 0;
     else if (n == "gz_gpu_min") h->gz_gpu_min = (uint64_t)std::max<long long>(0, value);
     else if (n == "md5_piece") { if (value < 0 || value % 64) return fail(TD_E_ARG, "md5_piece: a multiple of 64, or 0"); h->md5_piece = (uint64_t)value; }
+    else if (n == "tagnet_max_compares") { if (value < 0) return fail(TD_E_ARG, "tagnet_max_compares: 0 or more"); h->tagnet_max_compares = (uint64_t)value; }
     else if (n == "gz_gpu_terr_kb") { if (value < 16 || value > 4096) return fail(TD_E_ARG, "gz_gpu_terr_kb: 16..4096"); h->gz_gpu_terr_kb = (uint32_t)value; }
     else if (n == "gz_gpu_release") { h->gzgpu.release(); }
     else if (n == "gz_gpu_verify") h->gz_gpu_verify = value ? 1 : 0;

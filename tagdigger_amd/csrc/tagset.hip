@@ -4,12 +4,9 @@
 //    (A 0, C 1, G 2, T 3), first base in the top bits, padded with A; plus the length.  With the length as a tie-break
 //    the order of (words, length) is Python's str order on ACGT strings ("AC" < "ACA" < "ACAA").  A byte outside ACGT
 //    is flagged, not packed.  Keys are word-major (key[w * n + i]) so a lane's reads of one word coalesce.
-// K2 the stable LSD radix sort of the tag permutation by (words, length), 8 bits per pass.  The permutation starts in
-//    the names' code-point order (the host ranks the names), so stability gives sorted(zip(seqs, names)).  One pass:
-//    k_rs_hist (per-tile histograms, digit-major), k_rs_scan (one workgroup, exclusive scan), k_rs_scatter (per tile:
-//    a wave ranks its 64 elements by digit with eight ballots, waves and iterations in index order keep it stable).
-//    k_rs_same first marks the digit positions where some key differs from key 0; the others are skipped.
-//    k_rs_gather then lays the keys out in sorted order for K3.
+// K2 the stable LSD radix sort of the tag permutation by (words, length), 8 bits per pass (radix_sort.hpp, shared with
+//    tagnet.hip).  The permutation starts in the names' code-point order (the host ranks the names), so stability gives
+//    sorted(zip(seqs, names)).  k_rs_gather then lays the keys out in sorted order for K3.
 // K3 k_tag_lookup: one thread per query, the reference's lookupMarkerByTag walk (tagdigger_fun.py:1674-1706) as four
 //    indices f, a, b, c (see the header).  Every block the walk crosses is contiguous in the sorted set (a run of
 //    duplicates, the strings that start with q, each run of prefixes of q), so each is one binary search: at most
@@ -24,6 +21,7 @@
 #include <vector>
 
 #include "../../include/tagdig.h"
+#include "radix_sort.hpp"
 
 // tagdig.hip (not exported): the library's error slot and the handle's device
 extern "C" {
@@ -48,10 +46,6 @@ namespace {
     } while (0)
 
 constexpr int TS_MAXW = TD_TAGSET_MAX_LEN / 32;   // 8 words
-constexpr int RS_THREADS = 256;
-constexpr int RS_ITEMS = 16;
-constexpr int RS_TILE = RS_THREADS * RS_ITEMS;     // 4 096 elements per workgroup
-constexpr int RS_SCAN_THREADS = 1024;
 
 template <typename T> struct TsBuf {
     T *p = nullptr;
@@ -92,122 +86,7 @@ __global__ __launch_bounds__(256) void k_tag_pack(const uint8_t *seqs, const uin
     if (bad) atomicMin(bad_first, i);
 }
 
-// ------------------------------------------------------------------ K2
-// digit position p: 0, 1 the length's bytes; 2 + 8 r + k byte k of word W - 1 - r (least significant first)
-__device__ __forceinline__ uint32_t rs_digit(const uint64_t *key, const uint16_t *len, uint32_t n, uint32_t W, uint32_t idx,
-                                             uint32_t p) {
-    if (p < 2) return (len[idx] >> (8 * p)) & 255u;
-    const uint32_t r = (p - 2) >> 3, k = (p - 2) & 7;
-    return (uint32_t)(key[(uint64_t)(W - 1 - r) * n + idx] >> (8 * k)) & 255u;
-}
-
-__global__ __launch_bounds__(256) void k_rs_same(const uint64_t *key, const uint16_t *len, uint32_t n, uint32_t W,
-                                                 uint32_t *differ) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t npos = 2 + 8 * W;
-    uint32_t m[3] = {0, 0, 0};
-    if (i < n) {
-        if (len[i] != len[0]) m[0] |= ((len[i] ^ len[0]) & 255u ? 1u : 0u) | ((len[i] ^ len[0]) >> 8 ? 2u : 0u);
-        for (uint32_t w = 0; w < W; ++w) {
-            const uint64_t x = key[(uint64_t)w * n + i] ^ key[(uint64_t)w * n];
-            if (!x) continue;
-            const uint32_t r = W - 1 - w;
-            for (uint32_t k = 0; k < 8; ++k)
-                if ((x >> (8 * k)) & 255u) {
-                    const uint32_t p = 2 + 8 * r + k;
-                    if (p < npos) m[p >> 5] |= 1u << (p & 31);
-                }
-        }
-    }
-    for (int q = 0; q < 3; ++q) {
-        uint32_t v = m[q];
-        for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicOr(&differ[q], v);
-    }
-}
-
-__global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const uint64_t *key, const uint16_t *len, const uint32_t *perm,
-                                                        uint32_t n, uint32_t W, uint32_t p, uint32_t nblocks, uint32_t *hist) {
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t base = (uint64_t)blockIdx.x * RS_TILE;
-    for (int it = 0; it < RS_ITEMS; ++it) {
-        const uint64_t j = base + (uint64_t)it * RS_THREADS + threadIdx.x;
-        if (j < n) atomicAdd(&h[rs_digit(key, len, n, W, perm[j], p)], 1u);
-    }
-    __syncthreads();
-    hist[(uint64_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
-}
-
-// exclusive scan of m entries in place, one workgroup
-__global__ __launch_bounds__(RS_SCAN_THREADS) void k_rs_scan(uint32_t *a, uint64_t m) {
-    __shared__ uint32_t part[RS_SCAN_THREADS];
-    const uint64_t chunk = (m + RS_SCAN_THREADS - 1) / RS_SCAN_THREADS;
-    const uint64_t lo0 = (uint64_t)threadIdx.x * chunk, lo = lo0 < m ? lo0 : m, hi = lo + chunk < m ? lo + chunk : m;
-    uint32_t s = 0;
-    for (uint64_t i = lo; i < hi; ++i) s += a[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int d = 1; d < RS_SCAN_THREADS; d <<= 1) {
-        const uint32_t v = threadIdx.x >= (uint32_t)d ? part[threadIdx.x - d] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - s;
-    for (uint64_t i = lo; i < hi; ++i) {
-        const uint32_t v = a[i];
-        a[i] = run;
-        run += v;
-    }
-}
-
-__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const uint64_t *key, const uint16_t *len, const uint32_t *perm_in,
-                                                           uint32_t *perm_out, uint32_t n, uint32_t W, uint32_t p,
-                                                           uint32_t nblocks, const uint32_t *hist) {
-    __shared__ uint32_t boff[256];
-    __shared__ uint32_t wcnt[RS_THREADS / 64][256];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    boff[threadIdx.x] = hist[(uint64_t)threadIdx.x * nblocks + blockIdx.x];
-    for (int w = 0; w < RS_THREADS / 64; ++w) wcnt[w][threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t base = (uint64_t)blockIdx.x * RS_TILE;
-    const uint64_t lt = (1ull << lane) - 1ull;
-    for (int it = 0; it < RS_ITEMS; ++it) {
-        const uint64_t j = base + (uint64_t)it * RS_THREADS + threadIdx.x;
-        const bool valid = j < n;
-        uint32_t v = 0, d = 0;
-        if (valid) {
-            v = perm_in[j];
-            d = rs_digit(key, len, n, W, v, p);
-        }
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const uint64_t bb = __ballot(valid && bit);
-            peers &= bit ? bb : ~bb;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & lt);
-        if (valid && (peers >> lane) == 1ull) wcnt[wv][d] = (uint32_t)__popcll(peers);   // the highest peer
-        __syncthreads();
-        if (valid) {
-            uint32_t dst = boff[d] + rank;
-            for (int w = 0; w < wv; ++w) dst += wcnt[w][d];
-            perm_out[dst] = v;
-        }
-        __syncthreads();
-        uint32_t add = 0;
-        for (int w = 0; w < RS_THREADS / 64; ++w) {
-            add += wcnt[w][threadIdx.x];
-            wcnt[w][threadIdx.x] = 0;
-        }
-        boff[threadIdx.x] += add;
-        __syncthreads();
-    }
-}
-
+// ------------------------------------------------------------------ K2 (the sort itself: radix_sort.hpp)
 __global__ __launch_bounds__(256) void k_rs_gather(const uint64_t *key, const uint16_t *len, const uint32_t *perm, uint32_t n,
                                                    uint32_t W, uint64_t *skey, uint16_t *slen) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -474,24 +353,10 @@ extern "C" int td_tagset_load(td_handle *h, const char *seqs, const uint64_t *of
     if (n) TSCHK(hipMemcpy(perm0.p, init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     TSCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
     TSCHK(hipEventRecord(ev.e[2], 0));
-    const uint32_t nblocks = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
     uint32_t npass = 0;
     if (n > 1) {
-        hipLaunchKernelGGL(k_rs_same, dim3((n + 255) / 256), dim3(256), 0, 0, key.p, len.p, n, W, differ.p);
-        TSCHK(hipGetLastError());
-        uint32_t dif[3];
-        TSCHK(hipMemcpy(dif, differ.p, sizeof dif, hipMemcpyDeviceToHost));
-        TSCHK(hist.alloc(256ull * nblocks));
-        for (uint32_t p = 0; p < 2 + 8 * W; ++p) {
-            if (!((dif[p >> 5] >> (p & 31)) & 1u)) continue;
-            hipLaunchKernelGGL(k_rs_hist, dim3(nblocks), dim3(RS_THREADS), 0, 0, key.p, len.p, perm0.p, n, W, p, nblocks, hist.p);
-            hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(RS_SCAN_THREADS), 0, 0, hist.p, 256ull * nblocks);
-            hipLaunchKernelGGL(k_rs_scatter, dim3(nblocks), dim3(RS_THREADS), 0, 0, key.p, len.p, perm0.p, perm1.p, n, W, p,
-                               nblocks, hist.p);
-            TSCHK(hipGetLastError());
-            std::swap(perm0.p, perm1.p);
-            ++npass;
-        }
+        TSCHK(hist.alloc(256ull * tdrs::rs_blocks(n)));
+        TSCHK(tdrs::rs_sort(key.p, len.p, n, W, &perm0.p, &perm1.p, differ.p, hist.p, &npass));
     }
     td_tagset *s = new td_tagset{td_handle_device(h), n, W, nullptr, nullptr};
     hipError_t e1 = hipMalloc(&s->key, std::max<size_t>(1, (size_t)W * n) * sizeof(uint64_t));

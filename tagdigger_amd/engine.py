@@ -94,6 +94,29 @@ class TagSet:
             pass
 
 
+class TagNet:
+    """A tag network built on the device (td_tagnet_build); freed by close() or when collected."""
+
+    def __init__(self, eng, ptr, n, stats, ms):
+        self._eng, self.ptr, self.n, self.stats, self.ms = eng, ptr, n, stats, ms
+
+    def close(self):
+        if self.ptr and self.ptr.value and getattr(self._eng, "_h", None):
+            self._eng._L.td_tagnet_free(self._eng._h, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+TAGNET_STATS = ("tags", "edges", "kept", "deg0", "deg1", "hubs", "pairs", "compares")
+TAGNET_MS = ("pack", "sort", "runs", "compare", "select", "host_order")
+TAGNET_TILE = 256           # TD_TAGNET_TILE: rows and columns of a compare tile of csrc/tagnet.hip
+
+
 class Engine:
     """Owns a td_handle on one GPU."""
 
@@ -376,6 +399,58 @@ class Engine:
     def census_end(self):
         B.check(self._L.td_census_end(self._h))
         self._census_taglen = 0
+
+    # ------------------------------------------------------------------ tag network (td_tagnet_*; csrc/tagnet.hip)
+    def tagnet_build(self, seqs, counts, taglen, ratio_ppm):
+        """td_tagnet_build: seqs is the n * taglen ASCII bytes of n distinct ACGT tags, counts their counts.  Returns a
+        TagNet (`.stats`: tags, edges, kept, deg0, deg1, hubs, pairs, compares; `.ms`: device time per kernel).  A
+        failure raises TagdigError; `.bad_index` holds the tag for TD_E_ALPHABET and TD_E_OVERLAP, `.stats` what is
+        known at a TD_E_LIMIT."""
+        import numpy as np
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        n = len(counts)
+        if len(seqs) != n * int(taglen) and 1 <= int(taglen) <= 64:
+            raise ValueError("seqs must hold n * taglen bytes")
+        buf = np.frombuffer(bytes(seqs), dtype=np.uint8) if len(seqs) else np.zeros(1, dtype=np.uint8)
+        cnt = counts if n else np.zeros(1, dtype=np.uint64)
+        out, st, ms = C.c_void_p(), (C.c_uint64 * 8)(), (C.c_double * 6)()
+        rc = self._L.td_tagnet_build(self._h, buf.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), n, int(taglen),
+                                     int(ratio_ppm), C.byref(out), st, ms)
+        if rc:
+            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err.bad_index = self._L.td_last_bad_index() if rc in (-3, -6) else None
+            err.stats = dict(zip(TAGNET_STATS, (int(x) for x in st)))
+            raise err
+        return TagNet(self, out, n, dict(zip(TAGNET_STATS, (int(x) for x in st))), dict(zip(TAGNET_MS, ms)))
+
+    def _tagnet_fetch(self, call, capacity):
+        import numpy as np
+        n = C.c_uint64(0)
+        if capacity is None:
+            B.check(call(None, 0, C.byref(n)))
+            capacity = n.value
+        out = np.zeros((max(1, int(capacity)), 2), dtype=np.uint32)
+        B.check(call(out.ctypes.data_as(C.c_void_p), int(capacity), C.byref(n)))
+        return out[:min(int(capacity), n.value)], n.value
+
+    def tagnet_edges(self, net, kept_only=True, capacity=None):
+        """td_tagnet_edges: (uint32 [k, 2] edges i < j ascending, how many there are); capacity None: all of them."""
+        return self._tagnet_fetch(lambda p, c, n: self._L.td_tagnet_edges(self._h, net.ptr, 1 if kept_only else 0, p, c, n),
+                                  capacity)
+
+    def tagnet_pairs(self, net, capacity=None):
+        """td_tagnet_pairs: (uint32 [k, 2] pairs i < j ascending, how many there are)."""
+        return self._tagnet_fetch(lambda p, c, n: self._L.td_tagnet_pairs(self._h, net.ptr, p, c, n), capacity)
+
+    def tagnet_degrees(self, net):
+        """td_tagnet_degrees: uint32 [n], kept edges at every tag."""
+        import numpy as np
+        deg = np.zeros(max(1, net.n), dtype=np.uint32)
+        B.check(self._L.td_tagnet_degrees(self._h, net.ptr, deg.ctypes.data_as(C.c_void_p)))
+        return deg[:net.n]
+
+    def tagnet_free(self, net):
+        net.close()
 
     # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
     def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):

@@ -202,7 +202,8 @@ def tag_census(fqfile, barcodes, cutsite="TGCAG", taglen=64, maxreads=5e9, min_c
     backend="gpu": the table is filled on the device (csrc/census.hip).  A table that fills up is begun again with
     four times the slots (from `slots`, default 2^22) and the file recounted, as long as the table stays within
     `max_table_bytes` (default 16 GiB); beyond that the TD_E_LIMIT is raised.  backend="host": a dict over the same
-    rule.  Not done here: tassel_tagcount weights, per-sample rows, several GPUs, mismatch-tolerant grouping."""
+    rule.  Not done here: tassel_tagcount weights, per-sample rows, several GPUs.  Grouping the tags into
+    markers: tag_network and census_markers."""
     if backend not in ("gpu", "host"):
         raise ValueError("backend must be 'gpu' or 'host'")
     taglen = int(taglen)
@@ -244,6 +245,129 @@ def tag_census(fqfile, barcodes, cutsite="TGCAG", taglen=64, maxreads=5e9, min_c
     if known is not None:
         out.append(_census_known_names(seqs, known, cutsite))
     out.stats = {k: stats[k] for k in ("reads", "barcut", "short", "ambiguous", "counted", "distinct")}
+    return out
+
+
+class NetworkResult:
+    """What tag_network returns: `.pairs` and `.edges` (the kept edges) as lists of (i, j), i < j, ascending; `.degree`,
+    the kept edges at every tag; `.stats`: tags, edges, kept, deg0, deg1, hubs, pairs, compares, backend."""
+
+    def __init__(self, pairs, edges, degree, stats):
+        self.pairs, self.edges, self.degree, self.stats = pairs, edges, degree, stats
+
+
+def _ratio_ppm(min_ratio):
+    if not 0 <= min_ratio <= 1:
+        raise ValueError("min_ratio must lie in [0, 1]")
+    return int(round(min_ratio * 1e6))
+
+
+def _network_input(seqs, counts):
+    """The tags upper-cased and checked against the rule's input: one length (1..64), ACGT, pairwise distinct."""
+    seqs = [s.upper() for s in seqs]
+    counts = [int(c) for c in counts]
+    if len(seqs) != len(counts):
+        raise ValueError("seqs and counts differ in length")
+    L = len(seqs[0]) if seqs else 0
+    if any(len(s) != L for s in seqs):
+        raise ValueError("tags of unequal length")
+    if seqs and not 1 <= L <= 64:
+        raise ValueError("tags must have 1..64 bases")
+    if not set("".join(seqs)) <= _ACGT:
+        raise ValueError("non-ACGT character in tag {}".format(next(i for i, s in enumerate(seqs) if not set(s) <= _ACGT)))
+    seen = {}
+    for i, s in enumerate(seqs):
+        if seen.setdefault(s, i) != i:
+            raise ValueError("tag {} equals tag {}".format(i, seen[s]))
+    return seqs, counts, L
+
+
+def _network_host(seqs, counts, L, ppm):
+    """The rule of DESIGN 4.13 over a dict: for every tag, every position and each of the three other bases, one
+    lookup -- 3 L n of them, no comparing of tag with tag."""
+    where = {s: i for i, s in enumerate(seqs)}
+    edges, kept = 0, []
+    others = {b: "ACGT".replace(b, "") for b in "ACGT"}
+    for i, s in enumerate(seqs):
+        for k in range(L):
+            head, tail = s[:k], s[k + 1:]
+            for base in others[s[k]]:
+                j = where.get(head + base + tail)
+                if j is None or j < i:
+                    continue
+                edges += 1
+                minor, major = min(counts[i], counts[j]), max(counts[i], counts[j])
+                if minor * 1000000 >= ppm * major:
+                    kept.append((i, j))
+    kept.sort()
+    degree = [0] * len(seqs)
+    for i, j in kept:
+        degree[i] += 1
+        degree[j] += 1
+    pairs = [(i, j) for i, j in kept if degree[i] == 1 and degree[j] == 1]
+    stats = dict(tags=len(seqs), edges=edges, kept=len(kept), deg0=degree.count(0), deg1=degree.count(1),
+                 hubs=sum(1 for d in degree if d >= 2), pairs=len(pairs), compares=0, backend="host")
+    return NetworkResult(pairs, kept, degree, stats)
+
+
+def tag_network(seqs, counts, min_ratio=0.03, device=0, backend="gpu"):
+    """The one-mismatch network of a census and its reciprocal pairs (the UNEAK network filter).
+
+    seqs: n distinct ACGT tags of one length (1..64; lower case is upper-cased), counts their counts.  An edge joins two
+    tags that differ at exactly one position; it is kept when minor * 1 000 000 >= round(min_ratio * 1e6) * major, in
+    integers (min_ratio in [0, 1]; the default is UNEAK's error tolerance rate); a pair is a kept edge whose two ends
+    have no other kept edge.  Returns a NetworkResult.
+
+    backend="gpu": the self-join runs on the device (csrc/tagnet.hip).  Its comparing is quadratic in the longest run of
+    tags that share a half; an input whose `compares` exceed the device's cap is answered by the host restatement
+    instead, and `.stats["backend"]` says which of the two it was.  backend="host": the dict restatement.
+    ValueError: unequal lengths, a character outside ACGT, a duplicate, min_ratio outside [0, 1].
+    Not done here: indels, distance 2, tags of more than 64 bases, several GPUs, per-sample filters."""
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    ppm = _ratio_ppm(min_ratio)
+    seqs, counts, L = _network_input(seqs, counts)
+    if backend == "host" or not seqs:
+        res = _network_host(seqs, counts, L, ppm)
+        if backend == "gpu":
+            res.stats["backend"] = "gpu"          # (nothing to send to the device)
+        return res
+    from ._binding import TagdigError
+    eng = default_engine(device)
+    try:
+        net = eng.tagnet_build("".join(seqs).encode("ascii"), counts, L, ppm)
+    except TagdigError as exc:
+        if exc.code != -7 or not exc.detail.startswith("tag network: compares"):
+            raise
+        return _network_host(seqs, counts, L, ppm)
+    try:
+        pairs = [(int(i), int(j)) for i, j in eng.tagnet_pairs(net)[0]]
+        edges = [(int(i), int(j)) for i, j in eng.tagnet_edges(net, kept_only=True)[0]]
+        degree = [int(d) for d in eng.tagnet_degrees(net)]
+        stats = dict(net.stats, backend="gpu")
+    finally:
+        net.close()
+    return NetworkResult(pairs, edges, degree, stats)
+
+
+def census_markers(seqs, counts, min_ratio=0.03, prefix="Mrkr", numdig=7, start=1, device=0, backend="gpu"):
+    """[marker names, merged strings, pair counts] of the reciprocal pairs of a census (tag_network's `.pairs`, in
+    their order).  Marker k is named prefix + zero-padded (start + k), as consolidateTagSets names new markers; its
+    merged string is mergeTags([major, minor]) with the major allele the tag of the lower index -- in a census the
+    commoner one, the alphabetically first on a tie -- and paircounts[k] = (count of the major, count of the minor).
+    The first two lists are what mergedTagList returns: they go straight into writeMarkerDatabase and exportFasta2.
+    `.stats` holds tag_network's statistics."""
+    if '_' in prefix:
+        raise ValueError("marker names cannot contain underscores: prefix {!r}".format(prefix))
+    net = tag_network(seqs, counts, min_ratio=min_ratio, device=device, backend=backend)
+    seqs = [s.upper() for s in seqs]
+    names, merged, paircounts = [], [], []
+    for k, (i, j) in enumerate(net.pairs):
+        names.append("{}{:0{width}}".format(prefix, start + k, width=numdig))
+        merged.append(mergeTags([seqs[i], seqs[j]]))
+        paircounts.append((int(counts[i]), int(counts[j])))
+    out = CensusResult([names, merged, paircounts])
+    out.stats = net.stats
     return out
 
 
