@@ -431,6 +431,62 @@ int td_tagnet_pairs(td_handle *h, const td_tagnet *net, uint32_t *ij_out, uint64
 int td_tagnet_degrees(td_handle *h, const td_tagnet *net, uint32_t *deg_out);
 int td_tagnet_free(td_handle *h, td_tagnet *net);
 
+/* ---- genotype calls and marker filters (csrc/genocall.hip; tagdigger_amd/tagdigger_fun.py call_genotypes drives it) --
+ *
+ * From the samples x tags count matrix to genotype calls, without bringing the matrix to the host.
+ * d_counts is S x T uint32, row-major, in DEVICE memory: a handle's bound or internal matrix, the destination of
+ * td_fold_rows, or any td_dev_alloc buffer.  Marker m is the pair of columns (i0[m], i1[m]) -- HOST arrays, both < T and
+ * different; no order or adjacency is assumed.  The rule, in integers only, with a = counts[s][i0[m]],
+ * b = counts[s][i1[m]], n = a + b (64-bit):
+ *   TD_GENO_MISSING (3)  n < min_depth
+ *   TD_GENO_PRESENCE     1 when a > 0 and b > 0, else 0 when a > 0, else 2 (with min_depth 1: writeDiploidGeno's table,
+ *                        tagdigger_fun.py:1144-1180)
+ *   TD_GENO_LIKELIHOOD   n > 127: a' = floor(127 a / n), b' = floor(127 b / n), n' = a' + b'; else the values themselves.
+ *                        1 when min(a', b') >= het_min[n'], else 0 when a' >= b', else 2
+ * The code is the number of allele-1 copies.  het_min[TD_GENO_TABLE] is DATA from the caller: het_min[n] = the smallest
+ * k in 0 .. n / 2 with (1/2)^n > (1 - e)^(n - k) e^k for e = err_ppm / 10^6 as an exact rational, n + 1 when there is
+ * none, het_min[0] = 1 (tagdigger_fun.het_threshold_table); the library evaluates no power and no logarithm, it checks
+ * het_min[n] <= n + 1 only.
+ * Per marker, stats_out[TD_GENO_NSTATS m + TD_GENO_*]: exact integers; depth0 / depth1 sum a and b over EVERY sample,
+ * missing ones included.  Marker m passes (pass_out[m] = 1) when
+ *   called * 10^6 >= min_call_ppm * S,  min(alt, 2 called - alt) * 10^6 >= min_maf_ppm * 2 called,
+ *   n1 * 10^6 <= max_het_ppm * called
+ * -- a marker nobody was called at passes only with min_call_ppm = 0.  *passed_out = the markers that pass.
+ * calls_out (optional, host, S x M bytes, row-major) receives the codes; d_calls_out (optional) receives the DEVICE
+ * buffer the kernel wrote them to, which is then the caller's (td_dev_free): a caller that wants the statistics and
+ * the mask only passes calls_out = NULL.  ms (optional): device time of the two kernels.
+ * Synchronous; waits for the work enqueued through this handle first.  M = 0 is answered without a launch; so is S = 0
+ * (zero statistics, nothing passes).  TD_E_ARG: a parameter outside its range (rule 0 | 1, err_ppm 1 .. 499 999,
+ * min_depth >= 1, min_call_ppm and max_het_ppm 0 .. 10^6, min_maf_ppm 0 .. 500 000), a table entry above n + 1, or a
+ * marker whose columns are not both below T or are equal: td_last_bad_index gives the marker. */
+typedef struct td_geno_params {
+    uint32_t rule;            /* TD_GENO_LIKELIHOOD | TD_GENO_PRESENCE                                    */
+    uint32_t err_ppm;         /* the error rate het_min was built for                                     */
+    uint64_t min_depth;       /* a + b below this: missing                                                */
+    uint32_t min_call_ppm;    /* marker filter: called / S                                                */
+    uint32_t min_maf_ppm;     /* marker filter: minor allele frequency among the called                   */
+    uint32_t max_het_ppm;     /* marker filter: heterozygous calls among the called; 10^6: off            */
+    uint32_t reserved;
+} td_geno_params;
+enum {
+    TD_GENO_LIKELIHOOD = 0,
+    TD_GENO_PRESENCE = 1,
+    TD_GENO_MISSING = 3,      /* the code of a cell below min_depth                                       */
+    TD_GENO_CALLED = 0,       /* stats: n0 + n1 + n2                                                      */
+    TD_GENO_N0 = 1,           /* calls by code                                                            */
+    TD_GENO_N1 = 2,
+    TD_GENO_N2 = 3,
+    TD_GENO_ALT = 4,          /* n1 + 2 n2: copies of allele 1                                            */
+    TD_GENO_DEPTH0 = 5,       /* sum of a                                                                 */
+    TD_GENO_DEPTH1 = 6,       /* sum of b                                                                 */
+    TD_GENO_NSTATS = 7,
+    TD_GENO_TABLE = 128,      /* entries of het_min; deeper cells are scaled to 127                       */
+    TD_GENO_CHUNK = 64        /* sample rows per workgroup of the call kernel (a choice, not yet measured) */
+};
+int td_geno_call(td_handle *h, const void *d_counts, uint32_t S, uint32_t T, uint32_t M, const uint32_t *i0,
+                 const uint32_t *i1, const uint16_t *het_min, const td_geno_params *p, uint8_t *calls_out,
+                 void **d_calls_out, uint64_t *stats_out, uint8_t *pass_out, uint64_t *passed_out, double *ms);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */

@@ -44,6 +44,12 @@ class SynthParams(C.Structure):
                 ("tag_cdf", C.c_void_p), ("bar_cdf", C.c_void_p), ("adapter", C.c_char * 64)]
 
 
+class GenoParams(C.Structure):
+    """td_geno_params of include/tagdig.h"""
+    _fields_ = [("rule", C.c_uint32), ("err_ppm", C.c_uint32), ("min_depth", C.c_uint64), ("min_call_ppm", C.c_uint32),
+                ("min_maf_ppm", C.c_uint32), ("max_het_ppm", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _hip_runtime_candidates():
     env = os.environ.get("TAGDIG_HIP_RUNTIME")
     if env:
@@ -158,6 +164,8 @@ def load():
     sig("td_tagnet_pairs", i32, vp, vp, vp, u64, C.POINTER(u64))
     sig("td_tagnet_degrees", i32, vp, vp, vp)
     sig("td_tagnet_free", i32, vp, vp)
+    sig("td_geno_call", i32, vp, vp, u32, u32, u32, vp, vp, vp, C.POINTER(GenoParams), vp, C.POINTER(vp), vp, vp,
+        C.POINTER(u64), dp)
     _lib = L
     return L
 
@@ -177,6 +185,7 @@ EXPORTS = [
     "td_md5_device", "td_md5_files",
     "td_census_begin", "td_census_device", "td_census_file", "td_census_stats", "td_census_fetch", "td_census_end",
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
+    "td_geno_call",
 ]
 
 

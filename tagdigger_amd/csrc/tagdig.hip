@@ -696,6 +696,13 @@ extern "C" __attribute__((visibility("hidden"))) int td_stage_thread_count(void)
 // for csrc/tagnet.hip (hidden): the "tagnet_max_compares" option, and the index td_last_bad_index reports
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_compares(const td_handle *h) { return h->tagnet_max_compares; }
 extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx) { g_bad = idx; }
+// for csrc/genocall.hip (hidden): every launch enqueued through this handle (they may be on its own streams) has finished
+extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h) {
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->work_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
+    return e == hipSuccess ? TD_OK : fail(TD_E_HIP, std::string("waiting for the handle's streams: ") + hipGetErrorString(e));
+}
 // for csrc/census.hip (hidden): its state's place on the handle, the work stream, the CU count; the barcode + cut-site
 // index by td_set_index's rules; the handle's line counting and tile scan
 extern "C" __attribute__((visibility("hidden"))) void **td_handle_census(td_handle *h) { return &h->census; }

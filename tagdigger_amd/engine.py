@@ -6,6 +6,7 @@ barcode+cutsite list, strip-or-shift decision -- and hands the two string
 lists to libtagdig (td_set_index), which builds the flat device index.  The
 record loop (:239-277) runs on the GPU.
 """
+import collections
 import ctypes as C
 import os
 import math
@@ -115,6 +116,36 @@ class TagNet:
 TAGNET_STATS = ("tags", "edges", "kept", "deg0", "deg1", "hubs", "pairs", "compares")
 TAGNET_MS = ("pack", "sort", "runs", "compare", "select", "host_order")
 TAGNET_TILE = 256           # TD_TAGNET_TILE: rows and columns of a compare tile of csrc/tagnet.hip
+
+
+GENO_STATS = ("called", "n0", "n1", "n2", "alt", "depth0", "depth1")     # TD_GENO_* slots of a marker's statistics row
+GENO_RULES = {"likelihood": 0, "presence": 1}
+GENO_TABLE = 128            # TD_GENO_TABLE: entries of het_min
+GENO_CHUNK = 64             # TD_GENO_CHUNK: sample rows per workgroup of csrc/genocall.hip's call kernel
+
+
+class GenoCalls(collections.namedtuple("GenoCalls", "calls stats mask ms passed d_calls")):
+    """What Engine.geno_call returns: calls (uint8 [S, M]; None when they were not fetched), stats (dict of uint64 [M]
+    arrays by GENO_STATS), mask (bool [M]), ms (device time), passed (how many pass), d_calls (the device buffer of the
+    calls when it was asked for -- the caller's, to be freed with dev_free -- else None)."""
+    __slots__ = ()
+
+
+def counts_as_uint32(counts):
+    """A count matrix as a C-contiguous uint32 array.  uint32 is what the device reads; another integer type is taken
+    when every value fits, and refused otherwise."""
+    import numpy as np
+    a = np.asarray(counts)
+    if a.ndim != 2:
+        raise ValueError("the count matrix must have two dimensions (samples x tags)")
+    if a.dtype != np.uint32:
+        if a.dtype.kind not in "iu":
+            raise TypeError("the count matrix must hold integers (uint32), not {}".format(a.dtype))
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xffffffff):
+            raise OverflowError("the count matrix holds values outside 0 .. 2^32 - 1 (min {}, max {}): genotype calling "
+                                "reads uint32 counts".format(int(a.min()), int(a.max())))
+        a = a.astype(np.uint32)
+    return np.ascontiguousarray(a)
 
 
 class Engine:
@@ -451,6 +482,59 @@ class Engine:
 
     def tagnet_free(self, net):
         net.close()
+
+    # ------------------------------------------------------------------ genotype calls (td_geno_call; csrc/genocall.hip)
+    def geno_call(self, counts, i0, i1, het_min, shape=None, rule=0, err_ppm=10000, min_depth=1, min_call_ppm=0,
+                  min_maf_ppm=0, max_het_ppm=1000000, fetch_calls=True, keep_device=False):
+        """td_geno_call: genotype calls, per-marker statistics and the filter mask of the markers (i0[m], i1[m]) --
+        pairs of columns -- of a samples x tags count matrix.  counts is a numpy matrix (uploaded; see counts_as_uint32)
+        or a device pointer with shape=(S, T): a matrix the counter or fold_rows filled is called where it lies.
+        het_min: the 128 thresholds of tagdigger_fun.het_threshold_table.  fetch_calls=False leaves the calls on the
+        device (statistics and mask only); keep_device=True hands their device buffer out as `.d_calls`.  Returns a
+        GenoCalls.  A failure raises TagdigError; `.bad_index` holds the marker for a bad pair of columns."""
+        import numpy as np
+        i0 = np.ascontiguousarray(i0, dtype=np.uint32)
+        i1 = np.ascontiguousarray(i1, dtype=np.uint32)
+        het = np.ascontiguousarray(het_min, dtype=np.uint16)
+        if i0.ndim != 1 or i0.shape != i1.shape:
+            raise ValueError("i0 and i1 must be two index lists of one length")
+        if het.shape != (GENO_TABLE,):
+            raise ValueError("het_min must have {} entries".format(GENO_TABLE))
+        M = len(i0)
+        uploaded = None
+        if isinstance(counts, int):
+            if shape is None:
+                raise ValueError("a device pointer needs shape=(samples, tags)")
+            S, T = (int(x) for x in shape)
+            d_counts = counts
+        else:
+            host = counts_as_uint32(counts)
+            S, T = host.shape
+            d_counts = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
+            if host.size:
+                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_counts), host.ctypes.data_as(C.c_void_p), host.nbytes))
+        try:
+            par = B.GenoParams(int(rule), int(err_ppm), int(min_depth), int(min_call_ppm), int(min_maf_ppm), int(max_het_ppm), 0)
+            calls = np.zeros((S, M), dtype=np.uint8) if fetch_calls else None
+            stats = np.zeros((max(1, M), len(GENO_STATS)), dtype=np.uint64)
+            mask = np.zeros(max(1, M), dtype=np.uint8)
+            passed, ms, d_calls = C.c_uint64(0), C.c_double(0), C.c_void_p()
+            idx0, idx1 = (a if M else np.zeros(1, dtype=np.uint32) for a in (i0, i1))
+            rc = self._L.td_geno_call(self._h, C.c_void_p(d_counts) if d_counts else None, S, T, M,
+                                      idx0.ctypes.data_as(C.c_void_p), idx1.ctypes.data_as(C.c_void_p),
+                                      het.ctypes.data_as(C.c_void_p), C.byref(par),
+                                      calls.ctypes.data_as(C.c_void_p) if fetch_calls and calls.size else None,
+                                      C.byref(d_calls) if keep_device else None, stats.ctypes.data_as(C.c_void_p),
+                                      mask.ctypes.data_as(C.c_void_p), C.byref(passed), C.byref(ms))
+        finally:
+            if uploaded:
+                self.dev_free(uploaded)
+        if rc:
+            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err.bad_index = self._L.td_last_bad_index() if rc == -2 and err.detail.startswith("marker ") else None
+            raise err
+        return GenoCalls(calls, {k: stats[:M, j].copy() for j, k in enumerate(GENO_STATS)}, mask[:M].astype(bool),
+                         ms.value, passed.value, d_calls.value if keep_device else None)
 
     # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
     def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):

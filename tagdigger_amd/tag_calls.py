@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""Genotype calls from tag counts: the step behind tag_census -> tag_pairs -> counting.  Calls every sample at every
+biallelic marker from the read depths of its two tags, and drops markers by call rate, minor allele frequency and
+heterozygosity.
+
+    python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --stats stats.csv --min-call-rate 0.8 --min-maf 0.05
+    python -m tagdigger_amd.tag_calls -b key.csv --MergedTags markers.csv -e PstI -o calls.csv --hapmap calls.hmp.txt
+
+The input is the counter's CSV (samples in rows, tag names Marker_..._0 / Marker_..._1 in the header), or the
+libraries of a key file, which are counted first: every library's barcode rows are folded into one samples x tags
+matrix on the device, and the calls are made from that matrix where it lies -- it comes to the host only when
+--counts-out asks for the CSV as well.  -o has writeDiploidGeno's layout with the markers that pass.
+"""
+import argparse
+import csv
+import sys
+
+from . import tagdigger_fun as tf
+from .tagdigger_script import FILE_OPTIONS, TAG_FORMATS, checked, cut_site, tag_format
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Genotype calls and marker filters from the tag counts of biallelic markers")
+    ap.add_argument("-i", "--counts", metavar="FILE", help="samples x tags CSV of the counter (instead of -b)")
+    ap.add_argument("-b", "--barcodefile", metavar="FILE", help="key file: FASTQ file, barcode, sample; its libraries are counted")
+    site = ap.add_argument_group("restriction site (with -b, one of the two)")
+    site.add_argument("-e", "--enzyme", choices=sorted(tf.enzymes), help="enzyme whose remnant follows the barcode")
+    site.add_argument("-c", "--cutsite", help="that remnant spelled out (IUPAC codes allowed)")
+    fmt = ap.add_argument_group("tags (with -b, and for --hapmap: exactly one format)")
+    for opt, what in FILE_OPTIONS.items():
+        fmt.add_argument("--" + opt, metavar="FILE", help=what)
+    ap.add_argument("-k", "--tokeep", metavar="FILE", help="marker names to keep, one per line")
+    ap.add_argument("--binaryOnly", choices=["T", "F"], default="T", help="T (default here): drop markers with more than two alleles")
+    ap.add_argument("--TASSELkeyFile", metavar="FILE", help="write the key to the TASSEL marker names here")
+    ap.add_argument("--maxreads", type=float, default=5e9, help="with -b: stop after this many reads of a library")
+    ap.add_argument("-o", "--output", required=True, metavar="FILE", help="genotype CSV to write (markers that pass)")
+    ap.add_argument("--stats", metavar="FILE", help="per-marker statistics CSV to write (every marker)")
+    ap.add_argument("--hapmap", metavar="FILE", help="HapMap table to write (markers that pass; needs the tag file)")
+    ap.add_argument("--counts-out", metavar="FILE", help="with -b: write the samples x tags counts as well")
+    ap.add_argument("--rule", choices=list(tf.GENO_RULES), default="likelihood",
+                    help="likelihood: heterozygous when the rarer allele's reads are too many for errors; presence: when both were seen")
+    ap.add_argument("--err", type=float, default=0.01, help="sequencing error rate of the likelihood rule")
+    ap.add_argument("--min-depth", type=int, default=1, help="fewer reads of both tags together: missing")
+    ap.add_argument("--min-call-rate", type=float, default=0.0, help="drop markers called in a smaller share of the samples")
+    ap.add_argument("--min-maf", type=float, default=0.0, help="drop markers with a smaller minor allele frequency")
+    ap.add_argument("--max-het", type=float, default=1.0, help="drop markers with a larger share of heterozygous calls")
+    ap.add_argument("--td-device", type=int, default=0, help="GPU to run on")
+    ap.add_argument("--td-backend", choices=["gpu", "host"], default="gpu", help="host: numpy on the CPU (with -i)")
+    return ap
+
+
+def read_counts(path):
+    """(sample names, tag names, uint32 matrix) of a CSV written by writeCounts."""
+    import numpy as np
+    from .engine import counts_as_uint32
+    with open(path, newline="") as fh:
+        rows = csv.reader(fh)
+        header = next(rows, None)
+        if header is None or len(header) < 2 or header[0] != "":
+            raise Exception("{}: not a counts file (an empty first header cell, then tag names, expected).".format(path))
+        samples, data = [], []
+        for row in rows:
+            if row:
+                if len(row) != len(header):
+                    raise Exception("{}: sample {} has {} counts, the header names {} tags.".format(
+                        path, row[0], len(row) - 1, len(header) - 1))
+                samples.append(row[0])
+                data.append([int(x) for x in row[1:]])
+    matrix = np.array(data, dtype=np.uint64).reshape(len(samples), len(header) - 1)
+    return samples, header[1:], counts_as_uint32(matrix)
+
+
+def read_tags(args):
+    """[tag names, tag sequences] by the one tag format whose options were given, prefix-free (sanitizeTags)."""
+    keep = checked(tf.readMarkerNames(args.tokeep), "marker names to keep") if args.tokeep is not None else None
+    tags = checked(TAG_FORMATS[tag_format(args)][1](args, keep, args.binaryOnly == "T"), "tags")
+    return tf.sanitizeTags(tags)
+
+
+def count_on_device(eng, keys, sequences, site, maxreads):
+    """Every library of the key file counted and folded into one samples x tags uint32 matrix in device memory
+    (combineReadCounts' sample order).  Returns (sample names, DeviceCounts); the buffer is the caller's."""
+    samples, rows = tf.sample_rows(keys)
+    nbytes = len(samples) * len(sequences) * 4
+    d_total = eng.dev_alloc(nbytes)
+    try:
+        zeros = bytes(min(nbytes, 64 << 20))
+        for off in range(0, nbytes, len(zeros) or 1):
+            eng.h2d(d_total + off, zeros[:nbytes - off])
+        eng.set_option("progress", 0)
+        for f in sorted(keys):
+            eng.set_index(keys[f][0], sequences, site)
+            eng.count_file(f, maxreads)
+            eng.fold_rows(rows[f], d_total, len(samples))
+    except BaseException:
+        eng.dev_free(d_total)
+        raise
+    return samples, tf.DeviceCounts(d_total, (len(samples), len(sequences)))
+
+
+def stats_line(result):
+    missing = int((result.calls == tf.GENO_MISSING).sum())
+    return "Samples: {} Markers: {} Passed: {} Calls: {} Missing: {}".format(
+        len(result.samples), len(result.markers), result.stats["passed"], result.calls.size - missing, missing)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if (args.counts is None) == (args.barcodefile is None):
+        raise Exception("Need either a counts file (-i) or a key file whose libraries are counted (-b, tags and -e or -c).")
+    have_tags = any(getattr(args, o) is not None for o in FILE_OPTIONS)
+    if args.hapmap is not None and not have_tags:
+        raise Exception("--hapmap needs the tag file (e.g. --MergedTags) for the alleles' bases.")
+    params = dict(rule=args.rule, err=args.err, min_depth=args.min_depth, min_call_rate=args.min_call_rate,
+                  min_maf=args.min_maf, max_het=args.max_het, device=args.td_device)
+    eng = d_counts = None
+    if args.counts is not None:
+        if args.counts_out is not None:
+            raise Exception("--counts-out goes with counting (-b); -i is that file already.")
+        samples, names, counts = read_counts(args.counts)
+        sequences = None
+        if have_tags:
+            tagnames, tagseqs = read_tags(args)
+            where = {n: k for k, n in enumerate(tagnames)}
+            missing = [n for n in names if n not in where]
+            if missing:
+                raise Exception("Tag {} of the counts file is not in the tag file.".format(missing[0]))
+            sequences = [tagseqs[where[n]] for n in names]
+        result = tf.call_genotypes(counts, samples, names, backend=args.td_backend, **params)
+    else:
+        if args.td_backend != "gpu":
+            raise Exception("Counting runs on the GPU; --td-backend host goes with a counts file (-i).")
+        site = cut_site(args)
+        names, sequences = read_tags(args)
+        keys = checked(tf.readBarcodeKeyfile(args.barcodefile), "barcode file")
+        unreadable = [f for f in sorted(keys) if not tf.isFastq(f)]
+        if unreadable:
+            print("Cannot read the following as FASTQ files:")
+            print(unreadable)
+            raise Exception("Cannot read all FASTQ files.")
+        tf._geno_markers(names)                          # (the alleles are checked before any file is counted)
+        eng = tf.default_engine(args.td_device)
+        samples, d_counts = count_on_device(eng, keys, sequences, site, args.maxreads)
+    try:
+        if d_counts is not None:
+            result = tf.call_genotypes(d_counts, samples, names, backend="gpu", **params)
+            if args.counts_out is not None:
+                import numpy as np
+                host = np.frombuffer(eng.d2h(d_counts.ptr, d_counts.shape[0] * d_counts.shape[1] * 4), dtype=np.uint32)
+                tf.writeCounts(args.counts_out, host.reshape(d_counts.shape), samples, names)
+    finally:
+        if d_counts is not None:
+            eng.dev_free(d_counts.ptr)
+    tf.writeGenoCalls(args.output, result, passing_only=True)
+    if args.stats is not None:
+        tf.writeMarkerStats(args.stats, result)
+    if args.hapmap is not None:
+        tf.writeHapMap(args.hapmap, result, sequences, passing_only=True)
+    print(stats_line(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

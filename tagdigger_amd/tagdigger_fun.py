@@ -1167,6 +1167,202 @@ def writeDiploidGeno(filename, counts, samnames, tagnames):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Genotype calls and marker filters from the count matrix: the step behind census -> pairs -> counts.
+# The rule is stated in integers; call_genotypes(backend="host") restates it in numpy, csrc/genocall.hip runs it where
+# the matrix lies.  Both read the same threshold table, which only this module builds.
+GENO_STATS = ("called", "n0", "n1", "n2", "alt", "depth0", "depth1")
+GENO_RULES = ("likelihood", "presence")
+GENO_MISSING = 3
+_HET_TABLE = {}
+
+
+def _ppm(value, lo, hi, what):
+    """A rate as parts per million, an integer in lo .. hi."""
+    ppm = int(round(float(value) * 1e6))
+    if not lo <= ppm <= hi:
+        raise ValueError("{} must lie in [{}, {}]".format(what, lo / 1e6, hi / 1e6))
+    return ppm
+
+
+def het_threshold_table(err):
+    """het_min[0 .. 127] for the sequencing error rate e = round(err * 10^6) / 10^6 (1 ppm .. 499 999 ppm), as exact
+    rationals: het_min[n] is the smallest k in 0 .. n // 2 for which a heterozygote explains k reads of the rarer allele
+    among n better than an error does -- (1/2)^n > (1 - e)^(n - k) e^k -- or n + 1 when no k does; het_min[0] = 1.
+    A cell with min(a, b) >= het_min[a + b] is called heterozygous."""
+    from fractions import Fraction
+    ppm = _ppm(err, 1, 499999, "err")
+    if ppm not in _HET_TABLE:
+        e = Fraction(ppm, 1000000)
+        table = [1]
+        for n in range(1, 128):
+            half = Fraction(1, 2) ** n
+            table.append(next((k for k in range(n // 2 + 1) if half > (1 - e) ** (n - k) * e ** k), n + 1))
+        _HET_TABLE[ppm] = tuple(table)
+    return list(_HET_TABLE[ppm])
+
+
+class DeviceCounts:
+    """A samples x tags uint32 count matrix in device memory (what the counter and Engine.fold_rows fill), for
+    call_genotypes(backend="gpu"): `ptr` a device pointer, `shape` = (samples, tags)."""
+
+    def __init__(self, ptr, shape):
+        self.ptr, self.shape = int(ptr), (int(shape[0]), int(shape[1]))
+
+    def __len__(self):
+        return self.shape[0]
+
+
+class GenoResult:
+    """What call_genotypes returns: `.markers` (names in first-seen order), `.samples`, `.calls` (uint8 [samples,
+    markers]: copies of allele 1, 3 = missing), `.stats` (called, n0, n1, n2, alt, depth0, depth1 as arrays over the
+    markers; passed, backend, ms and the parameters), `.mask` (bool per marker: it passes the filters), `.columns`
+    (the count matrix' columns of allele 0 and allele 1 per marker)."""
+
+    def __init__(self, markers, samples, calls, stats, mask, columns):
+        self.markers, self.samples, self.calls, self.stats, self.mask, self.columns = markers, samples, calls, stats, mask, columns
+
+
+def _geno_markers(tagnames):
+    """(marker names, columns of allele '0', columns of allele '1') by extractMarkers."""
+    markers, alleles = extractMarkers(tagnames)
+    if not all(sorted(a[0]) == ['0', '1'] for a in alleles):
+        raise Exception("All allele names must be '0' or '1'.")
+    return markers, [a[1][a[0].index('0')] for a in alleles], [a[1][a[0].index('1')] for a in alleles]
+
+
+def _geno_host(counts, i0, i1, table, rule, min_depth, min_call_ppm, min_maf_ppm, max_het_ppm):
+    """The rule of DESIGN 4.14 in numpy's uint64, which holds every intermediate exactly: n < 2^33, 127 a < 2^39, the
+    filters' products < 2^54."""
+    import numpy as np
+    S, M = counts.shape[0], len(i0)
+    a = counts[:, i0].astype(np.uint64)
+    b = counts[:, i1].astype(np.uint64)
+    n = a + b
+    if rule == "presence":
+        code = np.where((a > 0) & (b > 0), 1, np.where(a > 0, 0, 2))
+    else:
+        deep = n > 127
+        div = np.where(deep, n, 1)
+        x = np.where(deep, 127 * a // div, a)
+        y = np.where(deep, 127 * b // div, b)
+        het = np.minimum(x, y) >= np.asarray(table, dtype=np.uint64)[x + y]
+        code = np.where(het, 1, np.where(x >= y, 0, 2))
+    calls = np.where(n < np.uint64(min_depth), GENO_MISSING, code).astype(np.uint8)
+    n0, n1, n2 = ((calls == c).sum(axis=0, dtype=np.uint64) for c in (0, 1, 2))
+    called, alt = n0 + n1 + n2, n1 + 2 * n2
+    million = np.uint64(1000000)
+    mask = ((called * million >= np.uint64(min_call_ppm * S)) &
+            (np.minimum(alt, 2 * called - alt) * million >= np.uint64(min_maf_ppm) * 2 * called) &
+            (n1 * million <= np.uint64(max_het_ppm) * called))
+    if S == 0:
+        mask[:] = False                               # no sample: no marker passes on no evidence
+    stats = dict(zip(GENO_STATS, (called, n0, n1, n2, alt, a.sum(axis=0, dtype=np.uint64), b.sum(axis=0, dtype=np.uint64))))
+    return calls, stats, mask
+
+
+def call_genotypes(counts, samnames, tagnames, rule="likelihood", err=0.01, min_depth=1, min_call_rate=0.0, min_maf=0.0,
+                   max_het=1.0, device=0, backend="gpu"):
+    """Genotype calls from a samples x tags count matrix, and which markers pass the filters.
+
+    Markers and alleles come from the tag names as extractMarkers reads them; every marker needs exactly one allele
+    '0' and one allele '1'.  For a sample's counts a and b of the two alleles, n = a + b:
+      missing (3)          n < min_depth
+      rule="presence"      1 when both were seen, else 0 or 2 -- writeDiploidGeno's table when min_depth is 1
+      rule="likelihood"    n above 127 is scaled to 127 first (a' = 127 a // n, b' = 127 b // n); heterozygous (1) when
+                           min(a', b') >= het_threshold_table(err)[a' + b'], else 0 when a' >= b', else 2
+    A marker passes when called / samples >= min_call_rate, its minor allele frequency among the called >= min_maf and
+    the share of heterozygous calls <= max_het -- all three compared as integers in parts per million.
+    counts: a numpy matrix or lists (uint32 values), or a DeviceCounts (backend="gpu" only).  backend="gpu" runs
+    csrc/genocall.hip on the matrix where it lies; backend="host" is the numpy restatement.  Returns a GenoResult."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    if rule not in GENO_RULES:
+        raise ValueError("rule must be 'likelihood' or 'presence'")
+    err_ppm = _ppm(err, 1, 499999, "err")
+    if int(min_depth) != min_depth or min_depth < 1:
+        raise ValueError("min_depth must be an integer of at least 1")
+    min_depth = int(min_depth)
+    min_call_ppm = _ppm(min_call_rate, 0, 1000000, "min_call_rate")
+    min_maf_ppm = _ppm(min_maf, 0, 500000, "min_maf")
+    max_het_ppm = _ppm(max_het, 0, 1000000, "max_het")
+    on_device = isinstance(counts, DeviceCounts)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCounts matrix needs backend='gpu'")
+    if not on_device:
+        from .engine import counts_as_uint32
+        counts = counts_as_uint32(counts if len(counts) else np.zeros((0, len(tagnames)), dtype=np.uint32))
+    assert len(samnames) == counts.shape[0], "Length of samnames should be the same as length of counts."
+    assert len(tagnames) == counts.shape[1], "Length of tagnames should be length of second dimension of counts."
+    markers, i0, i1 = _geno_markers(tagnames)
+    table = het_threshold_table(err_ppm / 1e6)
+    if backend == "host":
+        calls, stats, mask = _geno_host(counts, i0, i1, table, rule, min_depth, min_call_ppm, min_maf_ppm, max_het_ppm)
+        ms = 0.0
+    else:
+        res = default_engine(device).geno_call(counts.ptr if on_device else counts, i0, i1, table,
+                                               shape=counts.shape if on_device else None, rule=GENO_RULES.index(rule),
+                                               err_ppm=err_ppm, min_depth=min_depth, min_call_ppm=min_call_ppm,
+                                               min_maf_ppm=min_maf_ppm, max_het_ppm=max_het_ppm)
+        calls, stats, mask, ms = res.calls, res.stats, res.mask, res.ms
+    stats = dict(stats, passed=int(mask.sum()), backend=backend, ms=ms, rule=rule, err_ppm=err_ppm, min_depth=min_depth,
+                 min_call_ppm=min_call_ppm, min_maf_ppm=min_maf_ppm, max_het_ppm=max_het_ppm)
+    return GenoResult(markers, list(samnames), calls, stats, mask, (i0, i1))
+
+
+def _geno_selected(result, passing_only):
+    return [m for m in range(len(result.markers)) if result.mask[m] or not passing_only]
+
+
+def writeGenoCalls(filename, result, passing_only=True):
+    """The calls in writeDiploidGeno's layout (samples in rows, markers in columns, csv.writer's CRLF rows): 0 / 1 / 2,
+    blank for missing.  passing_only: the markers that pass the filters; False: all of them."""
+    import numpy as np
+    keep = _geno_selected(result, passing_only)
+    rows = np.array(['0', '1', '2', ''])[result.calls[:, keep]].tolist()
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow([""] + [result.markers[m] for m in keep])
+        for name, calls in zip(result.samples, rows):
+            out.writerow([name] + calls)
+
+
+def writeMarkerStats(filename, result):
+    """One row per marker: name, called, n0, n1, n2, alt, depth0, depth1, pass (1 / 0); CSV with a header row."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Marker name"] + list(GENO_STATS) + ["pass"])
+        for m, name in enumerate(result.markers):
+            out.writerow([name] + [int(result.stats[k][m]) for k in GENO_STATS] + [1 if result.mask[m] else 0])
+
+
+HAPMAP_HEADER = ("rs#", "alleles", "chrom", "pos", "strand", "assembly#", "center", "protLSID", "assayLSID", "panelLSID",
+                 "QCcode")
+
+
+def writeHapMap(filename, result, tagseqs, passing_only=True):
+    """The calls as a HapMap table (tab-separated, LF): rs# the marker name, alleles X/Y from the one base at which the
+    marker's two tags differ, chrom 0, pos the marker's 1-based ordinal among the result's markers, strand +, the other
+    leading columns NA; then per sample X (code 0), Y (code 2), the IUPAC code of the two (code 1) or N (missing).
+    tagseqs: the tag sequences, one per column of the count matrix.  A marker whose tags differ in length or at another
+    number of bases than one cannot be written this way: an Exception names it."""
+    i0, i1 = result.columns
+    lines = ["\t".join(HAPMAP_HEADER + tuple(result.samples))]
+    for m in _geno_selected(result, passing_only):
+        t0, t1 = tagseqs[i0[m]].upper(), tagseqs[i1[m]].upper()
+        sites = [k for k in range(min(len(t0), len(t1))) if t0[k] != t1[k]]
+        if len(t0) != len(t1) or len(sites) != 1:
+            raise Exception("Marker {}: HapMap output needs two tags of one length that differ at exactly one base."
+                            .format(result.markers[m]))
+        x, y = t0[sites[0]], t1[sites[0]]
+        letters = (x, IUPAC_codes[frozenset(x + y)], y, "N")
+        lines.append("\t".join([result.markers[m], x + "/" + y, "0", str(m + 1), "+"] + ["NA"] * 6 +
+                               [letters[c] for c in result.calls[:, m].tolist()]))
+    with open(filename, mode='w', newline='') as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Tag Manager (reference tagdigger_fun.py:1389-1905 and the prompts of :936-1028, :1182-1200).
 #
 # Every function keeps the reference's signature, return values, printed lines, files and exceptions.  Those with a
