@@ -106,7 +106,13 @@ int td_reset(td_handle *h);
  *   max_reads    reads (sequence lines) with ordinal > max_reads are ignored;
  *                pass max(1, ceil(maxreads)) for the semantics of :272-273
  *   weights      0 for the plain +1 count (:267); 1 for tassel_tagcount
- *                (:251-253,:264-265): header lines carry count=N
+ *                (:251-253,:264-265): header lines carry count=N, read as int() reads it (ASCII: blanks of
+ *                str.strip() around it, a sign, digits with single underscores between them).  A header and
+ *                its sequence line must lie in ONE buffer: a header that is the buffer's last line counts
+ *                nothing (it still raises if malformed), and first_line = 1 (mod 4) -- a buffer that opens
+ *                with a sequence line whose header went before -- is unsupported with weights (the reference
+ *                has no answer either: its weight would be unbound).  td_count_host and td_count_file see
+ *                to that themselves: with weights on, none of their pieces ends behind a header line.
  *   stream       hipStream_t to launch on (NULL = default stream)
  * Asynchronous: returns once the work is enqueued.  ONE stream in flight per handle: the launch's
  * scratch (per-tile words, fix-up queue, tail copy, block sums) belongs to the handle, so work
@@ -565,6 +571,8 @@ int64_t td_format_csv_row(const int64_t *vals, uint64_t n, char *out, uint64_t c
  *   "gpu_inflate"    1 (default): BGZF members are inflated on the GPU; 0: on host threads
  *   "gpu_inflate_crc" 1 (default): every member's CRC-32 is checked on the device
  *   "zb_members"     BGZF members per GPU batch (tests; the built-in 49 152 is also the maximum)
+ *   "stage_kb"       KiB per staged piece of a host buffer, plain file or host-inflated stream (tests; 64 .. 32 768,
+ *                    0 = the built-in 32 MiB)
  *   "md5_piece"      td_md5_files: bytes a file contributes per round (tests; a multiple of 64, 0 = the built-in size)
  *   "tagnet_max_compares"  td_tagnet_build: the compare cap (tests; 0 = TD_TAGNET_DEFAULT_MAX_COMPARES)
  *   "debug_ablate"   timing-only ablation bits -- the counts are WRONG when non-zero

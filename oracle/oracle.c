@@ -180,7 +180,12 @@ int orc_count(const orc_index *ix, const uint8_t *data, uint64_t n, uint64_t fir
             if (p >= q) return ORC_ERR_TASSEL;
             uint64_t v = 0; int neg = 0;
             if (data[p] == '+' || data[p] == '-') { neg = data[p] == '-'; p++; if (p >= q) return ORC_ERR_TASSEL; }
-            for (; p < q; p++) { if (data[p] < '0' || data[p] > '9') return ORC_ERR_TASSEL; v = v * 10 + (data[p] - '0'); }
+            int digit = 0;                        /* int(): single underscores between digits */
+            for (; p < q; p++) {
+                if (data[p] >= '0' && data[p] <= '9') { v = v * 10 + (data[p] - '0'); digit = 1; }
+                else if (data[p] == '_' && digit && p + 1 < q && data[p + 1] >= '0' && data[p + 1] <= '9') digit = 0;
+                else return ORC_ERR_TASSEL;
+            }
             weight = neg ? (uint64_t)(-(int64_t)v) : v;
         }
         if (ph == 1) {                            /* :254 */

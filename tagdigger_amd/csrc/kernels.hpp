@@ -669,9 +669,12 @@ __global__ __launch_bounds__(BLOCK, TD_WAVES_PER_SIMD) void k_count(const KParam
         bool ok = a0 < a1, neg = false;
         if (ok && (gb(a0) == '+' || gb(a0) == '-')) { neg = gb(a0) == '-'; a0++; ok = a0 < a1; }
         unsigned long long v = 0;
+        bool digit = false;                         // the byte before was a digit
         for (uint64_t q = a0; ok && q < a1; q++) {
             uint32_t b = gb(q);
-            if (b < '0' || b > '9') ok = false; else v = v * 10ull + (b - '0');
+            if (b >= '0' && b <= '9') { v = v * 10ull + (b - '0'); digit = true; }
+            else if (b == '_' && digit && q + 1 < a1 && gb(q + 1) >= '0' && gb(q + 1) <= '9') digit = false;   // int(): single underscores between digits
+            else ok = false;
         }
         if (!ok) { atomicOr(p.stats + ST_ERR, ERR_TASSEL); return ~0ull; }
         weight = neg ? 0ull - v : v;

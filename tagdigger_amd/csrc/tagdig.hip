@@ -188,10 +188,12 @@ struct td_handle {
     std::vector<uint64_t> host_acc;           // flushed counts
     uint64_t bytes_since_flush = 0;
     uint64_t flush_limit = 0xFFFFFFFFull;     // hits a uint32 cell may have taken before the matrix is flushed (tests lower it)
+    uint32_t stage_kb = 0;                    // (tests: size of pump()'s staged pieces; 0 = the built-in 32 MiB)
     // launch state
     DevBuf<uint64_t> d_state, d_tilecounts;
     DevBuf<uint32_t> d_ticket;
     DevBuf<unsigned long long> d_cursor;      // [2] line cursor for streamed pieces
+    DevBuf<unsigned long long> d_seam_lines;  // weighted counting: terminators of a device piece up to its cut (cut_before_header_device)
     DevBuf<uint32_t> d_tileinfo, d_nfix;      // fast path: per-tile count+phase, fix-up queue length
     DevBuf<uint8_t> d_tail;                   // fast path: zero-padded copy of the buffer's last tiles
     // barcode splitter (td_set_splitter / td_split_*)
@@ -781,7 +783,7 @@ void td_destroy(td_handle *h) {
     if (h->pin_cursor) (void)hipHostFree(h->pin_cursor);
     h->d_win.release(); h->d_tilesums.release(); h->d_f4np.release(); h->d_sp_entries16.release(); h->d_sp_e8.release(); h->d_sp_pool2.release();
     h->d_counts64.release(); h->d_stats.release(); h->d_state.release(); h->d_tilecounts.release();
-    h->d_ticket.release(); h->d_cursor.release(); h->d_tileinfo.release(); h->d_nfix.release(); h->d_tail.release(); h->d_fixlist.release(); h->d_rowmap.release();
+    h->d_ticket.release(); h->d_cursor.release(); h->d_seam_lines.release(); h->d_tileinfo.release(); h->d_nfix.release(); h->d_tail.release(); h->d_fixlist.release(); h->d_rowmap.release();
     for (auto &ev : h->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (auto &sl : h->sp_slot) {
         if (sl.pin) (void)hipHostFree(sl.pin);
@@ -1066,6 +1068,51 @@ size_t cut_at_line_end(const uint8_t *p, size_t n) {
     return 0;
 }
 
+// tassel_tagcount: a piece never ends behind a header line.  The kernel reads a header's sequence line from the header's own
+// buffer, and a piece that opens with a sequence line has no header for it: a header that is a piece's last line would lose
+// its read.  p[0..c) ends at the cut cut_at_line_end chose and `line_at_cut` is the index of the line that starts there; when
+// that is a sequence line (phase 1) the cut moves back to the header's first byte and the header goes on with its record.
+// 0: the header starts at p[0] or before it.
+size_t cut_before_header(const uint8_t *p, size_t c, uint64_t line_at_cut) {
+    if ((line_at_cut & 3) != 1 || c == 0) return c;
+    size_t i = c - 1;                                   // the header's terminator: \n, \r\n or a bare \r
+    if (p[i] == '\n' && i > 0 && p[i - 1] == '\r') i--;
+    while (i > 0 && p[i - 1] != '\n' && p[i - 1] != '\r') i--;
+    return i;
+}
+// line terminators of p[0..n) by the kernels' rule (\r\n is one); p[n - 1] is a piece's last byte
+uint64_t count_line_ends(const uint8_t *p, size_t n) {
+    uint64_t k = 0;
+    for (size_t i = 0; i < n; i++) k += p[i] == '\n' || (p[i] == '\r' && !(i + 1 < n && p[i + 1] == '\n'));
+    return k;
+}
+// The same for a piece that lies on the device, d_buf[0..total), whose last `ntail` bytes the host holds in `tail`: *c is the
+// cut inside the tail.  The line phase at the cut comes from the line-count kernels over the piece up to the cut (a pass
+// more, and a wait for it: weighted counting only).  *line_at: index of the line the piece starts with, moved on to the cut.
+int cut_before_header_device(td_handle *h, const uint8_t *d_buf, size_t total, const uint8_t *tail, size_t ntail, hipStream_t st,
+                             uint64_t *line_at, size_t *c) {
+    if (*c == 0) return TD_OK;
+    const uint64_t nbytes = total - ntail + *c, nt = (nbytes + 16383) / 16384;
+    if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
+    int rc = h->d_tilecounts.ensure(nt); if (rc) return rc;
+    rc = h->d_state.ensure(nt); if (rc) return rc;
+    rc = h->d_seam_lines.ensure(1); if (rc) return rc;
+    const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
+    hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, st, d_buf, nbytes, (uint32_t)nt, h->d_tilecounts.p);
+    hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, st, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, h->d_seam_lines.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long lines = 0;
+    HIPCHK(hipMemcpyAsync(&lines, h->d_seam_lines.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t c2 = cut_before_header(tail, *c, *line_at + lines);
+    if (c2 != *c) {
+        if (c2 == 0 && ntail < total) return fail(TD_E_LIMIT, "a header line exceeds the staging buffer");
+        *c = c2; lines--;
+    }
+    *line_at += lines;
+    return TD_OK;
+}
+
 // Staging a piece into pinned memory on several host threads (one memcpy or pread stream does not
 // reach PCIe speed): `part(offset, n)` fills bytes [offset, offset + n) of the piece.
 inline int stage_threads() {
@@ -1099,7 +1146,7 @@ template <typename Reader>
 int pump(td_handle *h, Reader &&reader, uint64_t size_hint, uint64_t first_line, uint64_t max_reads, int weights,
          uint64_t *lines_out) {
     Stager st;
-    size_t cap = (size_t)32 << 20;
+    size_t cap = h->stage_kb ? (size_t)h->stage_kb << 10 : (size_t)32 << 20;
     if (size_hint && size_hint < cap) cap = std::max<size_t>(1 << 16, (size_hint + 4095) / 4096 * 4096);
     int rc = st.init(h, cap, first_line); if (rc) return rc;
     std::vector<uint8_t> carry;
@@ -1107,6 +1154,7 @@ int pump(td_handle *h, Reader &&reader, uint64_t size_hint, uint64_t first_line,
     // (reference :272: the loop ends at maxreads -- here the input stops being read once a drained piece's line
     // index shows that the bound has been passed; the kernels ignore reads past it either way)
     const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
+    uint64_t line_at = first_line;              // weights: index of the line the next piece starts with
     while (!eof) {
         uint8_t *buf; rc = st.acquire(&buf); if (rc) return rc;
         if (first_line + st.lines_seen >= stop_line) break;
@@ -1122,7 +1170,13 @@ int pump(td_handle *h, Reader &&reader, uint64_t size_hint, uint64_t first_line,
         size_t cut = have;
         if (!eof) {
             cut = cut_at_line_end(buf, have);
-            if (cut == 0) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
+            if (weights && cut) {               // (a header stays with its record: cut_before_header)
+                uint64_t lines = count_line_ends(buf, cut);
+                const size_t c2 = cut_before_header(buf, cut, line_at + lines);
+                if (c2 != cut) { cut = c2; lines--; }
+                line_at += lines;
+            }
+            if (cut == 0) return fail(TD_E_LIMIT, weights ? "a header line and its record exceed the staging buffer" : "a single line exceeds the staging buffer");
             carry.assign(buf + cut, buf + have);
         }
         rc = st.submit(cut, max_reads, weights); if (rc) return rc;
@@ -1270,6 +1324,7 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
     const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
     int rc = prepare(0, cur); if (rc) return rc;
     size_t carry = 0;                                       // bytes of an unfinished line at the front of this slot's output
+    uint64_t line_at = 0;                                   // weights: index of the line the next piece starts with
     uint64_t bytes_submitted = 0;
     unsigned pieces = 0;
     for (;;) {
@@ -1292,7 +1347,8 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
             if (z.pin_status[i]) return fail(TD_E_IO, z.pin_status[i] == 100 ? "BGZF member fails its CRC-32" : "inflate error in a BGZF member");
         size_t cut = total;
         if (!cur.last && total) {
-            const size_t c = cut_at_line_end(z.pin_tail, ntail);
+            size_t c = cut_at_line_end(z.pin_tail, ntail);
+            if (weights) { rc = cut_before_header_device(h, z.d_out, total, z.pin_tail, ntail, h->work_stream, &line_at, &c); if (rc) return rc; }
             if (c == 0) {                                       // (no line end in sight: everything waits for the next batch)
                 if (total > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
                 cut = 0;
@@ -1470,6 +1526,7 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
     Batch cur, nxt;
     int slot = 0;
     rc = prepare(0, cur); if (rc) return rc;
+    uint64_t line_at = 0;                                       // weights: index of the line the next piece starts with
     uint64_t bytes_submitted = 0;
     unsigned pieces = 0;
     while (cur.valid) {
@@ -1499,7 +1556,8 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
         if (h->pin_cursor[0] >= stop_line) break;               // (the batches counted so far already hold read number max_reads)
         size_t cut = total;
         if (!cur.last && total) {
-            const size_t c = cut_at_line_end(g.pin_tail, ntail);
+            size_t c = cut_at_line_end(g.pin_tail, ntail);
+            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, g.pin_tail, ntail, h->work_stream, &line_at, &c); if (rc) return rc; }
             if (c == 0) {
                 // no line end in sight -- a member that stops inside a line, followed by an empty one or one of a few bytes
                 // (a batch closes at every member end): everything waits for the next batch
@@ -1936,6 +1994,7 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
     struct Free { uint8_t *&p; ~Free() { if (p) (void)hipHostFree(p); } } free_tail{pin_tail};
     const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
     size_t carry = 0;
+    uint64_t line_at = 0;                                                  // weights: index of the line the next piece starts with
     uint64_t bytes_submitted = 0;
     unsigned pieces = 0;
     const double t0 = tdhost::ParInflate::now();
@@ -1957,7 +2016,8 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
             const size_t ntail = std::min(total, ZB_TAIL);
             HIPCHK(hipMemcpyAsync(pin_tail, g.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            const size_t c = cut_at_line_end(pin_tail, ntail);
+            size_t c = cut_at_line_end(pin_tail, ntail);
+            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, pin_tail, ntail, st, &line_at, &c); if (rc) return rc; }
             if (c == 0) {
                 if (total > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
                 cut = 0;
@@ -2728,6 +2788,8 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
         h->fast_max_matrix = value > 0 ? std::min<uint64_t>((uint64_t)value, 1ull << 32) : 1ull << 32;
     else if (n == "flush_limit")                // (tests: flush the uint32 matrix to the host accumulator early; 0 = the built-in 2^32 - 1)
         h->flush_limit = value > 0 ? std::min<uint64_t>((uint64_t)value, 0xFFFFFFFFull) : 0xFFFFFFFFull;
+    else if (n == "stage_kb")                   // (tests: pieces of a host buffer or plain file small enough for seams inside a small input; 0 = the built-in 32 MiB)
+        h->stage_kb = value > 0 ? (uint32_t)std::max<int64_t>(64, std::min<int64_t>(value, 32768)) : 0;
     else if (n == "debug_ablate") h->debug_ablate = (uint32_t)value;   // timing-only ablations, wrong results
     else return fail(TD_E_ARG, "unknown option " + n);
     return TD_OK;
