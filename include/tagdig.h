@@ -77,11 +77,31 @@ void td_destroy(td_handle *h);
  *   tags[ntags]       upper-case tags after the strip decision of :222-231;
  *                     tag k is count-matrix column k
  * Duplicate / extension shadowing and the overlap assertion of :76-82 are
- * reproduced (TD_E_OVERLAP).  The count matrix becomes barnum x ntags, zeroed. */
+ * reproduced (TD_E_OVERLAP).  The count matrix becomes barnum x ntags, zeroed.
+ * Limits (TD_E_LIMIT): barcode + cut site of at most 32 bases, tagoff at most 63, tags of at most 320 bases -- and
+ * behind a tagoff above 32, as many fewer as the widest kernel stages (15 + tagoff + tag length <= 368). */
 int td_set_index(td_handle *h,
                  const char *const *barcut, uint32_t n_barcut, uint32_t barnum,
                  const uint32_t *tagoff,
                  const char *const *tags, uint32_t ntags);
+
+/* The shape of the tag hash table that the last td_set_index built: out[TD_INDEX_*].  Known on the host from the
+ * insertion itself; nothing runs on the device.  For tests and diagnostics (has an index reached the chains, the ring
+ * wrap, the width it was meant to?) -- no count depends on it.  TD_E_STATE without an index. */
+enum {
+    TD_INDEX_W = 0,           /* 64-bit words per packed tag: 1, 2, 3, 4, 6 or 10                                */
+    TD_INDEX_M_BASES = 1,     /* leading bases that are hashed (at most 32); shorter tags are on the short list  */
+    TD_INDEX_BUCKETS = 2,     /* buckets of the table (a power of two)                                           */
+    TD_INDEX_SPB = 3,         /* slots per bucket                                                                */
+    TD_INDEX_NSHORT = 4,      /* tags on the short list                                                          */
+    TD_INDEX_DISPLACED = 5,   /* tags that found their home bucket full and lie in a later one                   */
+    TD_INDEX_LONGEST = 6,     /* the farthest of them, in buckets from its home bucket                           */
+    TD_INDEX_WRAPPED = 7,     /* 1: an insertion went on from the last bucket to bucket 0                        */
+    TD_INDEX_NCH = 8,         /* 16-byte chunks staged per read by k_count / k_fast                              */
+    TD_INDEX_NCH2 = 9,        /* 16-byte pieces packed per read by k_fast2 / k_fast4 (0: W > 3, they do not run) */
+    TD_INDEX_NINFO = 10
+};
+int td_index_info(td_handle *h, uint64_t out[TD_INDEX_NINFO]);
 
 /* Use caller-provided device memory (barnum*ntags uint32, zeroed by the
  * caller) for the count matrix, e.g. a torch tensor that is later all-reduced

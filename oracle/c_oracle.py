@@ -84,8 +84,11 @@ def _raise(rc, bad):
 class COracle:
     """Index built once, then count_bytes() on as many buffers as wanted."""
 
-    def __init__(self, barcodes, tags, cutsite="TGCAG"):
+    def __init__(self, barcodes, tags, cutsite="TGCAG", extra_off=0):
+        # extra_off: the tag search starts that many bases behind where find_tags_fastq puts it (the C-ABI's tagoff may
+        # lie behind the barcode entry; tests/index_edges_cases.py)
         barcut, barnum, tags2, barcutlen = pyorc.prepare_lists(barcodes, tags, cutsite)
+        barcutlen = [x + extra_off for x in barcutlen]
         self.barnum, self.ntags = barnum, len(tags2)
         self._bl = (C.c_uint32 * max(1, barnum))(*barcutlen)
         L = lib()

@@ -249,6 +249,7 @@ struct td_handle {
     int gpu_inflate = 1;                      // BGZF input: inflate on the GPU (0: member-parallel on the host)
     int gpu_inflate_crc = 1;                  // ... and check every member's CRC-32 there
     uint32_t max_need = 0;                    // bases from a read's start that the matcher may look at
+    uint64_t index_info[TD_INDEX_NINFO] = {}; // td_index_info: the shape of the tag table td_set_index built last
     // options
     int tile_kb = 32, blocks_per_cu = 0, prescan = 0, timing = 0, fastpath = 1, nt_loads = 1;
     int kernel_gen = 4;                       // main pass of the free-running path: 4 = k_fast4 (producer / consumer waves), 2 = k_fast2 (lazy packing), 1 = k_fast
@@ -840,9 +841,13 @@ int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uin
     size_t maxlen = 0;
     std::vector<uint32_t> lens;
     for (auto &t : rt.out) { maxlen = std::max(maxlen, t.first.size()); lens.push_back((uint32_t)t.first.size()); }
+    // the narrowest width that holds the longest tag AND stages it: k_count / k_fast read 2 W + 3 chunks of 16 bytes from
+    // the chunk a read starts in, which must reach the tag's last base behind a read that starts at the chunk's byte 15.
+    // A tag offset of up to 32 bases (barcode + cut site) always fits; one beyond that (the C-ABI takes up to 63) with a
+    // tag that fills its width takes the next width, or its last bases would silently not be compared
     int W = 0;
-    for (int w : W_CHOICES) if ((size_t)w * 32 >= maxlen) { W = w; break; }
-    if (!W) return fail(TD_E_LIMIT, "tag longer than 320 bases");
+    for (int w : W_CHOICES) if ((size_t)w * 32 >= maxlen && (size_t)16 * (2 * w + 3) >= 15 + max_off + maxlen) { W = w; break; }
+    if (!W) return fail(TD_E_LIMIT, maxlen > 320 ? "tag longer than 320 bases" : "tag offset + tag length beyond what the widest kernel stages");
     std::sort(lens.begin(), lens.end());
     uint32_t m = 32;
     if (lens.size() > MAX_SHORT) m = std::min<uint32_t>(32, lens[MAX_SHORT]);
@@ -864,6 +869,8 @@ int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uin
     std::vector<uint32_t> slots(nbuckets * bucket_dw, 0);
     std::vector<uint32_t> shorts;
     std::vector<uint64_t> words(W);
+    uint64_t displaced = 0, longest = 0;      // (td_index_info) keys not in their home bucket; the farthest of them, in buckets
+    bool wrapped = false;                     // ... and whether one went on from the last bucket to bucket 0
     for (auto &t : rt.out) {
         const uint32_t L = (uint32_t)t.first.size();
         pack_bases(t.first, words.data(), W);
@@ -874,7 +881,7 @@ int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uin
         }
         const uint32_t hk = hash_key(words[0] >> (64 - 2 * m));
         size_t b = hk & (nbuckets - 1);
-        for (;;) {
+        for (uint64_t hops = 0;; hops++) {
             uint32_t *bp = &slots[b * bucket_dw];
             int free_slot = -1;
             for (int k = 0; k < spb; k++) if (bp[1 + k * slot_dw + 2 * W] == 0) { free_slot = k; break; }
@@ -882,9 +889,11 @@ int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uin
                 uint32_t *sp = bp + 1 + free_slot * slot_dw;
                 for (int w = 0; w < W; w++) { sp[2 * w] = (uint32_t)words[w]; sp[2 * w + 1] = (uint32_t)(words[w] >> 32); }
                 sp[2 * W] = (t.second << 10) | L;
+                if (hops) { displaced++; longest = std::max(longest, hops); }
                 break;
             }
             bp[0] |= 1u << (hk >> 27);        // full: lookups of keys with this filter bit that miss here must go on
+            if (b == nbuckets - 1) wrapped = true;
             b = (b + 1) & (nbuckets - 1);
         }
     }
@@ -900,6 +909,10 @@ int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uin
     // nch chunks; k_fast2: nch2 pieces from the line's own first byte, and its vote reads 8 bytes)
     h->halo = (std::max(h->nch * 16, h->nch2 * 16 + 16) + 63) / 64 * 64;
     h->barnum = barnum; h->ntags = ntags;
+    h->index_info[TD_INDEX_W] = (uint64_t)W; h->index_info[TD_INDEX_M_BASES] = m; h->index_info[TD_INDEX_BUCKETS] = nbuckets;
+    h->index_info[TD_INDEX_SPB] = (uint64_t)spb; h->index_info[TD_INDEX_NSHORT] = h->nshort; h->index_info[TD_INDEX_DISPLACED] = displaced;
+    h->index_info[TD_INDEX_LONGEST] = longest; h->index_info[TD_INDEX_WRAPPED] = wrapped ? 1 : 0;
+    h->index_info[TD_INDEX_NCH] = h->nch; h->index_info[TD_INDEX_NCH2] = h->nch2;
     if (lds_bytes(h, 16) > LDS_BUDGET) return fail(TD_E_LIMIT, "barcode index does not fit the LDS budget");
     if (lds_bytes(h, h->tile_kb) > LDS_BUDGET) h->tile_kb = 16;
     if (h->tile_kb2 && lds_bytes_fast2(h, h->tile_kb2) > LDS_BUDGET) h->tile_kb2 = 0;     // (back to the automatic choice)
@@ -915,6 +928,13 @@ int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uin
     h->host_acc.assign((size_t)barnum * ntags, 0);
     h->have_index = true;
     return zero_results(h);
+}
+
+int td_index_info(td_handle *h, uint64_t out[TD_INDEX_NINFO]) {
+    if (!h || !out) return fail(TD_E_ARG, "NULL argument");
+    if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
+    for (int i = 0; i < TD_INDEX_NINFO; i++) out[i] = h->index_info[i];
+    return TD_OK;
 }
 
 int td_bind_counts(td_handle *h, void *d_counts) {

@@ -52,6 +52,8 @@ def census_index(barcodes, cutsite):
     return barcut, len(barcodes), [len(x) for x in barcodes]
 
 
+INDEX_INFO = ("W", "m_bases", "buckets", "spb", "nshort", "displaced", "longest", "wrapped", "nch", "nch2")     # TD_INDEX_* slots
+
 CENSUS_STATS = ("reads", "barcut", "short", "ambiguous", "counted", "distinct", "slots", "max_keys")
 
 
@@ -204,11 +206,27 @@ class Engine:
                 tags = [x[cutlen:] for x in tags]          # site already checked with the barcode
             else:
                 barcutlen = [x - cutlen for x in barcutlen]  # tags keep the (variable) site
-        off = (C.c_uint32 * max(1, barnum))(*barcutlen)
+        self._set_index_lists(barcut, barnum, barcutlen, tags)
+        self._index_key = key
+
+    def _set_index_lists(self, barcut, barnum, tagoff, tags):
+        """td_set_index as include/tagdig.h states it: the barcode + cut site strings (entry k belongs to barcode
+        k % barnum), where the tag search starts in a read of each barcode (up to 63 bases in: it may lie behind the
+        barcode entry), and the tags as the table stores them.  set_index derives these from find_tags_fastq's
+        arguments; called directly only by tests that need an offset find_tags_fastq never asks for."""
+        self._index_key = None
+        off = (C.c_uint32 * max(1, barnum))(*tagoff)
         B.check(self._L.td_set_index(self._h, _c_strings(barcut), len(barcut), barnum, off,
                                      _c_strings(tags), len(tags)))
         self.barnum, self.ntags = barnum, len(tags)
-        self._index_key = key
+
+    def index_info(self):
+        """td_index_info: the shape of the tag hash table the last set_index built, by INDEX_INFO's names (W, m_bases,
+        buckets, spb, nshort, displaced, longest, wrapped, nch, nch2).  Host-side bookkeeping of the build: for tests
+        and diagnostics, never part of a count."""
+        out = (C.c_uint64 * len(INDEX_INFO))()
+        B.check(self._L.td_index_info(self._h, out))
+        return dict(zip(INDEX_INFO, (int(x) for x in out)))
 
     # ------------------------------------------------------------------ counting
     def reset(self):
