@@ -513,6 +513,35 @@ int td_geno_call(td_handle *h, const void *d_counts, uint32_t S, uint32_t T, uin
                  const uint32_t *i1, const uint16_t *het_min, const td_geno_params *p, uint8_t *calls_out,
                  void **d_calls_out, uint64_t *stats_out, uint8_t *pass_out, uint64_t *passed_out, double *ms);
 
+/* ---- pairwise sample relations (csrc/relate.hip; tagdigger_amd/tagdigger_fun.py sample_relations drives it) -----------
+ *
+ * From the calls to the check of the samples themselves, without bringing the calls to the host.
+ * d_calls is S x M uint8, row-major, in DEVICE memory: td_geno_call's d_calls_out or any td_dev_alloc buffer.  A
+ * sample's row is M contiguous bytes and rows are exactly M bytes apart, so no alignment of a row is assumed.  Codes as
+ * td_geno_call writes them: 0, 1, 2 copies of allele 1; ANY byte above 2 is missing (TD_GENO_MISSING = 3 included).
+ * use (optional, HOST, M bytes): marker m takes part iff use == NULL or use[m] != 0.  The rule, in integers only:
+ *   joint[i][j][a][b] = the participating markers m with calls[i][m] == a and calls[j][m] == b
+ * for every ordered pair of samples, i == j included, and a, b in 0 .. 2: uint32, S x S x 3 x 3, row-major.  So
+ * joint[j][i][b][a] == joint[i][j][a][b], joint[i][i][a][b] == 0 for a != b, and the trace of joint[i][i] is the calls of
+ * sample i.  Every pairwise statistic in common use (IBS distance, IBS0 / 1 / 2, the KING-robust kinship) is a function of
+ * this table; tagdigger_fun.sample_relations derives them.  The table is the Gram product of the one-hot planes of the
+ * calls and is computed on the matrix cores in int8 with int32 accumulators: exact, and independent of scheduling (the
+ * partial tables of the marker chunks are combined with integer atomics).  No byte beyond calls[S M - 1] is read.
+ * joint_out (optional, HOST, 9 S S uint32) receives the table; d_joint_out (optional) the DEVICE buffer it was computed
+ * in, which is then the caller's (td_dev_free).  ms (optional): device time of the kernel.
+ * Synchronous; waits for the work enqueued through this handle first.  Checked before anything is read, allocated or
+ * launched, whatever the other dimension is: S <= TD_RELATE_MAX_SAMPLES (the table is 9 S^2 4 bytes) and M < 2^31 (no
+ * int32 accumulator or uint32 cell can overflow); a violation is TD_E_ARG, and so is a NULL matrix with S M > 0.  After
+ * that S = 0 or M = 0 gives an all-zero (or empty) table without a launch. */
+enum {
+    TD_RELATE_MAX_SAMPLES = 16384,
+    TD_RELATE_TILE = 64,      /* samples along a workgroup's tile edge                                    */
+    TD_RELATE_KCHUNK = 32768  /* markers per workgroup; the chunks' partial tables are added with atomics */
+};
+int td_relate_joint(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const uint8_t *use /* HOST, M bytes, or NULL */,
+                    uint32_t *joint_out /* HOST, 9*S*S, or NULL */, void **d_joint_out /* or NULL; the caller's, td_dev_free */,
+                    double *ms);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */

@@ -167,6 +167,7 @@ def load():
     sig("td_tagnet_free", i32, vp, vp)
     sig("td_geno_call", i32, vp, vp, u32, u32, u32, vp, vp, vp, C.POINTER(GenoParams), vp, C.POINTER(vp), vp, vp,
         C.POINTER(u64), dp)
+    sig("td_relate_joint", i32, vp, vp, u32, u32, vp, vp, C.POINTER(vp), dp)
     _lib = L
     return L
 
@@ -186,7 +187,7 @@ EXPORTS = [
     "td_md5_device", "td_md5_files",
     "td_census_begin", "td_census_device", "td_census_file", "td_census_stats", "td_census_fetch", "td_census_end",
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
-    "td_geno_call",
+    "td_geno_call", "td_relate_joint",
 ]
 
 

@@ -133,6 +133,18 @@ class GenoCalls(collections.namedtuple("GenoCalls", "calls stats mask ms passed 
     __slots__ = ()
 
 
+RELATE_MAX_SAMPLES = 16384  # TD_RELATE_MAX_SAMPLES: the joint table is 9 S^2 uint32
+RELATE_TILE = 64            # TD_RELATE_TILE: samples along a workgroup's tile edge of csrc/relate.hip
+RELATE_KCHUNK = 32768       # TD_RELATE_KCHUNK: markers per workgroup of csrc/relate.hip
+
+
+class RelateJoint(collections.namedtuple("RelateJoint", "joint ms d_joint")):
+    """What Engine.relate_joint returns: joint (uint32 [S, S, 3, 3]; None when it was not fetched), ms (device time),
+    d_joint (the device buffer of the table when it was asked for -- the caller's, to be freed with dev_free -- else
+    None)."""
+    __slots__ = ()
+
+
 def counts_as_uint32(counts):
     """A count matrix as a C-contiguous uint32 array.  uint32 is what the device reads; another integer type is taken
     when every value fits, and refused otherwise."""
@@ -553,6 +565,49 @@ class Engine:
             raise err
         return GenoCalls(calls, {k: stats[:M, j].copy() for j, k in enumerate(GENO_STATS)}, mask[:M].astype(bool),
                          ms.value, passed.value, d_calls.value if keep_device else None)
+
+    # ------------------------------------------------------------------ sample relations (td_relate_joint; csrc/relate.hip)
+    def relate_joint(self, calls, shape=None, use=None, fetch=True, keep_device=False):
+        """td_relate_joint: joint[i][j][a][b] = the markers at which sample i is called a and sample j is called b
+        (a, b in 0 .. 2; any byte above 2 is missing), for every ordered pair of samples.  calls is a numpy uint8 matrix
+        [S, M] (uploaded) or a device pointer with shape=(S, M): the calls Engine.geno_call(keep_device=True) left on
+        the device are read where they lie.  use: M bytes, a marker takes part iff its byte is not zero (None: all).
+        fetch=False leaves the table on the device; keep_device=True hands its device buffer out as `.d_joint`.
+        Returns a RelateJoint.  A failure raises TagdigError."""
+        import numpy as np
+        uploaded = None
+        if calls is None or isinstance(calls, int):
+            if shape is None:
+                raise ValueError("a device pointer needs shape=(samples, markers)")
+            S, M = (int(x) for x in shape)
+            d_calls = calls or 0
+        else:
+            host = np.ascontiguousarray(calls)
+            if host.ndim != 2 or host.dtype != np.uint8:
+                raise ValueError("the call matrix must be a uint8 matrix (samples x markers)")
+            S, M = host.shape
+            d_calls = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
+            if host.size:
+                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_calls), host.ctypes.data_as(C.c_void_p), host.nbytes))
+        try:
+            if use is not None:
+                use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+                if use.shape != (M,):
+                    raise ValueError("use must have one entry per marker")
+                if not M:
+                    use = None
+            in_range = S <= RELATE_MAX_SAMPLES and M < 1 << 31     # (the library answers TD_E_ARG otherwise)
+            joint = np.zeros((S, S, 3, 3), dtype=np.uint32) if fetch and in_range else None
+            ms, d_joint = C.c_double(0), C.c_void_p()
+            rc = self._L.td_relate_joint(self._h, C.c_void_p(d_calls) if d_calls else None, S, M,
+                                         use.ctypes.data_as(C.c_void_p) if use is not None else None,
+                                         joint.ctypes.data_as(C.c_void_p) if joint is not None and joint.size else None,
+                                         C.byref(d_joint) if keep_device else None, C.byref(ms))
+        finally:
+            if uploaded:
+                self.dev_free(uploaded)
+        B.check(rc)
+        return RelateJoint(joint, ms.value, d_joint.value if keep_device else None)
 
     # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
     def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):

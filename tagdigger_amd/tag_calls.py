@@ -5,11 +5,13 @@ heterozygosity.
 
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --stats stats.csv --min-call-rate 0.8 --min-maf 0.05
     python -m tagdigger_amd.tag_calls -b key.csv --MergedTags markers.csv -e PstI -o calls.csv --hapmap calls.hmp.txt
+    python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --relations pairs.csv --relations-matrix dist.csv
 
 The input is the counter's CSV (samples in rows, tag names Marker_..._0 / Marker_..._1 in the header), or the
 libraries of a key file, which are counted first: every library's barcode rows are folded into one samples x tags
 matrix on the device, and the calls are made from that matrix where it lies -- it comes to the host only when
---counts-out asks for the CSV as well.  -o has writeDiploidGeno's layout with the markers that pass.
+--counts-out asks for the CSV as well.  -o has writeDiploidGeno's layout with the markers that pass.  --relations
+checks the samples themselves over the markers that pass (tag_relate's table; the calls stay on the device for it).
 """
 import argparse
 import csv
@@ -37,6 +39,10 @@ def build_parser():
     ap.add_argument("--stats", metavar="FILE", help="per-marker statistics CSV to write (every marker)")
     ap.add_argument("--hapmap", metavar="FILE", help="HapMap table to write (markers that pass; needs the tag file)")
     ap.add_argument("--counts-out", metavar="FILE", help="with -b: write the samples x tags counts as well")
+    ap.add_argument("--relations", metavar="FILE", help="pairs CSV to write: the samples' relations over the markers that pass (see tag_relate)")
+    ap.add_argument("--relations-matrix", metavar="FILE", help="distance matrix CSV to write (samples x samples)")
+    ap.add_argument("--max-dist", type=float, default=0.02, help="--relations: a pair at most this far apart is a duplicate")
+    ap.add_argument("--min-shared", type=int, default=50, help="--relations: ... when at least this many markers are called in both")
     ap.add_argument("--rule", choices=list(tf.GENO_RULES), default="likelihood",
                     help="likelihood: heterozygous when the rarer allele's reads are too many for errors; presence: when both were seen")
     ap.add_argument("--err", type=float, default=0.01, help="sequencing error rate of the likelihood rule")
@@ -113,7 +119,8 @@ def main(argv=None):
         raise Exception("--hapmap needs the tag file (e.g. --MergedTags) for the alleles' bases.")
     params = dict(rule=args.rule, err=args.err, min_depth=args.min_depth, min_call_rate=args.min_call_rate,
                   min_maf=args.min_maf, max_het=args.max_het, device=args.td_device)
-    eng = d_counts = None
+    relate = args.relations is not None or args.relations_matrix is not None
+    eng = d_counts = d_calls = relations = None
     if args.counts is not None:
         if args.counts_out is not None:
             raise Exception("--counts-out goes with counting (-b); -i is that file already.")
@@ -126,7 +133,7 @@ def main(argv=None):
             if missing:
                 raise Exception("Tag {} of the counts file is not in the tag file.".format(missing[0]))
             sequences = [tagseqs[where[n]] for n in names]
-        result = tf.call_genotypes(counts, samples, names, backend=args.td_backend, **params)
+        backend = args.td_backend
     else:
         if args.td_backend != "gpu":
             raise Exception("Counting runs on the GPU; --td-backend host goes with a counts file (-i).")
@@ -141,21 +148,32 @@ def main(argv=None):
         tf._geno_markers(names)                          # (the alleles are checked before any file is counted)
         eng = tf.default_engine(args.td_device)
         samples, d_counts = count_on_device(eng, keys, sequences, site, args.maxreads)
+        counts, backend = d_counts, "gpu"
     try:
-        if d_counts is not None:
-            result = tf.call_genotypes(d_counts, samples, names, backend="gpu", **params)
-            if args.counts_out is not None:
-                import numpy as np
-                host = np.frombuffer(eng.d2h(d_counts.ptr, d_counts.shape[0] * d_counts.shape[1] * 4), dtype=np.uint32)
-                tf.writeCounts(args.counts_out, host.reshape(d_counts.shape), samples, names)
+        keep = relate and backend == "gpu"               # the relations read the calls where the call kernel wrote them
+        result = tf.call_genotypes(counts, samples, names, backend=backend, keep_device=keep, **params)
+        d_calls = result.d_calls
+        if d_counts is not None and args.counts_out is not None:
+            import numpy as np
+            host = np.frombuffer(eng.d2h(d_counts.ptr, d_counts.shape[0] * d_counts.shape[1] * 4), dtype=np.uint32)
+            tf.writeCounts(args.counts_out, host.reshape(d_counts.shape), samples, names)
+        if relate:
+            relations = tf.sample_relations(d_calls if keep else result.calls, samples, mask=result.mask, max_dist=args.max_dist,
+                                            min_shared=args.min_shared, device=args.td_device, backend=backend)
     finally:
         if d_counts is not None:
             eng.dev_free(d_counts.ptr)
+        if d_calls is not None and d_calls.ptr:
+            tf.default_engine(args.td_device).dev_free(d_calls.ptr)
     tf.writeGenoCalls(args.output, result, passing_only=True)
     if args.stats is not None:
         tf.writeMarkerStats(args.stats, result)
     if args.hapmap is not None:
         tf.writeHapMap(args.hapmap, result, sequences, passing_only=True)
+    if args.relations is not None:
+        tf.writeRelations(args.relations, relations)
+    if args.relations_matrix is not None:
+        tf.writeDistanceMatrix(args.relations_matrix, relations)
     print(stats_line(result))
     return 0
 

@@ -1216,10 +1216,12 @@ class GenoResult:
     """What call_genotypes returns: `.markers` (names in first-seen order), `.samples`, `.calls` (uint8 [samples,
     markers]: copies of allele 1, 3 = missing), `.stats` (called, n0, n1, n2, alt, depth0, depth1 as arrays over the
     markers; passed, backend, ms and the parameters), `.mask` (bool per marker: it passes the filters), `.columns`
-    (the count matrix' columns of allele 0 and allele 1 per marker)."""
+    (the count matrix' columns of allele 0 and allele 1 per marker), `.d_calls` (call_genotypes(keep_device=True) on the
+    gpu backend: a DeviceCalls, the calls where the kernel wrote them, which the caller frees; else None)."""
 
-    def __init__(self, markers, samples, calls, stats, mask, columns):
+    def __init__(self, markers, samples, calls, stats, mask, columns, d_calls=None):
         self.markers, self.samples, self.calls, self.stats, self.mask, self.columns = markers, samples, calls, stats, mask, columns
+        self.d_calls = d_calls
 
 
 def _geno_markers(tagnames):
@@ -1261,7 +1263,7 @@ def _geno_host(counts, i0, i1, table, rule, min_depth, min_call_ppm, min_maf_ppm
 
 
 def call_genotypes(counts, samnames, tagnames, rule="likelihood", err=0.01, min_depth=1, min_call_rate=0.0, min_maf=0.0,
-                   max_het=1.0, device=0, backend="gpu"):
+                   max_het=1.0, device=0, backend="gpu", keep_device=False):
     """Genotype calls from a samples x tags count matrix, and which markers pass the filters.
 
     Markers and alleles come from the tag names as extractMarkers reads them; every marker needs exactly one allele
@@ -1273,7 +1275,9 @@ def call_genotypes(counts, samnames, tagnames, rule="likelihood", err=0.01, min_
     A marker passes when called / samples >= min_call_rate, its minor allele frequency among the called >= min_maf and
     the share of heterozygous calls <= max_het -- all three compared as integers in parts per million.
     counts: a numpy matrix or lists (uint32 values), or a DeviceCounts (backend="gpu" only).  backend="gpu" runs
-    csrc/genocall.hip on the matrix where it lies; backend="host" is the numpy restatement.  Returns a GenoResult."""
+    csrc/genocall.hip on the matrix where it lies; backend="host" is the numpy restatement.  keep_device=True with the
+    gpu backend leaves the calls on the device as well: `.d_calls` is a DeviceCalls for sample_relations, and the
+    caller's to free (default_engine(device).dev_free(result.d_calls.ptr) when ptr is not 0).  Returns a GenoResult."""
     import numpy as np
     if backend not in ("gpu", "host"):
         raise ValueError("backend must be 'gpu' or 'host'")
@@ -1296,6 +1300,7 @@ def call_genotypes(counts, samnames, tagnames, rule="likelihood", err=0.01, min_
     assert len(tagnames) == counts.shape[1], "Length of tagnames should be length of second dimension of counts."
     markers, i0, i1 = _geno_markers(tagnames)
     table = het_threshold_table(err_ppm / 1e6)
+    d_calls = None
     if backend == "host":
         calls, stats, mask = _geno_host(counts, i0, i1, table, rule, min_depth, min_call_ppm, min_maf_ppm, max_het_ppm)
         ms = 0.0
@@ -1303,11 +1308,14 @@ def call_genotypes(counts, samnames, tagnames, rule="likelihood", err=0.01, min_
         res = default_engine(device).geno_call(counts.ptr if on_device else counts, i0, i1, table,
                                                shape=counts.shape if on_device else None, rule=GENO_RULES.index(rule),
                                                err_ppm=err_ppm, min_depth=min_depth, min_call_ppm=min_call_ppm,
-                                               min_maf_ppm=min_maf_ppm, max_het_ppm=max_het_ppm)
+                                               min_maf_ppm=min_maf_ppm, max_het_ppm=max_het_ppm,
+                                               keep_device=bool(keep_device))
         calls, stats, mask, ms = res.calls, res.stats, res.mask, res.ms
+        if keep_device:
+            d_calls = DeviceCalls(res.d_calls or 0, calls.shape)
     stats = dict(stats, passed=int(mask.sum()), backend=backend, ms=ms, rule=rule, err_ppm=err_ppm, min_depth=min_depth,
                  min_call_ppm=min_call_ppm, min_maf_ppm=min_maf_ppm, max_het_ppm=max_het_ppm)
-    return GenoResult(markers, list(samnames), calls, stats, mask, (i0, i1))
+    return GenoResult(markers, list(samnames), calls, stats, mask, (i0, i1), d_calls)
 
 
 def _geno_selected(result, passing_only):
@@ -1360,6 +1368,158 @@ def writeHapMap(filename, result, tagseqs, passing_only=True):
                                [letters[c] for c in result.calls[:, m].tolist()]))
     with open(filename, mode='w', newline='') as fh:
         fh.write("\n".join(lines) + "\n")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Pairwise sample relations from the calls: the step behind the calls.  Everything is a function of one
+# table, joint[i][j][a][b] = the participating markers at which sample i is called a and sample j is called b; it is
+# exact in integers.  csrc/relate.hip computes it on the matrix cores from the calls where they lie, _relations_host
+# restates it in numpy.  Floats appear only in .distance and .kinship.
+RELATE_MAX_SAMPLES = 16384
+
+
+class DeviceCalls:
+    """A samples x markers uint8 call matrix in device memory (what call_genotypes(keep_device=True) leaves there), for
+    sample_relations(backend="gpu"): `ptr` a device pointer (0: no buffer, an empty matrix), `shape` = (samples,
+    markers)."""
+
+    def __init__(self, ptr, shape):
+        self.ptr, self.shape = int(ptr), (int(shape[0]), int(shape[1]))
+
+    def __len__(self):
+        return self.shape[0]
+
+
+class RelationResult:
+    """What sample_relations returns: `.samples`, `.joint` (uint32 [S, S, 3, 3]) and, as int64 [S, S] arrays over the
+    ordered pairs, `.shared` (markers called in both), `.ibs0`, `.ibs1`, `.ibs2`, `.hethet`, `.het_i`, `.het_j`, `.dist`
+    (= ibs1 + 2 ibs0); `.distance` = dist / (2 shared) and `.kinship` = (hethet - 2 ibs0) / (het_i + het_j) as float64
+    with nan where the denominator is 0; `.duplicates` (list of (i, j), i < j); `.stats` (backend, ms, markers, used,
+    max_dist_ppm, min_shared)."""
+
+    def __init__(self, samples, joint, max_dist_ppm, min_shared, stats):
+        import numpy as np
+        J = joint.astype(np.int64)
+        self.samples, self.joint = samples, joint
+        self.shared = J.sum(axis=(2, 3))
+        self.ibs0 = J[:, :, 0, 2] + J[:, :, 2, 0]
+        self.ibs2 = J[:, :, 0, 0] + J[:, :, 1, 1] + J[:, :, 2, 2]
+        self.ibs1 = self.shared - self.ibs0 - self.ibs2
+        self.hethet = J[:, :, 1, 1].copy()
+        self.het_i = J[:, :, 1, :].sum(axis=2)
+        self.het_j = J[:, :, :, 1].sum(axis=2)
+        self.dist = self.ibs1 + 2 * self.ibs0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.distance = np.where(self.shared > 0, self.dist / (2.0 * self.shared), np.nan)
+            het = self.het_i + self.het_j
+            self.kinship = np.where(het > 0, (self.hethet - 2 * self.ibs0) / het.astype(np.float64), np.nan)
+        # the duplicate rule in integers: dist <= 2^32 and 10^6 < 2^20, so every product stays below 2^53
+        flagged = (self.shared >= min_shared) & (self.dist * 1000000 <= max_dist_ppm * 2 * self.shared)
+        self.duplicates = [(int(i), int(j)) for i, j in zip(*np.nonzero(np.triu(flagged, 1)))]
+        self.stats = dict(stats, max_dist_ppm=max_dist_ppm, min_shared=min_shared)
+
+
+def _relations_host(calls, use=None):
+    """joint[i][j][a][b] of DESIGN 4.15 in numpy: the Gram product of the one-hot planes, in float32 over blocks of
+    markers short enough to be exact there (< 2^24), summed in int64."""
+    import numpy as np
+    calls = np.asarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    total = np.zeros((3 * S, 3 * S), dtype=np.int64)
+    cols = np.arange(M) if use is None else np.nonzero(np.asarray(use) != 0)[0]
+    block = max(1, min((1 << 24) - 1, (1 << 26) // max(1, 3 * S)))
+    for lo in range(0, len(cols), block):
+        part = calls[:, cols[lo:lo + block]]
+        X = np.stack([part == a for a in (0, 1, 2)], axis=1).reshape(3 * S, -1).astype(np.float32)
+        total += np.rint(X @ X.T).astype(np.int64)
+    return total.reshape(S, 3, S, 3).transpose(0, 2, 1, 3).astype(np.uint32)
+
+
+def sample_relations(calls, samnames, mask=None, max_dist=0.02, min_shared=50, device=0, backend="gpu"):
+    """Pairwise relations of the samples from their genotype calls: are two wells the same plant, was a
+    sample swapped, which samples are relatives.
+
+    calls: a samples x markers matrix of codes 0, 1, 2 (copies of allele 1) and 3 (missing) -- numpy or lists -- or a
+    DeviceCalls (backend="gpu" only; there any byte above 2 is missing).  mask: one entry per marker, a marker takes
+    part iff its entry is true (None: all) -- call_genotypes' `.mask` restricts the relations to the markers that pass.
+    For every pair the 3 x 3 table of how often call a in one sample meets call b in the other is counted; the IBS
+    counts, the IBS distance dist / (2 shared) and the KING-robust kinship (hethet - 2 ibs0) / (het_i + het_j) follow
+    from it.  A pair i < j is a duplicate iff shared >= min_shared and dist * 10^6 <= max_dist_ppm * 2 * shared, in
+    integers (max_dist is taken in parts per million).  backend="gpu" runs csrc/relate.hip on the calls where they lie;
+    backend="host" is the numpy restatement.  Returns a RelationResult."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    max_dist_ppm = _ppm(max_dist, 0, 1000000, "max_dist")
+    if isinstance(min_shared, bool) or int(min_shared) != min_shared or min_shared < 0:
+        raise ValueError("min_shared must be an integer of at least 0")
+    min_shared = int(min_shared)
+    on_device = isinstance(calls, DeviceCalls)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCalls matrix needs backend='gpu'")
+    samnames = list(samnames)
+    if not on_device:
+        calls = np.asarray(calls if len(calls) else np.zeros((0, 0 if mask is None else len(mask)), dtype=np.uint8))
+        if calls.ndim != 2:
+            raise ValueError("the call matrix must have two dimensions (samples x markers)")
+        if calls.dtype.kind not in "iub":
+            raise ValueError("the call matrix must hold the integer codes 0 .. 3, not {}".format(calls.dtype))
+        if calls.size and (int(calls.min()) < 0 or int(calls.max()) > 3):
+            raise ValueError("the call matrix must hold 0, 1, 2 or 3 (missing) only")
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    if len(samnames) != S:
+        raise ValueError("samnames must name every row of the call matrix")
+    if S > RELATE_MAX_SAMPLES:
+        raise ValueError("at most {} samples".format(RELATE_MAX_SAMPLES))
+    if M >= 1 << 31:
+        raise ValueError("markers must number below 2^31")
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (M,):
+            raise ValueError("mask must have one entry per marker")
+        mask = mask != 0
+    if backend == "host":
+        joint, ms = _relations_host(calls, mask), 0.0
+    else:
+        res = default_engine(device).relate_joint(calls.ptr or None if on_device else calls,
+                                                  shape=(S, M) if on_device else None, use=mask)
+        joint, ms = res.joint, res.ms
+    used = M if mask is None else int(mask.sum())
+    return RelationResult(samnames, joint, max_dist_ppm, min_shared, dict(backend=backend, ms=ms, markers=M, used=used))
+
+
+RELATION_COLUMNS = ("sample_i", "sample_j", "shared", "ibs0", "ibs1", "ibs2", "hethet", "het_i", "het_j", "distance",
+                    "kinship", "duplicate")
+
+
+def _na(x):
+    return "NA" if x != x else format(x, ".6f")
+
+
+def writeRelations(filename, result):
+    """One row per pair of samples i < j: the names, shared, ibs0, ibs1, ibs2, hethet, het_i, het_j, distance and
+    kinship (six decimals, NA where undefined) and duplicate (1 / 0); CSV with a header row, csv.writer's CRLF rows."""
+    dups = set(result.duplicates)
+    S = len(result.samples)
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(RELATION_COLUMNS)
+        for i in range(S):
+            for j in range(i + 1, S):
+                out.writerow([result.samples[i], result.samples[j]] +
+                             [int(getattr(result, k)[i, j]) for k in RELATION_COLUMNS[2:9]] +
+                             [_na(float(result.distance[i, j])), _na(float(result.kinship[i, j])), 1 if (i, j) in dups else 0])
+
+
+def writeDistanceMatrix(filename, result):
+    """The samples x samples IBS distances (six decimals, NA where two samples share no called marker): the sample
+    names in the header row and the first column; CSV, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow([""] + list(result.samples))
+        for i, name in enumerate(result.samples):
+            out.writerow([name] + [_na(float(x)) for x in result.distance[i]])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
