@@ -542,6 +542,48 @@ int td_relate_joint(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, c
                     uint32_t *joint_out /* HOST, 9*S*S, or NULL */, void **d_joint_out /* or NULL; the caller's, td_dev_free */,
                     double *ms);
 
+/* ---- pairwise marker LD (csrc/ld.hip; tagdigger_amd/tagdigger_fun.py marker_ld drives it) ------------------------------
+ *
+ * From the calls to the check of the markers against each other: which pairs of markers are correlated
+ * over the samples.  d_calls, the codes and use are those of the sample relations above: S x M uint8, row-major, in DEVICE
+ * memory, rows exactly M bytes apart, 0 / 1 / 2 copies of allele 1, ANY byte above 2 missing; marker m takes part iff
+ * use == NULL or use[m] != 0 (HOST, M bytes).  The rule, in integers only.  For two participating markers i < j (original
+ * numbering), over the samples s at which BOTH are called, with x = calls[s][i] and y = calls[s][j]:
+ *   n = sum 1, sx = sum x, sy = sum y, sxx = sum x^2, syy = sum y^2, sxy = sum x y
+ *   cov = n sxy - sx sy (signed), var_i = n sxx - sx^2, var_j = n syy - sy^2
+ * and the pair is an EDGE iff n >= min_shared, var_i > 0, var_j > 0 and cov^2 10^6 >= min_r2_ppm var_i var_j.  With
+ * S <= TD_LD_MAX_SAMPLES cov, var_i and var_j fit 32 bits and their products 64; the two sides of the comparison reach 76
+ * bits and are compared as 128-bit values.  r^2 = cov^2 / (var_i var_j) and the phase sign(cov) are the caller's to derive.
+ * The six sums are Gram products over the samples and run on the matrix cores in int8 with int32 accumulators: exact.
+ *
+ * *n_out is always the number of edges.  edges_out == NULL counts only.  With a buffer of `capacity` records and
+ * n <= capacity the edges are returned ascending by (i, j): the same bytes on every run.  With n > capacity the call
+ * returns TD_E_LIMIT; *n_out, degree_out and called_out are complete all the same and no record past the capacity has been
+ * written anywhere.  degree_out[m] (optional, HOST, M): the edges m takes part in, whether or not they fit the buffer;
+ * called_out[m] (optional, HOST, M): the samples called at m; both 0 for a marker that does not take part.  ms (optional):
+ * device time of the two kernels; td_ld_last_times gives the transpose, pair kernel (device ms) and sort (host ms) of the
+ * CALLING THREAD's last td_ld_pairs apart, whichever handle that call used (the times are kept per thread, not per handle).  No byte beyond calls[S M - 1] or use[M - 1] is read.
+ * Synchronous; waits for the work enqueued through this handle first.  Checked before anything is read, allocated or
+ * launched: S <= TD_LD_MAX_SAMPLES, M < 2^31, min_r2_ppm <= 10^6, no NULL matrix with S M > 0 (TD_E_ARG each); then more
+ * than TD_LD_MAX_MARKERS participating markers is TD_E_LIMIT.  After that S = 0 or fewer than two participating markers
+ * gives no edges without a launch. */
+typedef struct td_ld_edge {
+    uint32_t i, j;            /* the markers, i < j, original numbering                                    */
+    uint32_t shared;          /* n: samples called at both                                                */
+    int32_t cov;
+    uint32_t var_i, var_j;
+} td_ld_edge;                 /* 24 bytes */
+enum {
+    TD_LD_MAX_SAMPLES = 16384,
+    TD_LD_MAX_MARKERS = 1 << 20,
+    TD_LD_TILE = 64           /* markers along a workgroup's tile edge                                    */
+};
+int td_ld_pairs(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const uint8_t *use /* HOST, M bytes, or NULL */,
+                uint32_t min_r2_ppm, uint32_t min_shared, td_ld_edge *edges_out /* HOST, capacity records, or NULL */,
+                uint64_t capacity, uint64_t *n_out, uint32_t *degree_out /* HOST, M, or NULL */,
+                uint32_t *called_out /* HOST, M, or NULL */, double *ms);
+int td_ld_last_times(td_handle *h, double *out3 /* transpose ms, pair kernel ms, sort ms of this thread's last td_ld_pairs */);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */

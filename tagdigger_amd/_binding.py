@@ -26,6 +26,9 @@ TD_E = {
 }
 
 
+TD_E_LIMIT = -7
+
+
 class TagdigError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("%s: %s" % (TD_E.get(code, code), message))
@@ -168,6 +171,8 @@ def load():
     sig("td_geno_call", i32, vp, vp, u32, u32, u32, vp, vp, vp, C.POINTER(GenoParams), vp, C.POINTER(vp), vp, vp,
         C.POINTER(u64), dp)
     sig("td_relate_joint", i32, vp, vp, u32, u32, vp, vp, C.POINTER(vp), dp)
+    sig("td_ld_pairs", i32, vp, vp, u32, u32, vp, u32, u32, vp, u64, C.POINTER(u64), vp, vp, dp)
+    sig("td_ld_last_times", i32, vp, dp)
     _lib = L
     return L
 
@@ -187,7 +192,7 @@ EXPORTS = [
     "td_md5_device", "td_md5_files",
     "td_census_begin", "td_census_device", "td_census_file", "td_census_stats", "td_census_fetch", "td_census_end",
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
-    "td_geno_call", "td_relate_joint",
+    "td_geno_call", "td_relate_joint", "td_ld_pairs", "td_ld_last_times",
 ]
 
 

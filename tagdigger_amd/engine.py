@@ -145,6 +145,19 @@ class RelateJoint(collections.namedtuple("RelateJoint", "joint ms d_joint")):
     __slots__ = ()
 
 
+LD_MAX_SAMPLES = 16384      # TD_LD_MAX_SAMPLES: cov and var of a pair of markers fit 32 bits
+LD_MAX_MARKERS = 1 << 20    # TD_LD_MAX_MARKERS: participating markers of one call
+LD_TILE = 64                # TD_LD_TILE: markers along a workgroup's tile edge of csrc/ld.hip
+LD_EDGE = [("i", "<u4"), ("j", "<u4"), ("shared", "<u4"), ("cov", "<i4"), ("var_i", "<u4"), ("var_j", "<u4")]    # td_ld_edge
+
+
+class LDPairs(collections.namedtuple("LDPairs", "edges n degree called ms times")):
+    """What Engine.ld_pairs returns: edges (structured array with the fields of td_ld_edge, ascending by (i, j)), n (how
+    many there are), degree and called (uint32 [M]), ms (device time of the two kernels), times (dict: transpose_ms and
+    pairs_ms on the device, sort_ms on the host, of the call that returned the edges)."""
+    __slots__ = ()
+
+
 def counts_as_uint32(counts):
     """A count matrix as a C-contiguous uint32 array.  uint32 is what the device reads; another integer type is taken
     when every value fits, and refused otherwise."""
@@ -608,6 +621,67 @@ class Engine:
                 self.dev_free(uploaded)
         B.check(rc)
         return RelateJoint(joint, ms.value, d_joint.value if keep_device else None)
+
+    # ------------------------------------------------------------------ marker LD (td_ld_pairs; csrc/ld.hip)
+    def ld_pairs(self, calls, shape=None, use=None, min_r2_ppm=800000, min_shared=50, capacity=None, retry=True,
+                 count_only=False):
+        """td_ld_pairs: the pairs of participating markers i < j with n >= min_shared, var_i > 0, var_j > 0 and
+        cov^2 * 10^6 >= min_r2_ppm * var_i * var_j over the samples called at both (include/tagdig.h has the rule).
+        calls is a numpy uint8 matrix [S, M] (uploaded) or a device pointer with shape=(S, M).  use: M bytes, a marker
+        takes part iff its byte is not zero (None: all).  capacity: records of the first buffer (None: 8 per marker, at
+        least 2^16 and at most 2^20, 24 MB); when there are more edges the call is made once more with the exact size -- unless
+        retry=False, with which the TagdigError of TD_E_LIMIT is raised and carries what is complete all the same as `.n`,
+        `.degree` and `.called`.  count_only=True passes no buffer: no edges, but n, degree and called.  Returns an
+        LDPairs.  A failure raises TagdigError."""
+        import numpy as np
+        uploaded = None
+        if calls is None or isinstance(calls, int):
+            if shape is None:
+                raise ValueError("a device pointer needs shape=(samples, markers)")
+            S, M = (int(x) for x in shape)
+            d_calls = calls or 0
+        else:
+            host = np.ascontiguousarray(calls)
+            if host.ndim != 2 or host.dtype != np.uint8:
+                raise ValueError("the call matrix must be a uint8 matrix (samples x markers)")
+            S, M = host.shape
+            d_calls = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
+            if host.size:
+                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_calls), host.ctypes.data_as(C.c_void_p), host.nbytes))
+        try:
+            if use is not None:
+                use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+                if use.shape != (M,):
+                    raise ValueError("use must have one entry per marker")
+                if not M:
+                    use = None
+            in_range = M < 1 << 31                               # (the library answers TD_E_ARG otherwise)
+            degree = np.zeros(max(1, M if in_range else 1), dtype=np.uint32)
+            called = np.zeros(max(1, M if in_range else 1), dtype=np.uint32)
+            capacity = max(1 << 16, min(8 * M, 1 << 20) if in_range else 0) if capacity is None else max(0, int(capacity))
+            n, ms, total_ms = C.c_uint64(0), C.c_double(0), 0.0
+            for attempt in range(2):
+                edges = np.zeros(0 if count_only else max(1, capacity), dtype=LD_EDGE)
+                rc = self._L.td_ld_pairs(self._h, C.c_void_p(d_calls) if d_calls else None, S, M,
+                                         use.ctypes.data_as(C.c_void_p) if use is not None else None, int(min_r2_ppm),
+                                         int(min_shared), None if count_only else edges.ctypes.data_as(C.c_void_p), capacity, C.byref(n),
+                                         degree.ctypes.data_as(C.c_void_p), called.ctypes.data_as(C.c_void_p), C.byref(ms))
+                total_ms += ms.value
+                if rc == B.TD_E_LIMIT and n.value > capacity and attempt == 0 and retry:     # once more with the exact size
+                    capacity = n.value
+                    continue
+                break
+        finally:
+            if uploaded:
+                self.dev_free(uploaded)
+        if rc:
+            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err.n, err.degree, err.called = n.value, degree[:M], called[:M]
+            raise err
+        t = (C.c_double * 3)()
+        B.check(self._L.td_ld_last_times(self._h, t))
+        return LDPairs(edges[:0 if count_only else n.value].copy(), n.value, degree[:M], called[:M], total_ms,
+                       dict(transpose_ms=t[0], pairs_ms=t[1], sort_ms=t[2]))
 
     # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
     def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):

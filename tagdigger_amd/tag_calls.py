@@ -6,12 +6,15 @@ heterozygosity.
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --stats stats.csv --min-call-rate 0.8 --min-maf 0.05
     python -m tagdigger_amd.tag_calls -b key.csv --MergedTags markers.csv -e PstI -o calls.csv --hapmap calls.hmp.txt
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --relations pairs.csv --relations-matrix dist.csv
+    python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --ld ld_pairs.csv --ld-keep keep.txt --relations pairs.csv --relations-ld-pruned
 
 The input is the counter's CSV (samples in rows, tag names Marker_..._0 / Marker_..._1 in the header), or the
 libraries of a key file, which are counted first: every library's barcode rows are folded into one samples x tags
 matrix on the device, and the calls are made from that matrix where it lies -- it comes to the host only when
 --counts-out asks for the CSV as well.  -o has writeDiploidGeno's layout with the markers that pass.  --relations
 checks the samples themselves over the markers that pass (tag_relate's table; the calls stay on the device for it).
+--ld, --ld-groups and --ld-keep check those markers against each other (tag_ld's files, from the same calls on the
+device); --relations-ld-pruned then restricts the relations to the LD-pruned markers.
 """
 import argparse
 import csv
@@ -43,6 +46,12 @@ def build_parser():
     ap.add_argument("--relations-matrix", metavar="FILE", help="distance matrix CSV to write (samples x samples)")
     ap.add_argument("--max-dist", type=float, default=0.02, help="--relations: a pair at most this far apart is a duplicate")
     ap.add_argument("--min-shared", type=int, default=50, help="--relations: ... when at least this many markers are called in both")
+    ap.add_argument("--ld", metavar="FILE", help="LD pairs CSV to write: the pairs of passing markers in LD (see tag_ld)")
+    ap.add_argument("--ld-groups", metavar="FILE", help="LD groups CSV to write (one row per passing marker)")
+    ap.add_argument("--ld-keep", metavar="FILE", help="names of the LD-pruned passing markers to write, one per line")
+    ap.add_argument("--min-r2", type=float, default=0.8, help="--ld: a pair with at least this r^2 is in LD")
+    ap.add_argument("--ld-min-shared", type=int, default=50, help="--ld: ... when at least this many samples are called at both")
+    ap.add_argument("--relations-ld-pruned", action="store_true", help="--relations over the markers that pass AND survive LD pruning")
     ap.add_argument("--rule", choices=list(tf.GENO_RULES), default="likelihood",
                     help="likelihood: heterozygous when the rarer allele's reads are too many for errors; presence: when both were seen")
     ap.add_argument("--err", type=float, default=0.01, help="sequencing error rate of the likelihood rule")
@@ -120,7 +129,10 @@ def main(argv=None):
     params = dict(rule=args.rule, err=args.err, min_depth=args.min_depth, min_call_rate=args.min_call_rate,
                   min_maf=args.min_maf, max_het=args.max_het, device=args.td_device)
     relate = args.relations is not None or args.relations_matrix is not None
-    eng = d_counts = d_calls = relations = None
+    if args.relations_ld_pruned and not relate:
+        raise Exception("--relations-ld-pruned goes with --relations or --relations-matrix.")
+    ld = args.relations_ld_pruned or any(x is not None for x in (args.ld, args.ld_groups, args.ld_keep))
+    eng = d_counts = d_calls = relations = ldres = ld_keep = None
     if args.counts is not None:
         if args.counts_out is not None:
             raise Exception("--counts-out goes with counting (-b); -i is that file already.")
@@ -150,15 +162,20 @@ def main(argv=None):
         samples, d_counts = count_on_device(eng, keys, sequences, site, args.maxreads)
         counts, backend = d_counts, "gpu"
     try:
-        keep = relate and backend == "gpu"               # the relations read the calls where the call kernel wrote them
+        keep = (relate or ld) and backend == "gpu"       # relations and LD read the calls where the call kernel wrote them
         result = tf.call_genotypes(counts, samples, names, backend=backend, keep_device=keep, **params)
         d_calls = result.d_calls
         if d_counts is not None and args.counts_out is not None:
             import numpy as np
             host = np.frombuffer(eng.d2h(d_counts.ptr, d_counts.shape[0] * d_counts.shape[1] * 4), dtype=np.uint32)
             tf.writeCounts(args.counts_out, host.reshape(d_counts.shape), samples, names)
+        if ld:
+            ldres = tf.marker_ld(d_calls if keep else result.calls, result.markers, mask=result.mask, min_r2=args.min_r2,
+                                 min_shared=args.ld_min_shared, device=args.td_device, backend=backend)
+            ld_keep = tf.ld_prune(ldres)
         if relate:
-            relations = tf.sample_relations(d_calls if keep else result.calls, samples, mask=result.mask, max_dist=args.max_dist,
+            relations = tf.sample_relations(d_calls if keep else result.calls, samples,
+                                            mask=result.mask & ld_keep if args.relations_ld_pruned else result.mask, max_dist=args.max_dist,
                                             min_shared=args.min_shared, device=args.td_device, backend=backend)
     finally:
         if d_counts is not None:
@@ -174,6 +191,13 @@ def main(argv=None):
         tf.writeRelations(args.relations, relations)
     if args.relations_matrix is not None:
         tf.writeDistanceMatrix(args.relations_matrix, relations)
+    if args.ld is not None:
+        tf.writeLDPairs(args.ld, ldres)
+    if args.ld_groups is not None:
+        tf.writeLDGroups(args.ld_groups, ldres, keep=ld_keep)
+    if args.ld_keep is not None:
+        from .tag_ld import write_keep
+        write_keep(args.ld_keep, ldres, ld_keep)
     print(stats_line(result))
     return 0
 

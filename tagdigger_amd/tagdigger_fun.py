@@ -1523,6 +1523,215 @@ def writeDistanceMatrix(filename, result):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Pairwise marker LD from the calls: the check of the markers against each other.  For two participating
+# markers i < j, over the samples called at both: n, sx, sy, sxx, syy, sxy; cov = n sxy - sx sy, var_i = n sxx - sx^2,
+# var_j = n syy - sy^2.  The pair is an edge iff n >= min_shared, var_i > 0, var_j > 0 and cov^2 10^6 >= min_r2_ppm var_i
+# var_j -- integers only, the two sides as 128-bit values.  csrc/ld.hip decides it on the matrix cores from the calls
+# where they lie, _ld_host restates it in numpy.  Floats appear only in .r2.
+LD_MAX_SAMPLES = 16384
+LD_MAX_MARKERS = 1 << 20
+LD_EDGE = [("i", "<u4"), ("j", "<u4"), ("shared", "<u4"), ("cov", "<i4"), ("var_i", "<u4"), ("var_j", "<u4")]
+_LD_HOST_CELLS = 1 << 21    # pairs of one block of _ld_host: a dozen int64 arrays of this size at a time
+
+
+class LDResult:
+    """What marker_ld returns: `.markers` (all M names), `.mask` (bool [M]: the marker takes part), `.edges` (structured
+    array i, j, shared, cov, var_i, var_j; i < j in the numbering of `.markers`, ascending by (i, j)), `.r2` (float64 per
+    edge, cov^2 / (var_i var_j)), `.phase` (int8 per edge, +1 / -1: the sign of cov; 0 only where min_r2 = 0 lets a pair
+    with cov = 0 in), `.degree` and `.called` (uint32 [M]; 0 for markers that do not take part), `.stats` (backend, ms,
+    markers, used, edges, min_r2_ppm, min_shared)."""
+
+    def __init__(self, markers, mask, edges, degree, called, stats):
+        import numpy as np
+        self.markers, self.mask, self.edges, self.degree, self.called = markers, mask, edges, degree, called
+        # cov^2 and var_i var_j pass 2^53: the quotient of Python's integers is the correctly rounded one
+        self.r2 = np.array([c * c / (a * b) for c, a, b in zip(edges["cov"].tolist(), edges["var_i"].tolist(),
+                                                                 edges["var_j"].tolist())], dtype=np.float64)
+        self.phase = np.sign(edges["cov"]).astype(np.int8)
+        self.stats = dict(stats, edges=len(edges))
+
+
+def _ld_wide(a, k):
+    """a * k as two uint64 words (high, low 32 bits) for a < 2^57 and k <= 2^20: nothing wraps."""
+    import numpy as np
+    t = (a & np.uint64(0xffffffff)) * np.uint64(k)
+    return (a >> np.uint64(32)) * np.uint64(k) + (t >> np.uint64(32)), t & np.uint64(0xffffffff)
+
+
+def _ld_host(calls, use, min_r2_ppm, min_shared):
+    """The rule of DESIGN 4.16 in numpy, over blocks of markers: the six sums as float32 products (at most 4 * 16384,
+    exact there), everything after them in 64-bit integers, the comparison on two words.  Returns (edges ascending by
+    (i, j), degree, called)."""
+    import numpy as np
+    calls = np.asarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    cols = np.arange(M) if use is None else np.nonzero(np.asarray(use) != 0)[0]
+    part = calls[:, cols]
+    ok = part <= 2
+    C = ok.astype(np.float32)
+    X = np.where(ok, part, 0).astype(np.float32)
+    Q = X * X
+    called = np.zeros(M, dtype=np.uint32)
+    called[cols] = ok.sum(axis=0)
+    degree = np.zeros(M, dtype=np.uint32)
+    Mp = len(cols)
+    found = []
+    block = max(1, _LD_HOST_CELLS // max(1, Mp))
+    for lo in range(0, Mp if S else 0, block):
+        hi = min(Mp, lo + block)
+        Cb, Xb, Qb = C[:, lo:hi].T, X[:, lo:hi].T, Q[:, lo:hi].T
+
+        def gram(a, b):
+            return np.rint(a @ b[:, lo:]).astype(np.int64)
+
+        n, sx, sy, sxy, sxx, syy = gram(Cb, C), gram(Xb, C), gram(Cb, X), gram(Xb, X), gram(Qb, C), gram(Cb, Q)
+        cov, var_i, var_j = n * sxy - sx * sy, n * sxx - sx * sx, n * syy - sy * sy
+        lhs_hi, lhs_lo = _ld_wide((cov * cov).astype(np.uint64), 1000000)
+        rhs_hi, rhs_lo = _ld_wide((var_i * var_j).astype(np.uint64), min_r2_ppm)
+        edge = (n >= min_shared) & (var_i > 0) & (var_j > 0) & ((lhs_hi > rhs_hi) | ((lhs_hi == rhs_hi) & (lhs_lo >= rhs_lo)))
+        edge &= np.arange(lo, Mp)[None, :] > np.arange(lo, hi)[:, None]                # i < j
+        bi, bj = np.nonzero(edge)                                                      # row-major: ascending (i, j)
+        rec = np.zeros(len(bi), dtype=LD_EDGE)
+        rec["i"], rec["j"] = cols[bi + lo], cols[bj + lo]
+        for name, a in (("shared", n), ("cov", cov), ("var_i", var_i), ("var_j", var_j)):
+            rec[name] = a[bi, bj]
+        found.append(rec)
+    edges = np.concatenate(found) if found else np.zeros(0, dtype=LD_EDGE)
+    if len(edges):
+        degree += np.bincount(edges["i"], minlength=M).astype(np.uint32) + np.bincount(edges["j"], minlength=M).astype(np.uint32)
+    return edges, degree, called
+
+
+def marker_ld(calls, marknames, mask=None, min_r2=0.8, min_shared=50, device=0, backend="gpu"):
+    """Pairwise LD of the markers from the genotype calls: which markers are redundant, which co-segregate,
+    which were made twice.
+
+    calls: a samples x markers matrix of codes 0, 1, 2 (copies of allele 1) and 3 (missing) -- numpy or lists -- or a
+    DeviceCalls (backend="gpu" only; there any byte above 2 is missing).  mask: one entry per marker, a marker takes
+    part iff its entry is true (None: all).  A pair of participating markers i < j is an edge iff at least min_shared
+    samples are called at both, both vary among those samples and r^2 = cov^2 / (var_i var_j) >= min_r2, compared in
+    integers (min_r2 is taken in parts per million).  backend="gpu" runs csrc/ld.hip on the calls where they lie;
+    backend="host" is the numpy restatement: the same edges in the same order.  Returns an LDResult."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    min_r2_ppm = _ppm(min_r2, 0, 1000000, "min_r2")
+    if isinstance(min_shared, bool) or int(min_shared) != min_shared or not 0 <= min_shared < 1 << 32:
+        raise ValueError("min_shared must be an integer of at least 0")
+    min_shared = int(min_shared)
+    on_device = isinstance(calls, DeviceCalls)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCalls matrix needs backend='gpu'")
+    marknames = list(marknames)
+    if not on_device:
+        calls = np.asarray(calls if len(calls) else np.zeros((0, len(marknames)), dtype=np.uint8))
+        if calls.ndim != 2:
+            raise ValueError("the call matrix must have two dimensions (samples x markers)")
+        if calls.dtype.kind not in "iub":
+            raise ValueError("the call matrix must hold the integer codes 0 .. 3, not {}".format(calls.dtype))
+        if calls.size and (int(calls.min()) < 0 or int(calls.max()) > 3):
+            raise ValueError("the call matrix must hold 0, 1, 2 or 3 (missing) only")
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    if len(marknames) != M:
+        raise ValueError("marknames must name every column of the call matrix")
+    if S > LD_MAX_SAMPLES:
+        raise ValueError("at most {} samples".format(LD_MAX_SAMPLES))
+    if M >= 1 << 31:
+        raise ValueError("markers must number below 2^31")
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (M,):
+            raise ValueError("mask must have one entry per marker")
+        mask = mask != 0
+    used = M if mask is None else int(mask.sum())
+    if used > LD_MAX_MARKERS:
+        raise ValueError("{} participating markers, at most {}".format(used, LD_MAX_MARKERS))
+    if backend == "host":
+        (edges, degree, called), ms = _ld_host(calls, mask, min_r2_ppm, min_shared), 0.0
+    else:
+        res = default_engine(device).ld_pairs(calls.ptr or None if on_device else calls, shape=(S, M) if on_device else None,
+                                              use=mask, min_r2_ppm=min_r2_ppm, min_shared=min_shared)
+        edges, degree, called, ms = res.edges, res.degree, res.called, res.ms
+    return LDResult(marknames, np.ones(M, dtype=bool) if mask is None else mask, edges, degree, called,
+                    dict(backend=backend, ms=ms, markers=M, used=used, min_r2_ppm=min_r2_ppm, min_shared=min_shared))
+
+
+def ld_groups(result):
+    """The connected components of the participating markers under the edges (linkage groups, bins of co-segregating
+    markers): int64 [M], groups numbered from 1 in the order of their smallest marker, singletons included, 0 for a
+    marker that does not take part."""
+    import numpy as np
+    M = len(result.markers)
+    label = np.arange(M, dtype=np.int64)
+    ei, ej = result.edges["i"].astype(np.int64), result.edges["j"].astype(np.int64)
+    while len(ei):                                 # every marker takes the smallest label around it, then its label's label
+        new = label.copy()
+        np.minimum.at(new, ei, label[ej])
+        np.minimum.at(new, ej, label[ei])
+        new = new[new]
+        if np.array_equal(new, label):
+            break
+        label = new
+    groups = np.zeros(M, dtype=np.int64)
+    part = np.nonzero(result.mask)[0]
+    roots = np.unique(label[part])                 # ascending: a component's label is its smallest marker
+    groups[part] = np.searchsorted(roots, label[part]) + 1
+    return groups
+
+
+def ld_prune(result):
+    """A keep mask over all M markers: the participating markers are walked by (`called` descending, index ascending)
+    and a marker is kept iff none of its neighbours is kept already.  No two kept markers are joined by an edge, every
+    dropped participating marker has a kept neighbour, and a marker that does not take part is False."""
+    import numpy as np
+    M = len(result.markers)
+    ei, ej = result.edges["i"].astype(np.int64), result.edges["j"].astype(np.int64)
+    src, dst = np.concatenate([ei, ej]), np.concatenate([ej, ei])
+    order = np.argsort(src, kind="stable")
+    dst = dst[order]
+    start = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=M))])
+    part = np.nonzero(result.mask)[0]
+    keep = np.zeros(M, dtype=bool)
+    for m in part[np.lexsort((part, -result.called[part].astype(np.int64)))]:
+        if not keep[dst[start[m]:start[m + 1]]].any():
+            keep[m] = True
+    return keep
+
+
+LD_PAIR_COLUMNS = ("marker_i", "marker_j", "shared", "r2", "phase")
+LD_GROUP_COLUMNS = ("marker", "group", "group_size", "degree", "called", "kept")
+
+
+def writeLDPairs(filename, result):
+    """One row per edge: the two marker names, shared, r2 (six decimals) and phase (+ / -, by the sign of cov; 0 when
+    cov is 0); CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(LD_PAIR_COLUMNS)
+        for e, r2 in zip(result.edges, result.r2):
+            cov = int(e["cov"])
+            out.writerow([result.markers[int(e["i"])], result.markers[int(e["j"])], int(e["shared"]), format(float(r2), ".6f"),
+                          "+" if cov > 0 else "-" if cov < 0 else "0"])
+
+
+def writeLDGroups(filename, result, groups=None, keep=None):
+    """One row per participating marker: marker, group (ld_groups), group_size, degree, called, kept (ld_prune: 1 / 0);
+    CSV with a header row, csv.writer's CRLF rows.  groups, keep: what ld_groups and ld_prune gave for this result, where
+    the caller has them already."""
+    import numpy as np
+    groups = ld_groups(result) if groups is None else groups
+    keep = ld_prune(result) if keep is None else keep
+    sizes = np.bincount(groups)
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(LD_GROUP_COLUMNS)
+        for m in np.nonzero(result.mask)[0]:
+            out.writerow([result.markers[m], int(groups[m]), int(sizes[groups[m]]), int(result.degree[m]), int(result.called[m]),
+                          1 if keep[m] else 0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Tag Manager (reference tagdigger_fun.py:1389-1905 and the prompts of :936-1028, :1182-1200).
 #
 # Every function keeps the reference's signature, return values, printed lines, files and exceptions.  Those with a
