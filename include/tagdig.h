@@ -664,6 +664,8 @@ int64_t td_format_csv_row(const int64_t *vals, uint64_t n, char *out, uint64_t c
  *   "zb_members"     BGZF members per GPU batch (tests; the built-in 49 152 is also the maximum)
  *   "stage_kb"       KiB per staged piece of a host buffer, plain file or host-inflated stream (tests; 64 .. 32 768,
  *                    0 = the built-in 32 MiB)
+ *   "max_grid"       cap on the workgroups of the free-running path's main pass, k_fast, k_fast2 or k_fast4 (tests: with 1,
+ *                    one workgroup takes every tile, run after run; 0 = no cap, the default).  The fix-up pass follows it
  *   "md5_piece"      td_md5_files: bytes a file contributes per round (tests; a multiple of 64, 0 = the built-in size)
  *   "tagnet_max_compares"  td_tagnet_build: the compare cap (tests; 0 = TD_TAGNET_DEFAULT_MAX_COMPARES)
  *   "debug_ablate"   timing-only ablation bits -- the counts are WRONG when non-zero

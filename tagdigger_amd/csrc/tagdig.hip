@@ -257,6 +257,7 @@ struct td_handle {
     int run = 8;                              // k_fast2: consecutive tiles per workgroup turn (measured: 4-16 alike, 1 and 64+ slower)
     int hot_cache = 1;                        // k_fast2: count through the per-wave hot-cell cache
     int f4_nprod = 0;                         // k_fast4: producer waves of sixteen (0: k_f4_estimate's, from the buffer's line density)
+    uint32_t max_grid = 0;                    // (tests: cap on the free-running main pass's grid, so that few workgroups take many tiles each; 0 = none)
     uint64_t fast_max_matrix = 1ull << 32;    // the free-running kernel addresses cells as base + 32-bit byte offset
     uint32_t debug_ablate = 0;
     double table_load = 0.25;
@@ -550,7 +551,8 @@ int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
             }
             bpc = h->occ_val;
         }
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cu * bpc);
+        uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)h->num_cu * bpc);
+        if (h->max_grid) grid = std::min(grid, h->max_grid);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->timing) {
             if (h->ev_used == h->ev_pool.size()) {
@@ -2810,6 +2812,8 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
         h->flush_limit = value > 0 ? std::min<uint64_t>((uint64_t)value, 0xFFFFFFFFull) : 0xFFFFFFFFull;
     else if (n == "stage_kb")                   // (tests: pieces of a host buffer or plain file small enough for seams inside a small input; 0 = the built-in 32 MiB)
         h->stage_kb = value > 0 ? (uint32_t)std::max<int64_t>(64, std::min<int64_t>(value, 32768)) : 0;
+    else if (n == "max_grid")                   // (tests: few workgroups take the whole buffer, each through many runs of its ring; 0 = no cap)
+        h->max_grid = value > 0 ? (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF) : 0;
     else if (n == "debug_ablate") h->debug_ablate = (uint32_t)value;   // timing-only ablations, wrong results
     else return fail(TD_E_ARG, "unknown option " + n);
     return TD_OK;

@@ -135,16 +135,18 @@ def test_fuzz_cases_that_once_failed(eng, seed):
     want = c_oracle.COracle(barcodes, tags, cutsite).count_bytes(data, stats=ost)
     eng.set_index(barcodes, tags, cutsite)
     try:
-        for nprod in (0, 7, 8, 9, 10, 11, 12, 13):
-            apply_mode(eng, dict(fastpath=1, kernel=4, f4_nprod=nprod))
-            for _ in range(3):
-                eng.reset()
-                eng.count_bytes(data)
-                st = eng.stats()
-                assert (eng.counts_numpy() == want).all(), nprod
-                assert (st["reads"], st["barcut"], st["tag"]) == (ost["reads"], ost["barcut"], ost["tag"]), nprod
+        for max_grid in (0, 1):             # (1: one workgroup takes all the tiles through its ring)
+            eng.set_option("max_grid", max_grid)
+            for nprod in (0, 7, 8, 9, 10, 11, 12, 13):
+                apply_mode(eng, dict(fastpath=1, kernel=4, f4_nprod=nprod))
+                for _ in range(3):
+                    eng.reset()
+                    eng.count_bytes(data)
+                    st = eng.stats()
+                    assert (eng.counts_numpy() == want).all(), (max_grid, nprod)
+                    assert (st["reads"], st["barcut"], st["tag"]) == (ost["reads"], ost["barcut"], ost["tag"]), (max_grid, nprod)
     finally:
-        apply_mode(eng, dict(f4_nprod=0))
+        apply_mode(eng, dict(f4_nprod=0, max_grid=0))
         apply_mode(eng, DEFAULT_MODE)
 
 
