@@ -584,6 +584,44 @@ int td_ld_pairs(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const
                 uint32_t *called_out /* HOST, M, or NULL */, double *ms);
 int td_ld_last_times(td_handle *h, double *out3 /* transpose ms, pair kernel ms, sort ms of this thread's last td_ld_pairs */);
 
+/* ---- LD-kNN imputation of the missing calls (csrc/impute.hip; tagdigger_amd/tagdigger_fun.py impute_calls drives it) ----
+ *
+ * Fills the holes of the call matrix from the samples most alike over the markers most in LD.  d_calls
+ * and the codes are those of the two sections above: S x M uint8, row-major, in DEVICE memory, rows exactly M bytes apart,
+ * 0 / 1 / 2 copies of allele 1, ANY byte above 2 missing.  nbr (HOST, M x L int32) is the neighbour table: row m lists the
+ * markers whose calls stand in for marker m; an entry is -1 (skipped, anywhere in the row) or a marker below M, never m
+ * itself, and none twice in a row (tagdigger_fun.ld_neighbours makes it from td_ld_pairs' edges).  The rule, in integers
+ * only.  For marker m let N(m) be the entries of its row that are not -1.  For every TARGET sample t with calls[t][m] > 2,
+ * every DONOR d != t with calls[d][m] <= 2 gets, over B = the q in N(m) with calls[t][q] <= 2 and calls[d][q] <= 2:
+ *   ovl = |B|,  dist = sum over B of |calls[t][q] - calls[d][q]|,  eligible iff ovl >= min_overlap,
+ *   w = floor(32768 (2 ovl - dist) / ovl), in 0 .. 65 536.
+ * The VOTERS are the first k eligible donors by (w descending, d ascending); V[g] = the sum of w over the voters with
+ * calls[d][m] == g, total = V[0] + V[1] + V[2].  The cell becomes g iff there is a voter, total > 0, exactly one g attains
+ * max V, and V[g] 10^6 >= min_conf_ppm total (64-bit).  Otherwise it keeps its input byte, whatever value above 2 that
+ * was; called cells are copied byte for byte.  Only the INPUT's calls are ever read: an imputed value serves nobody as a
+ * donor's or a neighbour's call, so the result depends on no order.
+ * Per marker, stats_out[TD_IMPUTE_STATS m + ...]: missing, imputed, no_donor (targets without an eligible donor, every
+ * target of a marker with N(m) empty included), undecided (the rest: tie, zero total, under the confidence).
+ * calls_out (optional, HOST, S x M) receives the filled matrix; d_calls_out (optional) the DEVICE buffer it was made in,
+ * which is then the caller's (td_dev_free).  ms (optional): device time of the two kernels; td_impute_last_times gives the
+ * transpose and the vote kernel of the CALLING THREAD's last td_impute_knn apart.  No byte beyond calls[S M - 1] is read.
+ * Synchronous; waits for the work enqueued through this handle first.  Checked before anything is allocated or launched,
+ * TD_E_ARG each: S <= TD_IMPUTE_MAX_SAMPLES (the samples' planes, 24 bytes each, lie in one workgroup's LDS), L in
+ * 1 .. TD_IMPUTE_MAX_NBR, k in 1 .. TD_IMPUTE_MAX_K, min_overlap >= 1, min_conf_ppm <= 10^6, M < 2^31, no NULL matrix or
+ * table with S M > 0, no bad row of the table (td_last_bad_index gives the marker).  After that S = 0 or M = 0 succeeds
+ * without a launch. */
+typedef struct td_impute_params { uint32_t L, k, min_overlap, min_conf_ppm; } td_impute_params;
+enum {
+    TD_IMPUTE_MAX_SAMPLES = 4096,
+    TD_IMPUTE_MAX_NBR = 64,
+    TD_IMPUTE_MAX_K = 32,
+    TD_IMPUTE_STATS = 4       /* missing, imputed, no_donor, undecided                                    */
+};
+int td_impute_knn(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const int32_t *nbr /* HOST, M*L */,
+                  const td_impute_params *p, uint8_t *calls_out /* HOST, S*M, or NULL */,
+                  void **d_calls_out /* or NULL; the caller's, td_dev_free */, uint32_t *stats_out /* HOST, M*4, or NULL */, double *ms);
+int td_impute_last_times(td_handle *h, double *out2 /* transpose ms, vote kernel ms of this thread's last td_impute_knn */);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */

@@ -53,6 +53,11 @@ class GenoParams(C.Structure):
                 ("min_maf_ppm", C.c_uint32), ("max_het_ppm", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ImputeParams(C.Structure):
+    """td_impute_params of include/tagdig.h"""
+    _fields_ = [("L", C.c_uint32), ("k", C.c_uint32), ("min_overlap", C.c_uint32), ("min_conf_ppm", C.c_uint32)]
+
+
 def _hip_runtime_candidates():
     env = os.environ.get("TAGDIG_HIP_RUNTIME")
     if env:
@@ -173,6 +178,8 @@ def load():
     sig("td_relate_joint", i32, vp, vp, u32, u32, vp, vp, C.POINTER(vp), dp)
     sig("td_ld_pairs", i32, vp, vp, u32, u32, vp, u32, u32, vp, u64, C.POINTER(u64), vp, vp, dp)
     sig("td_ld_last_times", i32, vp, dp)
+    sig("td_impute_knn", i32, vp, vp, u32, u32, vp, C.POINTER(ImputeParams), vp, C.POINTER(vp), vp, dp)
+    sig("td_impute_last_times", i32, vp, dp)
     _lib = L
     return L
 
@@ -193,6 +200,7 @@ EXPORTS = [
     "td_census_begin", "td_census_device", "td_census_file", "td_census_stats", "td_census_fetch", "td_census_end",
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
     "td_geno_call", "td_relate_joint", "td_ld_pairs", "td_ld_last_times",
+    "td_impute_knn", "td_impute_last_times",
 ]
 
 

@@ -158,6 +158,19 @@ class LDPairs(collections.namedtuple("LDPairs", "edges n degree called ms times"
     __slots__ = ()
 
 
+IMPUTE_MAX_SAMPLES = 4096   # TD_IMPUTE_MAX_SAMPLES: the samples' planes lie in one workgroup's LDS
+IMPUTE_MAX_NBR = 64         # TD_IMPUTE_MAX_NBR: a plane is one 64-bit word per sample
+IMPUTE_MAX_K = 32           # TD_IMPUTE_MAX_K: voters of a cell
+IMPUTE_STATS = ("missing", "imputed", "no_donor", "undecided")     # the columns of a marker's statistics row
+
+
+class ImputeKnn(collections.namedtuple("ImputeKnn", "calls stats ms times d_calls")):
+    """What Engine.impute_knn returns: calls (uint8 [S, M], the filled matrix; None when it was not fetched), stats
+    (uint32 [M, 4] by IMPUTE_STATS), ms (device time of the two kernels), times (dict: transpose_ms, vote_ms), d_calls (the
+    device buffer of the filled matrix when it was asked for -- the caller's, to be freed with dev_free -- else None)."""
+    __slots__ = ()
+
+
 def counts_as_uint32(counts):
     """A count matrix as a C-contiguous uint32 array.  uint32 is what the device reads; another integer type is taken
     when every value fits, and refused otherwise."""
@@ -682,6 +695,55 @@ class Engine:
         B.check(self._L.td_ld_last_times(self._h, t))
         return LDPairs(edges[:0 if count_only else n.value].copy(), n.value, degree[:M], called[:M], total_ms,
                        dict(transpose_ms=t[0], pairs_ms=t[1], sort_ms=t[2]))
+
+    # ------------------------------------------------------------------ LD-kNN imputation (td_impute_knn; csrc/impute.hip)
+    def impute_knn(self, calls, nbr, shape=None, k=10, min_overlap=4, min_conf_ppm=600000, fetch=True, keep_device=False):
+        """td_impute_knn: every missing cell (a byte above 2) of the call matrix is filled by the vote of the k samples
+        most alike over the marker's neighbours, or keeps its byte (include/tagdig.h has the rule).  calls is a numpy
+        uint8 matrix [S, M] (uploaded) or a device pointer with shape=(S, M).  nbr: int32 [M, L], row m the markers that
+        stand in for marker m, -1 where there is none (tagdigger_fun.ld_neighbours).  fetch=False leaves the filled matrix
+        on the device; keep_device=True hands its device buffer out as `.d_calls`.  Returns an ImputeKnn.  A failure
+        raises TagdigError; `.bad_index` holds the marker for a bad row of the table."""
+        import numpy as np
+        nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+        if nbr.ndim != 2:
+            raise ValueError("the neighbour table must have two dimensions (markers x neighbours)")
+        uploaded = None
+        if calls is None or isinstance(calls, int):
+            if shape is None:
+                raise ValueError("a device pointer needs shape=(samples, markers)")
+            S, M = (int(x) for x in shape)
+            d_calls = calls or 0
+        else:
+            host = np.ascontiguousarray(calls)
+            if host.ndim != 2 or host.dtype != np.uint8:
+                raise ValueError("the call matrix must be a uint8 matrix (samples x markers)")
+            S, M = host.shape
+            d_calls = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
+            if host.size:
+                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_calls), host.ctypes.data_as(C.c_void_p), host.nbytes))
+        try:
+            in_range = S <= IMPUTE_MAX_SAMPLES and M < 1 << 31     # (the library answers TD_E_ARG otherwise)
+            if in_range and nbr.shape[0] != M:
+                raise ValueError("the neighbour table must have one row per marker")
+            par = B.ImputeParams(nbr.shape[1], int(k), int(min_overlap), int(min_conf_ppm))
+            out = np.zeros((S, M), dtype=np.uint8) if fetch and in_range else None
+            stats = np.zeros((max(1, M if in_range else 1), len(IMPUTE_STATS)), dtype=np.uint32)
+            ms, d_out = C.c_double(0), C.c_void_p()
+            rc = self._L.td_impute_knn(self._h, C.c_void_p(d_calls) if d_calls else None, S, M,
+                                       nbr.ctypes.data_as(C.c_void_p) if nbr.size else None, C.byref(par),
+                                       out.ctypes.data_as(C.c_void_p) if out is not None and out.size else None,
+                                       C.byref(d_out) if keep_device else None, stats.ctypes.data_as(C.c_void_p), C.byref(ms))
+        finally:
+            if uploaded:
+                self.dev_free(uploaded)
+        if rc:
+            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err.bad_index = self._L.td_last_bad_index() if rc == -2 and err.detail.startswith("neighbours of marker ") else None
+            raise err
+        t = (C.c_double * 2)()
+        B.check(self._L.td_impute_last_times(self._h, t))
+        return ImputeKnn(out, stats[:M], ms.value, dict(transpose_ms=t[0], vote_ms=t[1]), d_out.value if keep_device else None)
 
     # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
     def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):

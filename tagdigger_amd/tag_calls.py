@@ -7,6 +7,7 @@ heterozygosity.
     python -m tagdigger_amd.tag_calls -b key.csv --MergedTags markers.csv -e PstI -o calls.csv --hapmap calls.hmp.txt
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --relations pairs.csv --relations-matrix dist.csv
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --ld ld_pairs.csv --ld-keep keep.txt --relations pairs.csv --relations-ld-pruned
+    python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --impute imputed.csv --impute-stats impute_stats.csv
 
 The input is the counter's CSV (samples in rows, tag names Marker_..._0 / Marker_..._1 in the header), or the
 libraries of a key file, which are counted first: every library's barcode rows are folded into one samples x tags
@@ -14,7 +15,8 @@ matrix on the device, and the calls are made from that matrix where it lies -- i
 --counts-out asks for the CSV as well.  -o has writeDiploidGeno's layout with the markers that pass.  --relations
 checks the samples themselves over the markers that pass (tag_relate's table; the calls stay on the device for it).
 --ld, --ld-groups and --ld-keep check those markers against each other (tag_ld's files, from the same calls on the
-device); --relations-ld-pruned then restricts the relations to the LD-pruned markers.
+device); --relations-ld-pruned then restricts the relations to the LD-pruned markers.  --impute fills the holes of the
+passing markers by LD-kNN imputation (tag_impute's file, from the same calls on the device) and writes them beside -o.
 """
 import argparse
 import csv
@@ -52,6 +54,10 @@ def build_parser():
     ap.add_argument("--min-r2", type=float, default=0.8, help="--ld: a pair with at least this r^2 is in LD")
     ap.add_argument("--ld-min-shared", type=int, default=50, help="--ld: ... when at least this many samples are called at both")
     ap.add_argument("--relations-ld-pruned", action="store_true", help="--relations over the markers that pass AND survive LD pruning")
+    ap.add_argument("--impute", metavar="FILE", help="genotype CSV to write as well: the passing markers with their holes filled (see tag_impute)")
+    ap.add_argument("--impute-stats", metavar="FILE", help="--impute: per-marker CSV to write (missing, imputed, no_donor, undecided, neighbours)")
+    from .tag_impute import add_tuning
+    add_tuning(ap.add_argument_group("--impute (its LD shares --ld-min-shared)"), prefix="impute-", min_r2="--impute-min-r2", ld_min_shared=False)
     ap.add_argument("--rule", choices=list(tf.GENO_RULES), default="likelihood",
                     help="likelihood: heterozygous when the rarer allele's reads are too many for errors; presence: when both were seen")
     ap.add_argument("--err", type=float, default=0.01, help="sequencing error rate of the likelihood rule")
@@ -132,7 +138,10 @@ def main(argv=None):
     if args.relations_ld_pruned and not relate:
         raise Exception("--relations-ld-pruned goes with --relations or --relations-matrix.")
     ld = args.relations_ld_pruned or any(x is not None for x in (args.ld, args.ld_groups, args.ld_keep))
-    eng = d_counts = d_calls = relations = ldres = ld_keep = None
+    if args.impute_stats is not None and args.impute is None:
+        raise Exception("--impute-stats goes with --impute.")
+    impute = args.impute is not None
+    eng = d_counts = d_calls = relations = ldres = ld_keep = imputed = None
     if args.counts is not None:
         if args.counts_out is not None:
             raise Exception("--counts-out goes with counting (-b); -i is that file already.")
@@ -162,7 +171,7 @@ def main(argv=None):
         samples, d_counts = count_on_device(eng, keys, sequences, site, args.maxreads)
         counts, backend = d_counts, "gpu"
     try:
-        keep = (relate or ld) and backend == "gpu"       # relations and LD read the calls where the call kernel wrote them
+        keep = (relate or ld or impute) and backend == "gpu"       # relations, LD and imputation read the calls where the call kernel wrote them
         result = tf.call_genotypes(counts, samples, names, backend=backend, keep_device=keep, **params)
         d_calls = result.d_calls
         if d_counts is not None and args.counts_out is not None:
@@ -177,6 +186,18 @@ def main(argv=None):
             relations = tf.sample_relations(d_calls if keep else result.calls, samples,
                                             mask=result.mask & ld_keep if args.relations_ld_pruned else result.mask, max_dist=args.max_dist,
                                             min_shared=args.min_shared, device=args.td_device, backend=backend)
+        if impute:
+            from .tag_impute import tuning
+            imputed = tf.impute_calls(d_calls if keep else result.calls, result.markers, mask=result.mask, device=args.td_device,
+                                      backend=backend, **tuning(args))
+            if keep:                                     # the filled matrix comes to the host once, to be written
+                import numpy as np
+                dev, filled, (S, M) = tf.default_engine(args.td_device), imputed.calls, imputed.calls.shape
+                try:
+                    imputed.calls = np.frombuffer(dev.d2h(filled.ptr, S * M) if filled.ptr else b"", dtype=np.uint8).reshape(S, M)
+                finally:
+                    if filled.ptr:
+                        dev.dev_free(filled.ptr)
     finally:
         if d_counts is not None:
             eng.dev_free(d_counts.ptr)
@@ -198,7 +219,15 @@ def main(argv=None):
     if args.ld_keep is not None:
         from .tag_ld import write_keep
         write_keep(args.ld_keep, ldres, ld_keep)
+    if impute:
+        tf.writeGenoCalls(args.impute, tf.GenoResult(result.markers, result.samples, imputed.calls, result.stats, result.mask,
+                                                     result.columns), passing_only=True)
+        if args.impute_stats is not None:
+            tf.writeImputeStats(args.impute_stats, imputed)
     print(stats_line(result))
+    if impute:
+        from .tag_impute import summary_line
+        print(summary_line(imputed))
     return 0
 
 

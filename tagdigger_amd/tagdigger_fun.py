@@ -1732,6 +1732,210 @@ def writeLDGroups(filename, result, groups=None, keep=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# LD-kNN imputation of the missing calls: the step that fills the holes.  For a missing cell (t, m): the
+# markers most in LD with m (a row of the neighbour table, from marker_ld's edges), the samples most alike over those
+# markers, and their vote.  Over B = the neighbours q at which target t and donor d are both called: ovl = |B|, dist =
+# the sum of |calls[t][q] - calls[d][q]|; a donor called at m with ovl >= min_overlap weighs
+# w = 32768 (2 ovl - dist) // ovl; the first k by (w descending, d ascending) vote with their call at m; the cell becomes
+# g iff V[g] is the only maximum, the total is positive and V[g] 10^6 >= min_conf_ppm total.  Integers only; only the
+# input's calls are read, so no cell depends on another's result.  csrc/impute.hip decides it from the calls where they
+# lie, _impute_host restates it in numpy.  No float takes part anywhere but in the order of the neighbours (LDResult.r2).
+IMPUTE_MAX_SAMPLES = 4096
+IMPUTE_MAX_NBR = 64
+IMPUTE_MAX_K = 32
+IMPUTE_STATS = ("missing", "imputed", "no_donor", "undecided")
+_IMPUTE_HOST_CELLS = 1 << 20    # target-donor pairs of one block of _impute_host at most: three float32 planes of L times this size at a time
+
+
+class ImputeResult:
+    """What impute_calls returns: `.markers`, `.calls` (uint8 [S, M], the filled matrix: imputed cells hold 0 / 1 / 2,
+    every other cell its input byte -- or a DeviceCalls, the caller's to free, when the input was one), `.stats` (uint32
+    [M, 4] by IMPUTE_STATS: missing, imputed, no_donor, undecided), `.neighbours` (int32 [M, l], -1 where there is none),
+    `.ms` (device time), `.imputed` (the cells filled in all), `.params` (backend, l, k, min_overlap, min_conf_ppm)."""
+
+    def __init__(self, markers, calls, stats, neighbours, ms, params):
+        self.markers, self.calls, self.stats, self.neighbours, self.ms, self.params = markers, calls, stats, neighbours, ms, params
+        self.imputed = int(stats[:, 1].sum(dtype="uint64")) if len(stats) else 0
+
+
+def ld_neighbours(result, l=20):
+    """The neighbour table of impute_calls from an LDResult: int32 [M, l]; row m holds the markers joined to m by an edge,
+    ordered by (r2 descending, other marker ascending), the first l of them, then -1."""
+    import numpy as np
+    if isinstance(l, bool) or int(l) != l or not 1 <= l <= IMPUTE_MAX_NBR:
+        raise ValueError("l must be an integer in 1 .. {}".format(IMPUTE_MAX_NBR))
+    l, M = int(l), len(result.markers)
+    table = np.full((M, l), -1, dtype=np.int32)
+    ei, ej = result.edges["i"].astype(np.int64), result.edges["j"].astype(np.int64)
+    src, dst, r2 = np.concatenate([ei, ej]), np.concatenate([ej, ei]), np.concatenate([result.r2, result.r2])
+    order = np.lexsort((dst, -r2, src))            # by marker, then r2 descending, then the other marker
+    src, dst = src[order], dst[order]
+    start = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=M))])
+    rank = np.arange(len(src)) - start[src]        # the place within the marker's run
+    take = rank < l
+    table[src[take], rank[take]] = dst[take]
+    return table
+
+
+def _impute_host(calls, nbr, k, min_overlap, min_conf_ppm):
+    """The rule of DESIGN 4.17 in numpy, over blocks of markers: ovl and dist of every target against every sample as
+    float32 products of the planes over the neighbours (at most 128, exact there), everything after them in int64.  Returns (the filled
+    matrix, stats uint32 [M, 4])."""
+    import numpy as np
+    calls = np.asarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    nbr = np.asarray(nbr, dtype=np.int64)
+    nbr = nbr.reshape(M, nbr.size // M if M else 1)
+    out = calls.copy()
+    stats = np.zeros((M, len(IMPUTE_STATS)), dtype=np.uint32)
+    own = np.ascontiguousarray(np.minimum(calls, 3).T)             # [M, S], codes 0 .. 3
+    gone = own == 3
+    stats[:, 0] = gone.sum(axis=1)
+    has = (nbr >= 0).any(axis=1)
+    stats[~has, 2] = stats[~has, 0]                # an empty row: no target has a donor
+    active = np.nonzero(has & (stats[:, 0] > 0))[0]
+    sample = np.arange(S, dtype=np.int64)
+    block = max(1, _IMPUTE_HOST_CELLS // max(1, S * S))
+    for lo in range(0, len(active), block):
+        ms = active[lo:lo + block]
+        nb = nbr[ms]
+        A = own[np.maximum(nb, 0)]                 # [b, L, S]
+        C = ((A <= 2) & (nb >= 0)[:, :, None]).astype(np.float32)
+        bt, tt = np.nonzero(gone[ms])              # the targets: (marker of the block, sample)
+        Cd, ct = C[bt], C[bt, :, tt][:, None, :]   # [n, L, S] over the donors; the target's own plane [n, 1, L]
+        o = np.rint((ct @ Cd)[:, 0, :]).astype(np.int64)           # [n, S]
+        ds = np.zeros_like(o)
+        for level in (1, 2):                       # the thermometer planes: |x - y| = [x >= 1 != y >= 1] + [x >= 2 != y >= 2]
+            X = C * (A >= level)
+            Xd, xt = X[bt], X[bt, :, tt][:, None, :]
+            ds += np.rint((xt @ Cd + ct @ Xd - 2 * (xt @ Xd))[:, 0, :]).astype(np.int64)
+        w = 32768 * (2 * o - ds) // np.maximum(o, 1)
+        key = np.where((o >= min_overlap) & ~gone[ms][bt], (w << 12) | (4095 - sample), -1)
+        top = -np.sort(-key, axis=1)[:, :k]        # the k largest keys, largest first
+        voter = top >= 0
+        tw = np.where(voter, top >> 12, 0)
+        cls = own[ms][bt[:, None], np.where(voter, 4095 - (top & 4095), 0)]
+        V = np.stack([(tw * (cls == g)).sum(axis=1) for g in (0, 1, 2)], axis=1)
+        total, best = V.sum(axis=1), V.max(axis=1)
+        sure = voter[:, 0] & (total > 0) & ((V == best[:, None]).sum(axis=1) == 1) & (best * 1000000 >= min_conf_ppm * total)
+        out[tt[sure], ms[bt[sure]]] = V.argmax(axis=1)[sure]
+        for col, sel in ((1, sure), (2, ~voter[:, 0]), (3, voter[:, 0] & ~sure)):
+            stats[ms, col] = np.bincount(bt[sel], minlength=len(ms))
+    return out, stats
+
+
+def _impute_params(l, k, min_overlap, min_conf):
+    for name, v, hi in (("l", l, IMPUTE_MAX_NBR), ("k", k, IMPUTE_MAX_K), ("min_overlap", min_overlap, (1 << 32) - 1)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= v <= hi:
+            raise ValueError("{} must be an integer in 1 .. {}".format(name, hi))
+    return int(l), int(k), int(min_overlap), _ppm(min_conf, 0, 1000000, "min_conf")
+
+
+def impute_calls(calls, marknames, ld=None, mask=None, l=20, k=10, min_overlap=4, min_conf=0.6, min_r2=0.5, ld_min_shared=50,
+                 device=0, backend="gpu"):
+    """LD-kNN imputation of the missing genotype calls.
+
+    calls, marknames and mask are marker_ld's: a samples x markers matrix of codes 0, 1, 2 and 3 (missing) -- numpy or
+    lists -- or a DeviceCalls (backend="gpu" only; there any byte above 2 is missing); a marker takes part iff its entry of
+    mask is true (None: all).  ld: the LDResult whose edges choose the neighbours; None runs marker_ld(calls, marknames,
+    mask, min_r2, ld_min_shared) first.  For a missing cell the l markers most in LD with its marker are taken
+    (ld_neighbours); the samples called at the marker are ranked by how alike they are to the cell's sample over those
+    neighbours, among those that share at least min_overlap of them; the k most alike vote with their own call, weighted by
+    likeness, and the cell is filled iff one class wins with at least min_conf of the weight (taken in parts per million).
+    A cell that is not filled keeps its input; a marker that does not take part, or is in LD with nothing, is left as it is.
+    backend="gpu" runs csrc/impute.hip on the calls where they lie; backend="host" is the numpy restatement: the same bytes.
+    At most IMPUTE_MAX_SAMPLES samples.  Returns an ImputeResult; with a DeviceCalls its `.calls` is a DeviceCalls too, and
+    the caller's to free."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    l, k, min_overlap, min_conf_ppm = _impute_params(l, k, min_overlap, min_conf)
+    on_device = isinstance(calls, DeviceCalls)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCalls matrix needs backend='gpu'")
+    marknames = list(marknames)
+    if ld is None:
+        ld = marker_ld(calls, marknames, mask=mask, min_r2=min_r2, min_shared=ld_min_shared, device=device, backend=backend)
+    if not on_device:
+        calls = np.asarray(calls if len(calls) else np.zeros((0, len(marknames)), dtype=np.uint8))
+        if calls.ndim != 2:
+            raise ValueError("the call matrix must have two dimensions (samples x markers)")
+        if calls.dtype.kind not in "iub":
+            raise ValueError("the call matrix must hold the integer codes 0 .. 3, not {}".format(calls.dtype))
+        if calls.size and (int(calls.min()) < 0 or int(calls.max()) > 3):
+            raise ValueError("the call matrix must hold 0, 1, 2 or 3 (missing) only")
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    if len(marknames) != M or len(ld.markers) != M:
+        raise ValueError("marknames and the LD result must name every column of the call matrix")
+    if S > IMPUTE_MAX_SAMPLES:
+        raise ValueError("at most {} samples".format(IMPUTE_MAX_SAMPLES))
+    neighbours = ld_neighbours(ld, l)
+    if mask is not None:                           # (an LD result made under another mask: nobody outside this one takes part)
+        mask = np.asarray(mask)
+        if mask.shape != (M,):
+            raise ValueError("mask must have one entry per marker")
+        mask = mask != 0
+        neighbours[~mask] = -1
+        neighbours[(neighbours >= 0) & ~mask[np.maximum(neighbours, 0)]] = -1
+    if backend == "host":
+        (filled, stats), ms = _impute_host(calls, neighbours, k, min_overlap, min_conf_ppm), 0.0
+    else:
+        res = default_engine(device).impute_knn(calls.ptr or None if on_device else calls, neighbours,
+                                                shape=(S, M) if on_device else None, k=k, min_overlap=min_overlap,
+                                                min_conf_ppm=min_conf_ppm, fetch=not on_device, keep_device=on_device)
+        filled, stats, ms = DeviceCalls(res.d_calls or 0, (S, M)) if on_device else res.calls, res.stats, res.ms
+    return ImputeResult(marknames, filled, stats, neighbours, ms,
+                        dict(backend=backend, l=l, k=k, min_overlap=min_overlap, min_conf_ppm=min_conf_ppm))
+
+
+def impute_hidden_cells(calls, hide_ppm=50000, seed=0, mask=None):
+    """The cells impute_check hides: floor(n hide_ppm / 10^6) of the n called cells (of the markers that take part),
+    drawn without replacement by numpy's default_rng(seed); flat indices into the matrix, ascending."""
+    import numpy as np
+    calls = np.asarray(calls)
+    if isinstance(hide_ppm, bool) or int(hide_ppm) != hide_ppm or not 0 <= hide_ppm <= 1000000:
+        raise ValueError("hide_ppm must be an integer in 0 .. 1000000")
+    called = calls <= 2
+    if mask is not None:
+        called = called & (np.asarray(mask) != 0)[None, :]
+    flat = np.flatnonzero(called)
+    n = len(flat) * int(hide_ppm) // 1000000
+    return np.sort(np.random.default_rng(seed).choice(flat, size=n, replace=False)) if n else flat[:0]
+
+
+def impute_check(calls, marknames, hide_ppm=50000, seed=0, **kw):
+    """How well would impute_calls(calls, marknames, **kw) do here?  Hides impute_hidden_cells(calls, hide_ppm, seed, mask)
+    (sets them missing), imputes the rest's way, and returns the int64 [3, 4] table of the hidden cells: true class (rows)
+    against outcome 0, 1, 2 or left missing (columns).  With ld=None the LD is taken from the matrix with the cells hidden,
+    as it would be in use.  The way to choose l, k, min_overlap and min_conf for one's own data: nothing is promised."""
+    import numpy as np
+    if isinstance(calls, DeviceCalls):
+        raise ValueError("impute_check hides cells of a host matrix")
+    truth = np.ascontiguousarray(np.asarray(calls if len(calls) else np.zeros((0, len(marknames)))), dtype=np.uint8)
+    hidden = impute_hidden_cells(truth, hide_ppm, seed, kw.get("mask"))
+    holed = truth.copy()
+    holed.reshape(-1)[hidden] = GENO_MISSING
+    got = impute_calls(holed, marknames, **kw).calls.reshape(-1)[hidden]
+    table = np.zeros((3, 4), dtype=np.int64)
+    np.add.at(table, (truth.reshape(-1)[hidden], np.minimum(got, 3)), 1)
+    return table
+
+
+IMPUTE_STAT_COLUMNS = ("marker",) + IMPUTE_STATS + ("neighbours",)
+
+
+def writeImputeStats(filename, result):
+    """One row per marker: marker, missing, imputed, no_donor, undecided and neighbours (the entries of its row of the
+    table); CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(IMPUTE_STAT_COLUMNS)
+        for m, name in enumerate(result.markers):
+            out.writerow([name] + [int(x) for x in result.stats[m]] + [int((result.neighbours[m] >= 0).sum())])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Tag Manager (reference tagdigger_fun.py:1389-1905 and the prompts of :936-1028, :1182-1200).
 #
 # Every function keeps the reference's signature, return values, printed lines, files and exceptions.  Those with a
