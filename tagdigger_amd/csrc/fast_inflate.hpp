@@ -344,6 +344,15 @@ class FastInflate {
         }
         return true;
     }
+    // zlib's rule for the codes of a dynamic block (inftrees.c): an incomplete set of lengths is an error unless its codes --
+    // one, or none -- have one bit
+    static bool incomplete_allowed(const uint8_t *lens, int nsym) {
+        for (int s = 0; s < nsym; s++) if (lens[s] > 1) return false;
+        return true;
+    }
+    static bool dynamic_codes_allowed(const uint8_t *ll, int nlit, bool lit_complete, const uint8_t *dl, int ndist, bool dist_complete) {
+        return (lit_complete || incomplete_allowed(ll, nlit)) && (dist_complete || incomplete_allowed(dl, ndist));
+    }
     // both tables of a block from its code lengths; false: over-subscribed.  pair_literals: see F_LIT2
     static bool build_block_tables(uint32_t *lit, uint32_t *dist, const uint8_t *ll, int nlit, const uint8_t *dl, int ndist,
                                    bool pair_literals, bool *lit_complete = nullptr, bool *dist_complete = nullptr) {
@@ -416,8 +425,10 @@ class FastInflate {
         refill();
         for (uint32_t i = 0; i < nclen; i++) { if (bitcnt_ < 8) refill(); cl[order[i]] = (uint8_t)bits(3); }
         uint32_t cltab[128 + 19 * 1];
-        if (!build(cltab, 7, cl, 19, F_SUB, [&](int s, int l) -> uint32_t { return ((uint32_t)s << 16) | (uint32_t)l; }))
+        bool cl_complete = false;
+        if (!build(cltab, 7, cl, 19, F_SUB, [&](int s, int l) -> uint32_t { return ((uint32_t)s << 16) | (uint32_t)l; }, &cl_complete))
             return fail("over-subscribed code-length code");
+        if (!cl_complete) return fail("incomplete code-length code");
         uint8_t lens[286 + 30];
         uint32_t i = 0;
         while (i < nlit + ndist) {
@@ -436,7 +447,10 @@ class FastInflate {
             while (rep--) lens[i++] = (uint8_t)val;
         }
         if (lens[256] == 0) return fail("no end-of-block code");
-        if (!build_tables(lens, (int)nlit, lens + nlit, (int)ndist)) return false;
+        bool lit_complete = false, dist_complete = false;
+        if (!build_block_tables(lit_, dist_, lens, (int)nlit, lens + nlit, (int)ndist, true, &lit_complete, &dist_complete))
+            return fail("over-subscribed Huffman code");
+        if (!dynamic_codes_allowed(lens, (int)nlit, lit_complete, lens + nlit, (int)ndist, dist_complete)) return fail("incomplete Huffman code");
         state_ = S_HUFF;
         return true;
     }

@@ -83,13 +83,14 @@ TDI_FN uint32_t rev(uint32_t code, uint32_t len) {            // the low `len` b
 
 // Canonical Huffman tables from `n` code lengths: primary[1 << bits] (entry = symbol << 4 | length, E_SLOW for the
 // prefixes of longer codes, 0 = no code), sym[] = symbols in canonical order, cnt[len] = codes of that length.
-// Returns false for an over-subscribed set (incomplete sets are allowed, as zlib allows a single distance code).
-TDI_FN bool build(const uint8_t *lens, uint32_t n, uint16_t *primary, uint32_t ts, uint32_t bits, uint16_t *sym, uint16_t *cnt) {
+// Returns what is left of the code space: negative for an over-subscribed set, 0 for a complete one (an incomplete set
+// builds: the fixed block's distance code is one, and zlib allows a single code of one bit -- see one_bit_only).
+TDI_FN int32_t build(const uint8_t *lens, uint32_t n, uint16_t *primary, uint32_t ts, uint32_t bits, uint16_t *sym, uint16_t *cnt) {
     for (uint32_t l = 0; l < 16; l++) cnt[l] = 0;
     for (uint32_t i = 0; i < n; i++) cnt[lens[i]]++;
     cnt[0] = 0;
     int32_t left = 1;
-    for (uint32_t l = 1; l < 16; l++) { left <<= 1; left -= (int32_t)cnt[l]; if (left < 0) return false; }
+    for (uint32_t l = 1; l < 16; l++) { left <<= 1; left -= (int32_t)cnt[l]; if (left < 0) return -1; }
     uint32_t offs[16], next[16];
     offs[1] = 0; next[1] = 0;
     for (uint32_t l = 1; l < 15; l++) { offs[l + 1] = offs[l] + cnt[l]; next[l + 1] = (next[l] + cnt[l]) << 1; }
@@ -106,7 +107,14 @@ TDI_FN bool build(const uint8_t *lens, uint32_t n, uint16_t *primary, uint32_t t
             primary[rev(code >> (l - bits), bits) * ts] = E_SLOW;
         }
     }
-    return true;
+    return left;
+}
+// zlib's rule for the codes of a dynamic block (inftrees.c): an incomplete set of lengths is an error unless its codes -- one,
+// or none -- have one bit
+TDI_FN bool one_bit_only(const uint16_t *cnt) {
+    uint32_t longer = 0;
+    for (uint32_t l = 2; l < 16; l++) longer |= cnt[l];
+    return longer == 0;
 }
 // a symbol whose code is longer than the primary index: bit by bit against the canonical arrays
 TDI_FN int32_t slow_symbol(Stream &s, const uint16_t *sym, const uint16_t *cnt) {
@@ -169,7 +177,7 @@ TDI_FN void header(Stream &s) {
         for (uint32_t i = 0; i < ncl; i++) { refill(s); cl[order[i]] = (uint8_t)take(s, 3); }
         // the code-length code: a 7-bit table in the distance table's place (built afterwards)
         uint16_t csym[19], ccnt[16];
-        if (!build(cl, 19, dtab, s.tstride, 7, csym, ccnt)) { s.state = ST_ERROR; s.err = ERR_LENGTHS; return; }
+        if (build(cl, 19, dtab, s.tstride, 7, csym, ccnt) != 0) { s.state = ST_ERROR; s.err = ERR_LENGTHS; return; }   // (zlib: must be complete)
         uint32_t i = 0;
         while (i < nlit + ndist) {
             refill(s);
@@ -188,7 +196,8 @@ TDI_FN void header(Stream &s) {
         for (uint32_t k = ndist; k-- > 0;) lens[288 + k] = lens[nlit + k];           // (backwards: the ranges overlap)
         for (uint32_t k = nlit; k < 288; k++) lens[k] = 0;
     }
-    if (!build(lens, nlit, ltab, s.tstride, LBITS, lsym, lcnt) || !build(lens + 288, ndist, dtab, s.tstride, DBITS, dsym, dcnt)) {
+    const int32_t rl = build(lens, nlit, ltab, s.tstride, LBITS, lsym, lcnt), rd = build(lens + 288, ndist, dtab, s.tstride, DBITS, dsym, dcnt);
+    if (rl < 0 || rd < 0 || (type == 2 && ((rl > 0 && !one_bit_only(lcnt)) || (rd > 0 && !one_bit_only(dcnt))))) {
         s.state = ST_ERROR; s.err = ERR_LENGTHS; return;
     }
     s.state = ST_SYMBOL;

@@ -670,7 +670,7 @@ class ParInflate {
         if (!FI::build(cltab, 7, cl, 19, FI::F_SUB, [&](int s, int l) -> uint32_t { return ((uint32_t)s << 16) | (uint32_t)l; }, &complete)) {
             err = "over-subscribed code-length code"; return H_BAD;
         }
-        if (strict && !complete) return H_BAD;
+        if (!complete) { err = "incomplete code-length code"; return H_BAD; }
         uint8_t lens[286 + 30];
         uint32_t i = 0;
         while (i < nlit + ndist) {
@@ -695,9 +695,11 @@ class ParInflate {
             for (uint32_t k = 0; k < ndist; k++) { dsum += lens[nlit + k] ? 32768u >> lens[nlit + k] : 0; used += lens[nlit + k] != 0; }
             if (lsum != 32768u || !(dsum == 32768u || used <= 1)) return H_BAD;
         }
-        if (!FI::build_block_tables(t.lit, t.dist, lens, (int)nlit, lens + nlit, (int)ndist, true)) {
+        bool lit_complete = false, dist_complete = false;
+        if (!FI::build_block_tables(t.lit, t.dist, lens, (int)nlit, lens + nlit, (int)ndist, true, &lit_complete, &dist_complete)) {
             err = "over-subscribed Huffman code"; return H_BAD;
         }
+        if (!FI::dynamic_codes_allowed(lens, (int)nlit, lit_complete, lens + nlit, (int)ndist, dist_complete)) { err = "incomplete Huffman code"; return H_BAD; }
         return H_DYNAMIC;
     }
 

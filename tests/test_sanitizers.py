@@ -73,6 +73,20 @@ def _streams():
 GOOD, BAD = _streams()
 
 
+def _deflate_edges():
+    """A handful of tests/deflate_cases.py's streams (what no zlib encoder writes: long codes in 48-bit tokens, empty blocks at
+    every alignment, false block starts inside stored blocks; refused ones whose trailer is right for a decoder without the
+    check)."""
+    import deflate_cases as dc
+    cases = dc.catalogue()
+    for name in ("long-codes-max-tokens", "empty-blocks-alignments", "decoy-in-stored", "dependent-copies", "repeat-across-lit-dist",
+                 "toofar-zero-trailer", "incomplete-litlen", "dist-too-far"):
+        (GOOD if cases[name].want is not None else BAD)["edge-" + name] = cases[name].member()
+
+
+_deflate_edges()
+
+
 @pytest.mark.parametrize("chunk", ["3000", "65536"])
 @pytest.mark.parametrize("san", ["tsan", "asan"])
 @pytest.mark.parametrize("name", sorted(GOOD) + sorted(BAD))
