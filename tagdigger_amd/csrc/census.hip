@@ -29,24 +29,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tagdig.h"
 #define TD_INST_ONLY                    // (k_scan_tiles is defined in tagdig.hip's translation unit)
 #include "kernels.hpp"
 #include "piece_sink.hpp"
-
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-__attribute__((visibility("hidden"))) void **td_handle_census(td_handle *h);
-__attribute__((visibility("hidden"))) void *td_handle_work_stream(const td_handle *h);
-__attribute__((visibility("hidden"))) int td_handle_num_cu(const td_handle *h);
-__attribute__((visibility("hidden"))) int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
-                                                         uint8_t **blob_out, uint32_t *bytes, uint32_t *off_bmeta, uint32_t *off_bdir);
-__attribute__((visibility("hidden"))) int td_line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, void *s, const uint64_t **prefix,
-                                                         unsigned long long *d_total);
-__attribute__((visibility("hidden"))) int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink);
-__attribute__((visibility("hidden"))) void td_census_release(td_handle *h);
-}
+#include "td_internal.hpp"
 
 namespace tdc {
 using namespace tdk;
@@ -362,13 +348,6 @@ __global__ __launch_bounds__(256) void k_census_compact(const unsigned long long
 // ============================================================================ host side
 namespace {
 
-#define CSCHK(call)                                                                                          \
-    do {                                                                                                     \
-        hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess)                                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str());  \
-    } while (0)
-
 constexpr uint64_t CENSUS_MIN_SLOTS = 1024, CENSUS_DEFAULT_SLOTS = 1ull << 22, CENSUS_MAX_SLOTS = 1ull << 32;
 constexpr size_t CENSUS_LDS_INDEX = 40 * 1024;            // the barcode index's share of a workgroup's LDS
 
@@ -393,9 +372,9 @@ struct Census {
 Census *census_of(td_handle *h) { return h ? (Census *)*td_handle_census(h) : nullptr; }
 
 int census_zero(Census *c, hipStream_t s) {
-    CSCHK(hipMemsetAsync(c->d_table, 0, c->slots * c->slot_words() * 8, s));
-    CSCHK(hipMemsetAsync(c->d_cs, 0, tdc::CS_NWORDS * 8, s));
-    CSCHK(hipStreamSynchronize(s));
+    TD_HIPCHK(hipMemsetAsync(c->d_table, 0, c->slots * c->slot_words() * 8, s));
+    TD_HIPCHK(hipMemsetAsync(c->d_cs, 0, tdc::CS_NWORDS * 8, s));
+    TD_HIPCHK(hipStreamSynchronize(s));
     c->used = false;
     return TD_OK;
 }
@@ -419,7 +398,7 @@ int census_launch(Census *c, const void *d_fastq, uint64_t nbytes, uint64_t firs
     p.cursor_in = cursor_in; p.cursor_out = cursor_out; p.combine = (uint32_t)c->combine;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(p.ntiles, (uint64_t)td_handle_num_cu(c->h) * 8);
     hipLaunchKernelGGL(tdc::k_census, dim3(grid), dim3(tdk::BLOCK), c->bblob_bytes, stream, p);
-    CSCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     return TD_OK;
 }
 
@@ -438,8 +417,8 @@ int census_check(Census *c, const unsigned long long *cs) {
 
 int census_sync_stats(Census *c, unsigned long long cs[tdc::CS_NWORDS]) {
     if (c->dead) return td_fail_internal(c->dead, c->dead_msg.c_str());
-    CSCHK(hipDeviceSynchronize());
-    CSCHK(hipMemcpy(cs, c->d_cs, tdc::CS_NWORDS * 8, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipMemcpy(cs, c->d_cs, tdc::CS_NWORDS * 8, hipMemcpyDeviceToHost));
     return census_check(c, cs);
 }
 
@@ -469,8 +448,8 @@ int td_census_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, 
     if (slots == 0) slots = CENSUS_DEFAULT_SLOTS;
     if (slots < CENSUS_MIN_SLOTS || slots > CENSUS_MAX_SLOTS || (slots & (slots - 1)))
         return td_fail_internal(TD_E_ARG, "slots must be a power of two, 1024 .. 2^32 (0: the default, 2^22)");
-    CSCHK(hipSetDevice(td_handle_device(h)));
-    CSCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipDeviceSynchronize());
     td_census_release(h);
     uint8_t *blob = nullptr;
     uint32_t bytes = 0, off_bmeta = 0, off_bdir = 0;
@@ -503,7 +482,7 @@ int td_census_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, 
 int td_census_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream) {
     Census *c = census_of(h);
     if (!c) return td_fail_internal(h ? TD_E_STATE : TD_E_ARG, h ? "td_census_begin has not been called" : "handle is NULL");
-    CSCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     return census_launch(c, d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
 }
 
@@ -526,7 +505,7 @@ int td_census_file(td_handle *h, const char *path, uint64_t max_reads) {
 int td_census_stats(td_handle *h, uint64_t out[8]) {
     Census *c = census_of(h);
     if (!c || !out) return td_fail_internal(h && out ? TD_E_STATE : TD_E_ARG, h && out ? "td_census_begin has not been called" : "NULL argument");
-    CSCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     unsigned long long cs[tdc::CS_NWORDS];
     const int rc = census_sync_stats(c, cs); if (rc) return rc;
     out[TD_CENSUS_READS] = cs[tdc::CS_READS]; out[TD_CENSUS_BARCUT] = cs[tdc::CS_BARCUT];
@@ -541,7 +520,7 @@ int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *
     Census *c = census_of(h);
     if (!c || !n_out) return td_fail_internal(h && n_out ? TD_E_STATE : TD_E_ARG, h && n_out ? "td_census_begin has not been called" : "NULL argument");
     if (capacity && (!seqs_out || !counts_out)) return td_fail_internal(TD_E_ARG, "NULL argument");
-    CSCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     *n_out = 0;
     unsigned long long cs[tdc::CS_NWORDS];
     int rc = census_sync_stats(c, cs); if (rc) return rc;
@@ -549,26 +528,26 @@ int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *
     const uint32_t two = c->taglen > 32 ? 1u : 0u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((c->slots + 255) / 256, (uint64_t)td_handle_num_cu(h) * 8);
     unsigned long long *d_n = nullptr, *d_out = nullptr;
-    CSCHK(hipMalloc((void **)&d_n, 8));
+    TD_HIPCHK(hipMalloc((void **)&d_n, 8));
     struct Free { unsigned long long *&a, *&b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } guard{d_n, d_out};
     unsigned long long n = cs[tdc::CS_DISTINCT];
     // how many there are: a pass that keeps nothing -- run when only the number is asked for, or when room for every
     // distinct window (the bound that needs no pass) would be more than 1 GiB
     const bool count_first = min_count > 1 && (capacity == 0 || n * 24 > (1ull << 30));
     if (count_first) {
-        CSCHK(hipMemset(d_n, 0, 8));
+        TD_HIPCHK(hipMemset(d_n, 0, 8));
         hipLaunchKernelGGL(tdc::k_census_compact, dim3(grid), dim3(256), 0, 0, c->d_table, c->slots, two, (unsigned long long)min_count,
                            (unsigned long long *)nullptr, 0ull, d_n);
-        CSCHK(hipGetLastError());
-        CSCHK(hipMemcpy(&n, d_n, 8, hipMemcpyDeviceToHost));
+        TD_HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipMemcpy(&n, d_n, 8, hipMemcpyDeviceToHost));
     }
     if (n == 0 || capacity == 0) { *n_out = n; return TD_OK; }
-    CSCHK(hipMalloc((void **)&d_out, n * 24));
-    CSCHK(hipMemset(d_n, 0, 8));
+    TD_HIPCHK(hipMalloc((void **)&d_out, n * 24));
+    TD_HIPCHK(hipMemset(d_n, 0, 8));
     hipLaunchKernelGGL(tdc::k_census_compact, dim3(grid), dim3(256), 0, 0, c->d_table, c->slots, two, (unsigned long long)min_count, d_out, n, d_n);
-    CSCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     unsigned long long n2 = 0;
-    CSCHK(hipMemcpy(&n2, d_n, 8, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(&n2, d_n, 8, hipMemcpyDeviceToHost));
     if (count_first || min_count <= 1 ? n2 != n : n2 > n)
         return td_fail_internal(TD_E_INTERNAL, "census compaction found another number of entries than the table holds");
     n = n2;
@@ -576,7 +555,7 @@ int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *
     if (n == 0) return TD_OK;
     struct Ent { uint64_t hi, lo, count; };
     std::vector<Ent> ents(n);
-    CSCHK(hipMemcpy(ents.data(), d_out, n * 24, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(ents.data(), d_out, n * 24, hipMemcpyDeviceToHost));
     for (Ent &e : ents) { e.hi = acgt_order(e.hi); e.lo = acgt_order(e.lo); }
     // count descending, then sequence ascending (A < C < G < T)
     std::sort(ents.begin(), ents.end(), [](const Ent &a, const Ent &b) {
@@ -599,8 +578,8 @@ int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *
 
 int td_census_end(td_handle *h) {
     if (!h) return td_fail_internal(TD_E_ARG, "handle is NULL");
-    CSCHK(hipSetDevice(td_handle_device(h)));
-    CSCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipDeviceSynchronize());
     td_census_release(h);
     return TD_OK;
 }

@@ -25,22 +25,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tagdig.h"
-
-// tagdig.hip (not exported): the library's error slot and the handle's device
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-}
+#include "td_internal.hpp"
 
 namespace {
-
-#define FRCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 constexpr int FR_THREADS = 256;
 constexpr int FR_BPT = 128;                      // bytes per thread: eight 16-byte loads
@@ -483,17 +470,6 @@ __global__ __launch_bounds__(256) void k_frag_gather(const uint8_t *seq, const t
     }
 }
 
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-template <typename T> struct FrBuf {
-    T *p = nullptr;
-    ~FrBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
 }  // namespace
 
 extern "C" int td_fasta_frame_device(td_handle *h, const void *d_text, uint64_t nbytes, void *d_out, uint64_t *n_out,
@@ -504,27 +480,26 @@ extern "C" int td_fasta_frame_device(td_handle *h, const void *d_text, uint64_t 
     *n_out = 0; *n_rec = 0; *nonascii = 0;
     if (ms) *ms = 0;
     if (!nbytes) return TD_OK;
-    FRCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     const uint64_t ntiles = (nbytes + FR_TILE - 1) / FR_TILE;
     if (ntiles > 0x7fffffffull) return td_fail_internal(TD_E_LIMIT, "genome file too large for one launch");
-    FrBuf<TileSum> sums;
-    FrBuf<TileOut> outs;
-    FrBuf<unsigned long long> tot;   // [0] kept bytes, [1] header lines, [2] flags
-    FRCHK(sums.alloc(ntiles));
-    FRCHK(outs.alloc(ntiles));
-    FRCHK(tot.alloc(4));
-    FRCHK(hipMemset(tot.p, 0, 4 * sizeof(unsigned long long)));
-    EventPair ev;
-    FRCHK(hipEventCreate(&ev.a));
-    FRCHK(hipEventCreate(&ev.b));
+    tdi::DevBuf<TileSum> sums;
+    tdi::DevBuf<TileOut> outs;
+    tdi::DevBuf<unsigned long long> tot;   // [0] kept bytes, [1] header lines, [2] flags
+    TD_HIPCHK(sums.alloc(ntiles));
+    TD_HIPCHK(outs.alloc(ntiles));
+    TD_HIPCHK(tot.alloc(4));
+    TD_HIPCHK(hipMemset(tot.p, 0, 4 * sizeof(unsigned long long)));
+    tdi::Events<2> ev;
+    TD_HIPCHK(ev.create());
     int *flags = (int *)(tot.p + 2);
-    FRCHK(hipEventRecord(ev.a, 0));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     hipLaunchKernelGGL(k_fasta_summary, dim3((uint32_t)ntiles), dim3(FR_THREADS), 0, 0, (const uint8_t *)d_text, nbytes, sums.p, flags);
-    FRCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_fasta_scan, dim3(1), dim3(FR_SCAN_THREADS), 0, 0, sums.p, outs.p, ntiles, tot.p);
-    FRCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     unsigned long long th[4];
-    FRCHK(hipMemcpy(th, tot.p, sizeof th, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(th, tot.p, sizeof th, hipMemcpyDeviceToHost));
     *n_rec = th[1];
     if (*(const int *)&th[2] & 1) {      // a byte >= 0x80: the caller reads this file on the host
         *nonascii = 1;
@@ -533,22 +508,22 @@ extern "C" int td_fasta_frame_device(td_handle *h, const void *d_text, uint64_t 
     if (th[0] > nbytes) return td_fail_internal(TD_E_INTERNAL, "k_fasta_scan: more kept bytes than input");
     if (th[1] > rec_cap) return td_fail_internal(TD_E_LIMIT, ("record table holds " + std::to_string(rec_cap) + " rows, the file has " +
                                                              std::to_string(th[1]) + " header lines").c_str());
-    FrBuf<unsigned long long> rec;
-    FRCHK(rec.alloc(3 * th[1]));
+    tdi::DevBuf<unsigned long long> rec;
+    TD_HIPCHK(rec.alloc(3 * th[1]));
     hipLaunchKernelGGL(k_fasta_emit, dim3((uint32_t)ntiles), dim3(FR_THREADS), 0, 0, (const uint8_t *)d_text, nbytes, outs.p,
                        flags, (uint8_t *)d_out, rec.p, (uint64_t)th[1]);
-    FRCHK(hipGetLastError());
-    FRCHK(hipEventRecord(ev.b, 0));
-    FRCHK(hipEventSynchronize(ev.b));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
     if (ms) {
         float f = 0;
-        FRCHK(hipEventElapsedTime(&f, ev.a, ev.b));
+        TD_HIPCHK(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
         *ms = f;
     }
-    FRCHK(hipMemcpy(th, tot.p, sizeof th, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(th, tot.p, sizeof th, hipMemcpyDeviceToHost));
     if (*(const int *)&th[2] & 2) return td_fail_internal(TD_E_INTERNAL, "k_fasta_emit: header row past the table");
     if (*(const int *)&th[2] & 4) return td_fail_internal(TD_E_INTERNAL, "k_fasta_emit: kept bytes past the input's size");
-    if (th[1]) FRCHK(hipMemcpy(rec_out, rec.p, 3 * th[1] * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (th[1]) TD_HIPCHK(hipMemcpy(rec_out, rec.p, 3 * th[1] * sizeof(uint64_t), hipMemcpyDeviceToHost));
     *n_out = th[0];
     return TD_OK;
 }
@@ -586,31 +561,30 @@ extern "C" int td_frag_search_device(td_handle *h, const void *d_seq, uint64_t s
     if (rc) return rc;
     if ((rc = frag_check_jobs(jobs, njobs, seq_bytes))) return rc;
     if (!njobs) return TD_OK;
-    FRCHK(hipSetDevice(td_handle_device(h)));
-    FrBuf<td_frag_job> dj;
-    FrBuf<int4> dout;
-    FrBuf<FragSites> dfs;
-    FRCHK(dj.alloc(njobs));
-    FRCHK(dout.alloc(njobs));
-    FRCHK(dfs.alloc(1));
-    FRCHK(hipMemcpy(dfs.p, &fs, sizeof fs, hipMemcpyHostToDevice));
-    FRCHK(hipMemcpy(dj.p, jobs, njobs * sizeof(td_frag_job), hipMemcpyHostToDevice));
-    EventPair ev;
-    FRCHK(hipEventCreate(&ev.a));
-    FRCHK(hipEventCreate(&ev.b));
-    FRCHK(hipEventRecord(ev.a, 0));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    tdi::DevBuf<td_frag_job> dj;
+    tdi::DevBuf<int4> dout;
+    tdi::DevBuf<FragSites> dfs;
+    TD_HIPCHK(dj.alloc(njobs));
+    TD_HIPCHK(dout.alloc(njobs));
+    TD_HIPCHK(dfs.alloc(1));
+    TD_HIPCHK(hipMemcpy(dfs.p, &fs, sizeof fs, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(dj.p, jobs, njobs * sizeof(td_frag_job), hipMemcpyHostToDevice));
+    tdi::Events<2> ev;
+    TD_HIPCHK(ev.create());
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     const uint64_t grid = (njobs + FS_WAVES - 1) / FS_WAVES;
     if (grid > 0x7fffffffull) return td_fail_internal(TD_E_LIMIT, "too many jobs for one launch");
     hipLaunchKernelGGL(k_frag_search, dim3((uint32_t)grid), dim3(FS_WAVES * 64), 0, 0, (const uint8_t *)d_seq, dj.p, njobs, dfs.p, dout.p);
-    FRCHK(hipGetLastError());
-    FRCHK(hipEventRecord(ev.b, 0));
-    FRCHK(hipEventSynchronize(ev.b));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
     if (ms) {
         float f = 0;
-        FRCHK(hipEventElapsedTime(&f, ev.a, ev.b));
+        TD_HIPCHK(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
         *ms = f;
     }
-    FRCHK(hipMemcpy(out, dout.p, njobs * sizeof(int4), hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(out, dout.p, njobs * sizeof(int4), hipMemcpyDeviceToHost));
     return TD_OK;
 }
 
@@ -631,34 +605,33 @@ extern "C" int td_frag_gather_device(td_handle *h, const void *d_seq, uint64_t s
     if (total > out_cap) return td_fail_internal(TD_E_LIMIT, "output buffer too small");
     if (!total) return TD_OK;
     if (!out) return td_fail_internal(TD_E_ARG, "NULL argument");
-    FRCHK(hipSetDevice(td_handle_device(h)));
-    FrBuf<td_frag_job> dj;
-    FrBuf<int32_t> dsz;
-    FrBuf<unsigned long long> doff;
-    FrBuf<uint8_t> dout;
-    FRCHK(dj.alloc(njobs));
-    FRCHK(dsz.alloc(njobs));
-    FRCHK(doff.alloc(njobs));
-    FRCHK(dout.alloc(total));
-    FRCHK(hipMemcpy(dj.p, jobs, njobs * sizeof(td_frag_job), hipMemcpyHostToDevice));
-    FRCHK(hipMemcpy(dsz.p, sizes, njobs * sizeof(int32_t), hipMemcpyHostToDevice));
-    FRCHK(hipMemcpy(doff.p, offs.data(), njobs * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    EventPair ev;
-    FRCHK(hipEventCreate(&ev.a));
-    FRCHK(hipEventCreate(&ev.b));
-    FRCHK(hipEventRecord(ev.a, 0));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    tdi::DevBuf<td_frag_job> dj;
+    tdi::DevBuf<int32_t> dsz;
+    tdi::DevBuf<unsigned long long> doff;
+    tdi::DevBuf<uint8_t> dout;
+    TD_HIPCHK(dj.alloc(njobs));
+    TD_HIPCHK(dsz.alloc(njobs));
+    TD_HIPCHK(doff.alloc(njobs));
+    TD_HIPCHK(dout.alloc(total));
+    TD_HIPCHK(hipMemcpy(dj.p, jobs, njobs * sizeof(td_frag_job), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(dsz.p, sizes, njobs * sizeof(int32_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(doff.p, offs.data(), njobs * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    tdi::Events<2> ev;
+    TD_HIPCHK(ev.create());
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     const uint64_t grid = (njobs + 3) / 4;
     if (grid > 0x7fffffffull) return td_fail_internal(TD_E_LIMIT, "too many fragments for one launch");
     hipLaunchKernelGGL(k_frag_gather, dim3((uint32_t)grid), dim3(256), 0, 0, (const uint8_t *)d_seq, dj.p, dsz.p, doff.p, njobs, dout.p);
-    FRCHK(hipGetLastError());
-    FRCHK(hipEventRecord(ev.b, 0));
-    FRCHK(hipEventSynchronize(ev.b));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
     if (ms) {
         float f = 0;
-        FRCHK(hipEventElapsedTime(&f, ev.a, ev.b));
+        TD_HIPCHK(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
         *ms = f;
     }
-    FRCHK(hipMemcpy(out, dout.p, total, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(out, dout.p, total, hipMemcpyDeviceToHost));
     *n_out = total;
     return TD_OK;
 }

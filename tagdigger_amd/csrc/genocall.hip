@@ -25,24 +25,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tagdig.h"
-
-// tagdig.hip (not exported): the error slot, the handle's device, waiting for the handle's own streams
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-__attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h);
-}
+#include "td_internal.hpp"
 
 namespace {
-
-#define GCCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 constexpr int GC_TILE = 256;                       // markers of a workgroup = its threads
 constexpr uint32_t GC_CHUNK = TD_GENO_CHUNK;       // sample rows of a workgroup
@@ -50,18 +35,6 @@ constexpr uint32_t GC_TABLE = TD_GENO_TABLE;       // entries of het_min
 constexpr uint64_t GC_SCALE = GC_TABLE - 1;        // depths above this are scaled down to it
 constexpr uint32_t GC_ROWS = 4;                    // sample rows whose loads a thread has in flight at once
 static_assert(GC_CHUNK % GC_ROWS == 0, "a chunk is walked GC_ROWS rows at a time");
-
-template <typename T> struct GcBuf {
-    T *p = nullptr;
-    ~GcBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
-struct GcEvents {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~GcEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 // the code of one cell; s_het: the table in LDS
 __device__ __forceinline__ uint32_t gc_code(uint32_t a, uint32_t b, uint32_t rule, uint64_t min_depth, const uint16_t *s_het) {
@@ -202,46 +175,46 @@ extern "C" int td_geno_call(td_handle *h, const void *d_counts, uint32_t S, uint
     if (chunks > 65535u) return td_fail_internal(TD_E_LIMIT, "more samples than one launch takes (65 535 chunks)");
     int rc = td_handle_wait_work(h);
     if (rc) return rc;
-    GCCHK(hipSetDevice(td_handle_device(h)));
-    GcEvents ev;
-    for (auto &e : ev.e) GCCHK(hipEventCreate(&e));
-    GcBuf<uint32_t> di, ncode;
-    GcBuf<uint16_t> dhet;
-    GcBuf<uint8_t> calls, pass;
-    GcBuf<uint64_t> stats;
-    GcBuf<unsigned long long> acc;                 // depth0[M] | depth1[M] | passed
-    GCCHK(di.alloc(2ull * M));
-    GCCHK(dhet.alloc(GC_TABLE));
-    GCCHK(ncode.alloc(3ull * M));
-    GCCHK(acc.alloc(2ull * M + 1));
-    GCCHK(calls.alloc((uint64_t)S * M));
-    GCCHK(pass.alloc(M));
-    GCCHK(stats.alloc((uint64_t)M * TD_GENO_NSTATS));
-    GCCHK(hipMemcpy(di.p, i0, (uint64_t)M * 4, hipMemcpyHostToDevice));
-    GCCHK(hipMemcpy(di.p + M, i1, (uint64_t)M * 4, hipMemcpyHostToDevice));
-    GCCHK(hipMemcpy(dhet.p, het_min, GC_TABLE * sizeof(uint16_t), hipMemcpyHostToDevice));
-    GCCHK(hipMemset(ncode.p, 0, 3ull * M * 4));
-    GCCHK(hipMemset(acc.p, 0, (2ull * M + 1) * 8));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    tdi::Events<2> ev;
+    TD_HIPCHK(ev.create());
+    tdi::DevBuf<uint32_t> di, ncode;
+    tdi::DevBuf<uint16_t> dhet;
+    tdi::DevBuf<uint8_t> calls, pass;
+    tdi::DevBuf<uint64_t> stats;
+    tdi::DevBuf<unsigned long long> acc;                 // depth0[M] | depth1[M] | passed
+    TD_HIPCHK(di.alloc(2ull * M));
+    TD_HIPCHK(dhet.alloc(GC_TABLE));
+    TD_HIPCHK(ncode.alloc(3ull * M));
+    TD_HIPCHK(acc.alloc(2ull * M + 1));
+    TD_HIPCHK(calls.alloc((uint64_t)S * M));
+    TD_HIPCHK(pass.alloc(M));
+    TD_HIPCHK(stats.alloc((uint64_t)M * TD_GENO_NSTATS));
+    TD_HIPCHK(hipMemcpy(di.p, i0, (uint64_t)M * 4, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(di.p + M, i1, (uint64_t)M * 4, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(dhet.p, het_min, GC_TABLE * sizeof(uint16_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemset(ncode.p, 0, 3ull * M * 4));
+    TD_HIPCHK(hipMemset(acc.p, 0, (2ull * M + 1) * 8));
     const uint32_t gx = (M + GC_TILE - 1) / GC_TILE;
-    GCCHK(hipEventRecord(ev.e[0], 0));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     hipLaunchKernelGGL(k_gc_call, dim3(gx, (uint32_t)chunks), dim3(GC_TILE), 0, 0, (const uint32_t *)d_counts, S, T, M, di.p,
                        di.p + M, dhet.p, p->rule, p->min_depth, calls.p, ncode.p, acc.p);
-    GCCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_gc_filter, dim3((M + 255) / 256), dim3(256), 0, 0, ncode.p, acc.p, S, M, p->min_call_ppm, p->min_maf_ppm,
                        p->max_het_ppm, stats.p, pass.p, acc.p + 2ull * M);
-    GCCHK(hipGetLastError());
-    GCCHK(hipEventRecord(ev.e[1], 0));
-    GCCHK(hipEventSynchronize(ev.e[1]));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
     if (ms) {
         float f = 0;
-        GCCHK(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
+        TD_HIPCHK(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
         *ms = f;
     }
     unsigned long long passed = 0;
-    GCCHK(hipMemcpy(&passed, acc.p + 2ull * M, sizeof passed, hipMemcpyDeviceToHost));
-    GCCHK(hipMemcpy(stats_out, stats.p, (uint64_t)M * TD_GENO_NSTATS * 8, hipMemcpyDeviceToHost));
-    GCCHK(hipMemcpy(pass_out, pass.p, M, hipMemcpyDeviceToHost));
-    if (calls_out) GCCHK(hipMemcpy(calls_out, calls.p, (uint64_t)S * M, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(&passed, acc.p + 2ull * M, sizeof passed, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(stats_out, stats.p, (uint64_t)M * TD_GENO_NSTATS * 8, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(pass_out, pass.p, M, hipMemcpyDeviceToHost));
+    if (calls_out) TD_HIPCHK(hipMemcpy(calls_out, calls.p, (uint64_t)S * M, hipMemcpyDeviceToHost));
     *passed_out = passed;
     if (d_calls_out) *d_calls_out = calls.release();
     return TD_OK;

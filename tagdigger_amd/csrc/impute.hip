@@ -7,9 +7,9 @@
 // ovl >= min_overlap weighs w = floor(32768 (2 ovl - dist) / ovl); the first k by (w descending, d ascending) vote with
 // their own call at m.  Only the INPUT's calls are read, so every cell is decided on its own.
 //
-// k_imp_transpose: grid (tiles of 64 markers), 256 threads.  k_ld_transpose of ld.hip over ALL markers, no compaction:
-//    T is Mpad rows of Spad bytes (both multiples of 64), codes 0 / 1 / 2 and 3 for everything else (missing, samples
-//    past S, rows past M).  missing[m] = S - the samples called at m falls out of the same pass.
+// k_calls_transpose<false> (calls_transpose.hpp, shared with ld.hip) over ALL markers, no compaction: T is Mpad rows of
+//    Spad bytes (both multiples of 64), codes 0 / 1 / 2 and 3 for everything else (missing, samples past S, rows past
+//    M).  called[m] = the samples called at m falls out of the same pass; S - called[m] are missing there.
 // k_impute: one workgroup of 256 threads per marker, decoded from a 2-D grid.  It leaves at once, after writing its
 //    statistics, when nobody is missing at m or the row of the table is empty.
 //      A. a thread takes samples s, s + 256, ...: it reads byte s of the L neighbour rows of T (the lanes are neighbouring
@@ -32,97 +32,23 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tagdig.h"
-
-// tagdig.hip (not exported): the error slot, the handle's device, waiting for the handle's own streams
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-__attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h);
-__attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx);
-}
+#include "calls_transpose.hpp"
+#include "td_internal.hpp"
 
 namespace {
 
-#define IMCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
-constexpr uint32_t IM_TILE = 64;                   // markers of a transpose tile
-constexpr uint32_t IM_STEP = 64;                   // samples staged at a time by the transpose; Spad is a multiple
 constexpr uint32_t IM_THREADS = 256;               // 4 waves
 constexpr uint32_t IM_WAVES = IM_THREADS / 64;
-constexpr uint32_t IM_ROW = IM_STEP + 16;          // bytes between the transpose tile's rows in LDS
 constexpr uint32_t IM_GRID_X = 65536;              // markers along grid x: a dimension holds fewer than 2^32 threads
-constexpr uint32_t IM_MISSING = 3;                 // what k_imp_transpose writes for every byte that is not 0 / 1 / 2
 constexpr uint32_t IM_TAIL = TD_IMPUTE_MAX_NBR * 4 + 16;   // LDS behind the planes: the table's row, four counters
-static_assert(IM_THREADS == IM_TILE * (IM_STEP / 16), "a thread of the transpose stages 16 samples of one marker");
+static_assert(CT_STEP % 64 == 0 && CT_MISSING > 2, "k_impute walks Spad by waves and takes a code above 2 as missing");
 static_assert(TD_IMPUTE_MAX_NBR == 64, "a plane is one 64-bit word per sample");
 static_assert(TD_IMPUTE_MAX_SAMPLES == 4096, "the key keeps 12 bits for the donor");
 static_assert(TD_IMPUTE_MAX_NBR <= IM_THREADS, "one thread loads one entry of the table's row");
 static_assert(25u * TD_IMPUTE_MAX_SAMPLES + IM_TAIL <= 160u * 1024u, "the planes of TD_IMPUTE_MAX_SAMPLES fit a CU's LDS");
 
-typedef int im_v4i __attribute__((ext_vector_type(4)));
-
-template <typename T> struct ImBuf {
-    T *p = nullptr;
-    ~ImBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
-struct ImEvents {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~ImEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 // the transpose and the vote kernel (device ms) of the calling thread's last td_impute_knn
 thread_local double g_im_times[2] = {0, 0};
-
-__global__ __launch_bounds__(IM_THREADS) void k_imp_transpose(const uint8_t *calls, uint32_t S, uint32_t M, uint32_t Spad, uint8_t *T,
-                                                              uint32_t *missing) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[IM_TILE * IM_ROW];
-    const uint32_t tid = threadIdx.x;
-    // gather: marker (tid & 63) of this tile, samples 16 (tid >> 6) .. + 15 of a step
-    const uint32_t gm = blockIdx.x * IM_TILE + (tid & 63u), gs = (tid >> 6) * 16u;
-    const uint8_t *col = gm < M ? calls + gm : nullptr;
-    // write: row (tid >> 2) of this tile, bytes 16 (tid & 3) .. + 15 of a step
-    const uint32_t wrow = tid >> 2, wq = (tid & 3u) * 16u;
-    uint8_t *out = T + (size_t)(blockIdx.x * IM_TILE + wrow) * Spad + wq;          // T has Mpad rows: inside it
-    uint32_t ncalled = 0;
-    for (uint32_t s0 = 0; s0 < Spad; s0 += IM_STEP) {
-        im_v4i v;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            uint32_t w = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                const uint32_t s = s0 + gs + 4u * d + k;
-                uint32_t c = col && s < S ? (uint32_t)col[(size_t)s * M] : IM_MISSING;     // s < S, gm < M: inside the matrix
-                if (c > 2u) c = IM_MISSING;
-                w |= c << (8 * k);
-            }
-            v[d] = (int)w;
-        }
-        *reinterpret_cast<im_v4i *>(tile + (tid & 63u) * IM_ROW + gs) = v;
-        __syncthreads();
-        const im_v4i r = *reinterpret_cast<const im_v4i *>(tile + wrow * IM_ROW + wq);
-        *reinterpret_cast<im_v4i *>(out + s0) = r;                 // Spad and the steps are multiples of 64: aligned
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const uint32_t w = (uint32_t)r[d];
-            ncalled += 4u - (uint32_t)__popc(w & (w >> 1) & 0x01010101u);          // a byte is 3 iff its bits 0 and 1 are set
-        }
-        __syncthreads();
-    }
-    ncalled += __shfl_xor(ncalled, 1);
-    ncalled += __shfl_xor(ncalled, 2);
-    const uint32_t m = blockIdx.x * IM_TILE + wrow;
-    if ((tid & 3u) == 0 && m < M) missing[m] = S - ncalled;        // (samples past S are written as 3 and not counted)
-}
 
 // the key of donor d for a target with planes (ct, t1, t2): (w << 12) | (4095 - d), or -1 when d is not called at the marker
 // (the target itself and the samples past S included) or shares fewer than min_overlap called neighbours with the target
@@ -147,7 +73,7 @@ __device__ __forceinline__ int im_wave_max(int v) {
 
 __global__ __launch_bounds__(IM_THREADS) void k_impute(const uint8_t *T, uint32_t Spad, uint32_t S, uint32_t M, const int32_t *nbr,
                                                        uint32_t L, uint32_t k, uint32_t min_overlap, uint32_t min_conf_ppm,
-                                                       const uint32_t *missing, uint8_t *out, uint32_t *stats) {
+                                                       const uint32_t *called, uint8_t *out, uint32_t *stats) {
     extern __shared__ __attribute__((aligned(16))) uint64_t im_lds[];
     const uint32_t m = blockIdx.y * IM_GRID_X + blockIdx.x;
     if (m >= M) return;                            // (the last row of the grid; uniform over the workgroup)
@@ -156,7 +82,7 @@ __global__ __launch_bounds__(IM_THREADS) void k_impute(const uint8_t *T, uint32_
     int32_t *nb = reinterpret_cast<int32_t *>(own + Spad);         // Spad is a multiple of 64: aligned
     uint32_t *cnt = reinterpret_cast<uint32_t *>(nb + TD_IMPUTE_MAX_NBR);          // imputed, no_donor, undecided
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t miss = missing[m];
+    const uint32_t miss = S - called[m];
     if (tid < L) nb[tid] = nbr[(size_t)m * L + tid];
     if (tid < 4u) cnt[tid] = 0;
     __syncthreads();
@@ -295,41 +221,42 @@ extern "C" int td_impute_knn(td_handle *h, const void *d_calls, uint32_t S, uint
     if (S == 0 || M == 0) return TD_OK;            // nothing missing, nothing to copy, no launch
     int rc = td_handle_wait_work(h);
     if (rc) return rc;
-    IMCHK(hipSetDevice(td_handle_device(h)));
-    const uint32_t ntiles = (M + IM_TILE - 1) / IM_TILE;
-    const uint32_t Spad = (S + IM_STEP - 1) / IM_STEP * IM_STEP;
-    const size_t Mpad = (size_t)ntiles * IM_TILE, cells = (size_t)S * M;
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    const uint32_t ntiles = (M + CT_TILE - 1) / CT_TILE;
+    const uint32_t Spad = (S + CT_STEP - 1) / CT_STEP * CT_STEP;
+    const size_t Mpad = (size_t)ntiles * CT_TILE, cells = (size_t)S * M;
     const uint32_t lds = 25u * Spad + IM_TAIL;
-    IMCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_impute), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ImEvents ev;
-    for (auto &e : ev.e) IMCHK(hipEventCreate(&e));
-    ImBuf<uint8_t> d_T, d_out;
-    ImBuf<uint32_t> d_missing, d_stats;
-    ImBuf<int32_t> d_nbr;
-    IMCHK(d_T.alloc(Mpad * Spad));
-    IMCHK(d_out.alloc(cells < 16 ? 16 : cells));   // (what td_dev_alloc would give)
-    IMCHK(d_missing.alloc(M));
-    IMCHK(d_stats.alloc((size_t)M * TD_IMPUTE_STATS));
-    IMCHK(d_nbr.alloc((size_t)M * L));
-    IMCHK(hipMemcpy(d_nbr.p, nbr, (size_t)M * L * sizeof(int32_t), hipMemcpyHostToDevice));
-    IMCHK(hipMemcpy(d_out.p, d_calls, cells, hipMemcpyDeviceToDevice));
-    IMCHK(hipEventRecord(ev.e[0], 0));
-    hipLaunchKernelGGL(k_imp_transpose, dim3(ntiles), dim3(IM_THREADS), 0, 0, (const uint8_t *)d_calls, S, M, Spad, d_T.p, d_missing.p);
-    IMCHK(hipGetLastError());
-    IMCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_impute), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    tdi::Events<3> ev;
+    TD_HIPCHK(ev.create());
+    tdi::DevBuf<uint8_t> d_T, d_out;
+    tdi::DevBuf<uint32_t> d_called, d_stats;
+    tdi::DevBuf<int32_t> d_nbr;
+    TD_HIPCHK(d_T.alloc(Mpad * Spad));
+    TD_HIPCHK(d_out.alloc(cells < 16 ? 16 : cells));   // (what td_dev_alloc would give)
+    TD_HIPCHK(d_called.alloc(Mpad));
+    TD_HIPCHK(d_stats.alloc((size_t)M * TD_IMPUTE_STATS));
+    TD_HIPCHK(d_nbr.alloc((size_t)M * L));
+    TD_HIPCHK(hipMemcpy(d_nbr.p, nbr, (size_t)M * L * sizeof(int32_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(d_out.p, d_calls, cells, hipMemcpyDeviceToDevice));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
+    hipLaunchKernelGGL(k_calls_transpose<false>, dim3(ntiles), dim3(CT_THREADS), 0, 0, (const uint8_t *)d_calls, S, M, nullptr, M, Spad, d_T.p,
+                       d_called.p);
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
     hipLaunchKernelGGL(k_impute, dim3(M < IM_GRID_X ? M : IM_GRID_X, (M + IM_GRID_X - 1) / IM_GRID_X), dim3(IM_THREADS), lds, 0,
-                       d_T.p, Spad, S, M, d_nbr.p, L, p->k, p->min_overlap, p->min_conf_ppm, d_missing.p, d_out.p, d_stats.p);
-    IMCHK(hipGetLastError());
-    IMCHK(hipEventRecord(ev.e[2], 0));
-    IMCHK(hipEventSynchronize(ev.e[2]));
+                       d_T.p, Spad, S, M, d_nbr.p, L, p->k, p->min_overlap, p->min_conf_ppm, d_called.p, d_out.p, d_stats.p);
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[2], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[2]));
     float f0 = 0, f1 = 0;
-    IMCHK(hipEventElapsedTime(&f0, ev.e[0], ev.e[1]));
-    IMCHK(hipEventElapsedTime(&f1, ev.e[1], ev.e[2]));
+    TD_HIPCHK(hipEventElapsedTime(&f0, ev.e[0], ev.e[1]));
+    TD_HIPCHK(hipEventElapsedTime(&f1, ev.e[1], ev.e[2]));
     g_im_times[0] = f0;
     g_im_times[1] = f1;
     if (ms) *ms = (double)f0 + (double)f1;
-    if (stats_out) IMCHK(hipMemcpy(stats_out, d_stats.p, (size_t)M * TD_IMPUTE_STATS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (calls_out) IMCHK(hipMemcpy(calls_out, d_out.p, cells, hipMemcpyDeviceToHost));
+    if (stats_out) TD_HIPCHK(hipMemcpy(stats_out, d_stats.p, (size_t)M * TD_IMPUTE_STATS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (calls_out) TD_HIPCHK(hipMemcpy(calls_out, d_out.p, cells, hipMemcpyDeviceToHost));
     if (d_calls_out) *d_calls_out = d_out.release();
     return TD_OK;
 }

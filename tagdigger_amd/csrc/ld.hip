@@ -7,11 +7,9 @@
 // The six sums behind cov and var are Gram products over the SAMPLES of the planes C (called, 0 / 1), X (dosage,
 // 0 / 1 / 2) and Q (dosage squared, 0 / 1 / 4), on the matrix cores (v_mfma_i32_32x32x32_i8): the transpose of relate.hip.
 //
-// k_ld_transpose: grid (tiles of 64 participating markers), 256 threads.  Gathers the participating columns through
+// k_calls_transpose<true> (calls_transpose.hpp, shared with impute.hip): gathers the participating columns through
 //    idx[] and writes them as rows: T is M'pad rows of Spad bytes (both multiples of 64), codes 0 / 1 / 2 and 3 for
-//    everything else (missing, samples past S, rows past M').  A thread reads 16 samples of one marker (the lanes of a
-//    wave are 64 neighbouring markers of one sample: one run of bytes where the mask leaves neighbours), and the tile
-//    goes through LDS so that four lanes write 64 contiguous bytes of a row.  called[] falls out of the same pass.
+//    everything else (missing, samples past S, rows past M').  called[] falls out of the same pass.
 // k_ld_pairs: grid (the tile pairs ti <= tj, LD_GRID_X to a row of the grid, decoded in closed form), 256 threads.  A
 //    workgroup owns 64 markers of tile ti against 64 of tile tj over all samples, LD_KSTEP at a time:
 //      - a thread loads 16 aligned bytes of one row of either tile (while the MFMAs of the step before run) and expands
@@ -34,91 +32,26 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tagdig.h"
-
-// tagdig.hip (not exported): the error slot, the handle's device, waiting for the handle's own streams
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-__attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h);
-}
+#include "calls_transpose.hpp"
+#include "td_internal.hpp"
 
 namespace {
 
-#define LDCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
 constexpr uint32_t LD_TILE = TD_LD_TILE;           // markers along a workgroup's tile edge
-constexpr uint32_t LD_KSTEP = 64;                  // samples staged in LDS at a time: two MFMAs of k = 32
-constexpr uint32_t LD_THREADS = 256;               // 4 waves, 2 x 2 over the tile pair
-constexpr uint32_t LD_ROW = LD_KSTEP + 16;         // bytes between plane rows in LDS (padded against bank conflicts)
+constexpr uint32_t LD_KSTEP = CT_STEP;             // samples staged in LDS at a time: two MFMAs of k = 32
+constexpr uint32_t LD_THREADS = CT_THREADS;        // 4 waves, 2 x 2 over the tile pair
+constexpr uint32_t LD_ROW = CT_ROW;                // bytes between plane rows in LDS (padded against bank conflicts)
 constexpr uint32_t LD_PLANE = LD_TILE * LD_ROW;    // bytes of one plane of one tile
 constexpr uint32_t LD_GRID_X = 32768;              // tile pairs along grid x: a dimension holds fewer than 2^32 threads, and y ends at 65 535
-constexpr uint32_t LD_MISSING = 3;                 // what k_ld_transpose writes for every byte that is not 0 / 1 / 2
+static_assert(LD_TILE == CT_TILE && CT_MISSING == 3, "a workgroup takes the rows of a transpose tile; ld_planes reads a code with bits 0 and 1 set as missing");
 static_assert(LD_TILE == 64 && LD_THREADS == LD_TILE * (LD_KSTEP / 16), "a thread stages 16 samples of one marker; 2 x 2 waves of 32 markers");
 static_assert(sizeof(td_ld_edge) == 24, "the edge record is six 32-bit words");
 
 typedef int ld_v4i __attribute__((ext_vector_type(4)));
 typedef int ld_v16i __attribute__((ext_vector_type(16)));
 
-template <typename T> struct LdBuf {
-    T *p = nullptr;
-    ~LdBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
-};
-
-struct LdEvents {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~LdEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 // the transpose, pair kernel (device ms) and sort (host ms) of the calling thread's last td_ld_pairs
 thread_local double g_ld_times[3] = {0, 0, 0};
-
-__global__ __launch_bounds__(LD_THREADS) void k_ld_transpose(const uint8_t *calls, uint32_t S, uint32_t M, const uint32_t *idx,
-                                                             uint32_t Mp, uint32_t Spad, uint8_t *T, uint32_t *called) {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[LD_TILE * LD_ROW];
-    const uint32_t tid = threadIdx.x;
-    // gather: marker (tid & 63) of this tile, samples 16 (tid >> 6) .. + 15 of a step
-    const uint32_t gm = blockIdx.x * LD_TILE + (tid & 63u), gs = (tid >> 6) * 16u;
-    const uint8_t *col = gm < Mp ? calls + idx[gm] : nullptr;      // idx[] < M
-    // write: row (tid >> 2) of this tile, bytes 16 (tid & 3) .. + 15 of a step
-    const uint32_t wrow = tid >> 2, wq = (tid & 3u) * 16u;
-    uint8_t *out = T + (size_t)(blockIdx.x * LD_TILE + wrow) * Spad + wq;
-    uint32_t ncalled = 0;
-    for (uint32_t s0 = 0; s0 < Spad; s0 += LD_KSTEP) {
-        ld_v4i v;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            uint32_t w = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                const uint32_t s = s0 + gs + 4u * d + k;
-                uint32_t c = col && s < S ? (uint32_t)col[(size_t)s * M] : LD_MISSING;     // s < S, idx < M: inside the matrix
-                if (c > 2u) c = LD_MISSING;
-                w |= c << (8 * k);
-            }
-            v[d] = (int)w;
-        }
-        *reinterpret_cast<ld_v4i *>(tile + (tid & 63u) * LD_ROW + gs) = v;
-        __syncthreads();
-        const ld_v4i r = *reinterpret_cast<const ld_v4i *>(tile + wrow * LD_ROW + wq);
-        *reinterpret_cast<ld_v4i *>(out + s0) = r;                 // Spad and the steps are multiples of 64: aligned
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            const uint32_t w = (uint32_t)r[d];
-            ncalled += 4u - (uint32_t)__popc(w & (w >> 1) & 0x01010101u);          // a byte is 3 iff its bits 0 and 1 are set
-        }
-        __syncthreads();
-    }
-    ncalled += __shfl_xor(ncalled, 1);
-    ncalled += __shfl_xor(ncalled, 2);
-    if ((tid & 3u) == 0) called[blockIdx.x * LD_TILE + wrow] = ncalled;           // (rows past M' count 0)
-}
 
 // the planes C, X, Q of 16 codes 0 .. 3 at dst, dst + LD_PLANE, dst + 2 LD_PLANE
 __device__ __forceinline__ void ld_planes(uint8_t *dst, ld_v4i c) {
@@ -301,11 +234,11 @@ extern "C" int td_ld_pairs(td_handle *h, const void *d_calls, uint32_t S, uint32
         if (!use || use[m]) idx[k++] = m;
     int rc = td_handle_wait_work(h);
     if (rc) return rc;
-    LDCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     if (Mp == 1) {                                 // no pair: the one column is counted on the host, without a launch
         if (called_out) {
             std::vector<uint8_t> col(S);
-            LDCHK(hipMemcpy2D(col.data(), 1, (const uint8_t *)d_calls + idx[0], M, 1, S, hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy2D(col.data(), 1, (const uint8_t *)d_calls + idx[0], M, 1, S, hipMemcpyDeviceToHost));
             uint32_t n = 0;
             for (uint8_t c : col) n += c <= 2;
             called_out[idx[0]] = n;
@@ -317,48 +250,48 @@ extern "C" int td_ld_pairs(td_handle *h, const void *d_calls, uint32_t S, uint32
     const uint32_t Mpad = ntiles * LD_TILE, Spad = (S + LD_KSTEP - 1) / LD_KSTEP * LD_KSTEP;
     const uint64_t pairs = (uint64_t)Mp * (Mp - 1) / 2;
     const uint64_t devcap = edges_out ? std::min(capacity, pairs) : 0;
-    LdEvents ev;
-    for (auto &e : ev.e) LDCHK(hipEventCreate(&e));
-    LdBuf<uint32_t> d_idx, d_called, d_degree;
-    LdBuf<uint8_t> d_T;
-    LdBuf<unsigned long long> d_count;
-    LdBuf<td_ld_edge> d_edges;
-    LDCHK(d_idx.alloc(Mp));
-    LDCHK(d_called.alloc(Mpad));
-    LDCHK(d_degree.alloc(Mpad));
-    LDCHK(d_T.alloc((size_t)Mpad * Spad));
-    LDCHK(d_count.alloc(1));
-    LDCHK(d_edges.alloc(devcap));
-    LDCHK(hipMemcpy(d_idx.p, idx.data(), (size_t)Mp * sizeof(uint32_t), hipMemcpyHostToDevice));
-    LDCHK(hipMemset(d_degree.p, 0, (size_t)Mpad * sizeof(uint32_t)));
-    LDCHK(hipMemset(d_count.p, 0, sizeof(unsigned long long)));
-    LDCHK(hipEventRecord(ev.e[0], 0));
-    hipLaunchKernelGGL(k_ld_transpose, dim3(ntiles), dim3(LD_THREADS), 0, 0, (const uint8_t *)d_calls, S, M, d_idx.p, Mp, Spad,
+    tdi::Events<3> ev;
+    TD_HIPCHK(ev.create());
+    tdi::DevBuf<uint32_t> d_idx, d_called, d_degree;
+    tdi::DevBuf<uint8_t> d_T;
+    tdi::DevBuf<unsigned long long> d_count;
+    tdi::DevBuf<td_ld_edge> d_edges;
+    TD_HIPCHK(d_idx.alloc(Mp));
+    TD_HIPCHK(d_called.alloc(Mpad));
+    TD_HIPCHK(d_degree.alloc(Mpad));
+    TD_HIPCHK(d_T.alloc((size_t)Mpad * Spad));
+    TD_HIPCHK(d_count.alloc(1));
+    TD_HIPCHK(d_edges.alloc(devcap));
+    TD_HIPCHK(hipMemcpy(d_idx.p, idx.data(), (size_t)Mp * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemset(d_degree.p, 0, (size_t)Mpad * sizeof(uint32_t)));
+    TD_HIPCHK(hipMemset(d_count.p, 0, sizeof(unsigned long long)));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
+    hipLaunchKernelGGL(k_calls_transpose<true>, dim3(ntiles), dim3(CT_THREADS), 0, 0, (const uint8_t *)d_calls, S, M, d_idx.p, Mp, Spad,
                        d_T.p, d_called.p);
-    LDCHK(hipGetLastError());
-    LDCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
     hipLaunchKernelGGL(k_ld_pairs, dim3(std::min(npairs, LD_GRID_X), (npairs + LD_GRID_X - 1) / LD_GRID_X), dim3(LD_THREADS), 0, 0,
                        d_T.p, Spad, Mp, npairs, d_idx.p, min_r2_ppm, min_shared, d_edges.p, (unsigned long long)devcap, d_count.p, d_degree.p);
-    LDCHK(hipGetLastError());
-    LDCHK(hipEventRecord(ev.e[2], 0));
-    LDCHK(hipEventSynchronize(ev.e[2]));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[2], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[2]));
     float f0 = 0, f1 = 0;
-    LDCHK(hipEventElapsedTime(&f0, ev.e[0], ev.e[1]));
-    LDCHK(hipEventElapsedTime(&f1, ev.e[1], ev.e[2]));
+    TD_HIPCHK(hipEventElapsedTime(&f0, ev.e[0], ev.e[1]));
+    TD_HIPCHK(hipEventElapsedTime(&f1, ev.e[1], ev.e[2]));
     g_ld_times[0] = f0;
     g_ld_times[1] = f1;
     if (ms) *ms = (double)f0 + (double)f1;
     unsigned long long total = 0;
-    LDCHK(hipMemcpy(&total, d_count.p, sizeof(total), hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(&total, d_count.p, sizeof(total), hipMemcpyDeviceToHost));
     if (n_out) *n_out = total;
     if (degree_out || called_out) {
         std::vector<uint32_t> tmp(Mp);
         if (degree_out) {
-            LDCHK(hipMemcpy(tmp.data(), d_degree.p, (size_t)Mp * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(tmp.data(), d_degree.p, (size_t)Mp * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (uint32_t k = 0; k < Mp; ++k) degree_out[idx[k]] = tmp[k];
         }
         if (called_out) {
-            LDCHK(hipMemcpy(tmp.data(), d_called.p, (size_t)Mp * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(tmp.data(), d_called.p, (size_t)Mp * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (uint32_t k = 0; k < Mp; ++k) called_out[idx[k]] = tmp[k];
         }
     }
@@ -366,7 +299,7 @@ extern "C" int td_ld_pairs(td_handle *h, const void *d_calls, uint32_t S, uint32
     if (total > capacity)
         return td_fail_internal(TD_E_LIMIT, (std::to_string(total) + " edges, the buffer holds " + std::to_string(capacity)).c_str());
     if (total) {
-        LDCHK(hipMemcpy(edges_out, d_edges.p, (size_t)total * sizeof(td_ld_edge), hipMemcpyDeviceToHost));
+        TD_HIPCHK(hipMemcpy(edges_out, d_edges.p, (size_t)total * sizeof(td_ld_edge), hipMemcpyDeviceToHost));
         const auto t0 = std::chrono::steady_clock::now();
         std::sort(edges_out, edges_out + total, [](const td_ld_edge &a, const td_ld_edge &b) {
             return a.i != b.i ? a.i < b.i : a.j < b.j;

@@ -32,24 +32,9 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/tagdig.h"
-
-// tagdig.hip (not exported): the library's error slot, the handle's device and options, the staging thread count
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-__attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h);
-__attribute__((visibility("hidden"))) int td_stage_thread_count(void);
-}
+#include "td_internal.hpp"
 
 namespace {
-
-#define MDCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 struct Md5Job {
     uint64_t off;       // bytes from the slab's start to the run's first block
@@ -184,26 +169,6 @@ __global__ __launch_bounds__(64) void k_md5_tail(const uint8_t *__restrict__ dat
     jobs[i] = Md5Job{128 * (uint64_t)i, total / 64u, i};
 }
 
-template <typename T> struct MdBuf {
-    T *p = nullptr;
-    ~MdBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
-template <typename T> struct MdPin {
-    T *p = nullptr;
-    ~MdPin() { if (p) (void)hipHostFree(p); }
-    hipError_t alloc(size_t n) { return hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault); }
-};
-struct MdEvent {
-    hipEvent_t e = nullptr;
-    ~MdEvent() { if (e) (void)hipEventDestroy(e); }
-};
-
-float md_elapsed(hipEvent_t a, hipEvent_t b) {
-    float f = 0.0f;
-    return hipEventElapsedTime(&f, a, b) == hipSuccess ? f : 0.0f;
-}
-
 hipError_t init_states(uint32_t *d_state, uint32_t n) {
     std::vector<uint32_t> init(4 * (size_t)n);
     for (size_t i = 0; i < n; i++) memcpy(&init[4 * i], MD5_INIT, 16);
@@ -242,39 +207,38 @@ extern "C" int td_md5_device(td_handle *h, const void *d_data, const uint64_t *o
         whole += (offs[i + 1] - offs[i]) / 64;
     }
     if (offs[n] && !d_data) return td_fail_internal(TD_E_ARG, "NULL data");
-    MDCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     std::vector<Md5Job> jobs(n);
     for (uint32_t i = 0; i < n; i++) {
         const uint64_t nb = (offs[i + 1] - offs[i]) / 64;
         if (nb > 0xffffffffull) return td_fail_internal(TD_E_LIMIT, "message of 256 GiB or more");
         jobs[i] = Md5Job{offs[i], (uint32_t)nb, i};
     }
-    MdBuf<uint32_t> d_state; MdBuf<Md5Job> d_jobs, d_tjobs; MdBuf<uint64_t> d_offs; MdBuf<uint8_t> d_tails;
-    MdEvent e0, e1;
-    MDCHK(d_state.alloc(4 * (size_t)n));
-    MDCHK(d_jobs.alloc(n));
-    MDCHK(d_tjobs.alloc(n));
-    MDCHK(d_offs.alloc((size_t)n + 1));
-    MDCHK(d_tails.alloc(128 * (size_t)n));
-    MDCHK(hipEventCreate(&e0.e));
-    MDCHK(hipEventCreate(&e1.e));
-    MDCHK(init_states(d_state.p, n));
-    MDCHK(hipMemcpy(d_jobs.p, jobs.data(), n * sizeof(Md5Job), hipMemcpyHostToDevice));
-    MDCHK(hipMemcpy(d_offs.p, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-    MDCHK(hipEventRecord(e0.e, 0));
+    tdi::DevBuf<uint32_t> d_state; tdi::DevBuf<Md5Job> d_jobs, d_tjobs; tdi::DevBuf<uint64_t> d_offs; tdi::DevBuf<uint8_t> d_tails;
+    tdi::Events<2> ev;
+    TD_HIPCHK(d_state.alloc(4 * (size_t)n));
+    TD_HIPCHK(d_jobs.alloc(n));
+    TD_HIPCHK(d_tjobs.alloc(n));
+    TD_HIPCHK(d_offs.alloc((size_t)n + 1));
+    TD_HIPCHK(d_tails.alloc(128 * (size_t)n));
+    TD_HIPCHK(ev.create());
+    TD_HIPCHK(init_states(d_state.p, n));
+    TD_HIPCHK(hipMemcpy(d_jobs.p, jobs.data(), n * sizeof(Md5Job), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(d_offs.p, offs, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     if (whole) {
         if (aligned) k_md5_update<true><<<waves(n), 64, 0, 0>>>((const uint8_t *)d_data, d_jobs.p, n, d_state.p);
         else k_md5_update<false><<<waves(n), 64, 0, 0>>>((const uint8_t *)d_data, d_jobs.p, n, d_state.p);
-        MDCHK(hipGetLastError());
+        TD_HIPCHK(hipGetLastError());
     }
     k_md5_tail<<<waves(n), 64, 0, 0>>>((const uint8_t *)d_data, d_offs.p, n, d_tails.p, d_tjobs.p);
-    MDCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     k_md5_update<true><<<waves(n), 64, 0, 0>>>(d_tails.p, d_tjobs.p, n, d_state.p);
-    MDCHK(hipGetLastError());
-    MDCHK(hipEventRecord(e1.e, 0));
-    MDCHK(hipEventSynchronize(e1.e));
-    if (ms) *ms = md_elapsed(e0.e, e1.e);
-    MDCHK(hipMemcpy(digests, d_state.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
+    if (ms) *ms = ev.elapsed(0, 1);
+    TD_HIPCHK(hipMemcpy(digests, d_state.p, 16 * (size_t)n, hipMemcpyDeviceToHost));
     return TD_OK;
 }
 
@@ -307,34 +271,33 @@ extern "C" int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, 
     uint64_t cap = 0;                       // the largest round: every file's first piece
     for (uint32_t i = 0; i < n; i++) cap += std::min(P, total[i]);
 
-    MDCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     struct Slot {
-        MdPin<uint8_t> pin; MdPin<Md5Job> pin_jobs; MdBuf<uint8_t> dev; MdBuf<Md5Job> dev_jobs;
-        MdEvent up, k0, k1; bool busy = false;
+        tdi::PinBuf<uint8_t> pin; tdi::PinBuf<Md5Job> pin_jobs; tdi::DevBuf<uint8_t> dev; tdi::DevBuf<Md5Job> dev_jobs;
+        tdi::Events<1> up; tdi::Events<2> k; bool busy = false;         // up: no timing; k: around the kernel
     } slot[2];
-    MdBuf<uint32_t> d_state;
+    tdi::DevBuf<uint32_t> d_state;
     // two streams: the upload of round r + 1 runs beside the kernel of round r (an event orders a round's kernel
     // behind its upload; a slot is refilled only after its kernel is through)
     hipStream_t st = nullptr, sc = nullptr;
     struct StreamGuard { hipStream_t &s; ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } guard{st}, guard_copy{sc};
-    MDCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    MDCHK(hipStreamCreateWithFlags(&sc, hipStreamNonBlocking));
-    MDCHK(d_state.alloc(4 * (size_t)n));
-    MDCHK(init_states(d_state.p, n));
+    TD_HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    TD_HIPCHK(hipStreamCreateWithFlags(&sc, hipStreamNonBlocking));
+    TD_HIPCHK(d_state.alloc(4 * (size_t)n));
+    TD_HIPCHK(init_states(d_state.p, n));
     for (auto &s : slot) {
-        MDCHK(s.pin.alloc(cap));
-        MDCHK(s.pin_jobs.alloc(n));
-        MDCHK(s.dev.alloc(cap));
-        MDCHK(s.dev_jobs.alloc(n));
-        MDCHK(hipEventCreateWithFlags(&s.up.e, hipEventDisableTiming));
-        MDCHK(hipEventCreate(&s.k0.e));
-        MDCHK(hipEventCreate(&s.k1.e));
+        TD_HIPCHK(s.pin.alloc(cap));
+        TD_HIPCHK(s.pin_jobs.alloc(n));
+        TD_HIPCHK(s.dev.alloc(cap));
+        TD_HIPCHK(s.dev_jobs.alloc(n));
+        TD_HIPCHK(hipEventCreateWithFlags(&s.up.e[0], hipEventDisableTiming));
+        TD_HIPCHK(s.k.create());
     }
     auto retire = [&](Slot &s) -> hipError_t {          // wait until the slot's kernel is through; book its time
         if (!s.busy) return hipSuccess;
         const double t0 = now_ms();
-        const hipError_t e = hipEventSynchronize(s.k1.e);
-        if (ms) { ms[1] += now_ms() - t0; ms[2] += md_elapsed(s.k0.e, s.k1.e); }
+        const hipError_t e = hipEventSynchronize(s.k.e[1]);
+        if (ms) { ms[1] += now_ms() - t0; ms[2] += s.k.elapsed(0, 1); }
         s.busy = false;
         return e;
     };
@@ -369,7 +332,7 @@ extern "C" int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, 
     const int nthreads = td_stage_thread_count();
     for (uint32_t round = 0;; round++) {
         Slot &s = slot[round & 1];
-        MDCHK(retire(s));
+        TD_HIPCHK(retire(s));
         tasks.clear();
         uint64_t used = 0;
         uint32_t njobs = 0;
@@ -392,18 +355,18 @@ extern "C" int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, 
         for (auto &th : pool) th.join();
         if (ms) ms[0] += now_ms() - t0;
         if (bad.load() != UINT32_MAX) return io_fail(bad.load(), "cannot read", bad_errno.load());
-        MDCHK(hipMemcpyAsync(s.dev.p, s.pin.p, used, hipMemcpyHostToDevice, sc));
-        MDCHK(hipMemcpyAsync(s.dev_jobs.p, s.pin_jobs.p, njobs * sizeof(Md5Job), hipMemcpyHostToDevice, sc));
-        MDCHK(hipEventRecord(s.up.e, sc));
-        MDCHK(hipStreamWaitEvent(st, s.up.e, 0));
-        MDCHK(hipEventRecord(s.k0.e, st));
+        TD_HIPCHK(hipMemcpyAsync(s.dev.p, s.pin.p, used, hipMemcpyHostToDevice, sc));
+        TD_HIPCHK(hipMemcpyAsync(s.dev_jobs.p, s.pin_jobs.p, njobs * sizeof(Md5Job), hipMemcpyHostToDevice, sc));
+        TD_HIPCHK(hipEventRecord(s.up.e[0], sc));
+        TD_HIPCHK(hipStreamWaitEvent(st, s.up.e[0], 0));
+        TD_HIPCHK(hipEventRecord(s.k.e[0], st));
         k_md5_update<true><<<waves(njobs), 64, 0, st>>>(s.dev.p, s.dev_jobs.p, njobs, d_state.p);
-        MDCHK(hipGetLastError());
-        MDCHK(hipEventRecord(s.k1.e, st));
+        TD_HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipEventRecord(s.k.e[1], st));
         s.busy = true;
     }
-    for (auto &s : slot) MDCHK(retire(s));
-    MDCHK(hipMemcpyAsync(digests, d_state.p, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
-    MDCHK(hipStreamSynchronize(st));
+    for (auto &s : slot) TD_HIPCHK(retire(s));
+    TD_HIPCHK(hipMemcpyAsync(digests, d_state.p, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+    TD_HIPCHK(hipStreamSynchronize(st));
     return TD_OK;
 }

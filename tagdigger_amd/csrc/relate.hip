@@ -23,23 +23,9 @@
 #include <string.h>
 #include <string>
 
-#include "../../include/tagdig.h"
-
-// tagdig.hip (not exported): the error slot, the handle's device, waiting for the handle's own streams
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-__attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h);
-}
+#include "td_internal.hpp"
 
 namespace {
-
-#define RLCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 constexpr uint32_t RL_TILE = TD_RELATE_TILE;       // samples along a workgroup's tile edge
 constexpr uint32_t RL_KCHUNK = TD_RELATE_KCHUNK;   // markers of a workgroup
@@ -52,18 +38,6 @@ static_assert(RL_KCHUNK % RL_KSTEP == 0, "a chunk is walked in whole steps");
 
 typedef int rl_v4i __attribute__((ext_vector_type(4)));
 typedef int rl_v16i __attribute__((ext_vector_type(16)));
-
-template <typename T> struct RlBuf {
-    T *p = nullptr;
-    ~RlBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
-struct RlEvents {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~RlEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 // 0x01 in every byte of x that equals `code`, 0x00 elsewhere (any byte value)
 __host__ __device__ __forceinline__ uint32_t rl_eq(uint32_t x, uint32_t code) {
@@ -226,41 +200,41 @@ extern "C" int td_relate_joint(td_handle *h, const void *d_calls, uint32_t S, ui
     if (S == 0 || M == 0) {                        // nothing takes part: all zero (or empty), no launch
         if (joint_out) memset(joint_out, 0, cells * sizeof(uint32_t));
         if (d_joint_out) {
-            RLCHK(hipSetDevice(td_handle_device(h)));
-            RlBuf<uint32_t> out;
-            RLCHK(out.alloc(cells));
-            RLCHK(hipMemset(out.p, 0, (cells ? cells : 1) * sizeof(uint32_t)));
+            TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+            tdi::DevBuf<uint32_t> out;
+            TD_HIPCHK(out.alloc(cells));
+            TD_HIPCHK(hipMemset(out.p, 0, (cells ? cells : 1) * sizeof(uint32_t)));
             *d_joint_out = out.release();
         }
         return TD_OK;
     }
     int rc = td_handle_wait_work(h);
     if (rc) return rc;
-    RLCHK(hipSetDevice(td_handle_device(h)));
-    RlEvents ev;
-    for (auto &e : ev.e) RLCHK(hipEventCreate(&e));
-    RlBuf<uint32_t> out;
-    RlBuf<uint8_t> duse;
-    RLCHK(out.alloc(cells));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    tdi::Events<2> ev;
+    TD_HIPCHK(ev.create());
+    tdi::DevBuf<uint32_t> out;
+    tdi::DevBuf<uint8_t> duse;
+    TD_HIPCHK(out.alloc(cells));
     if (use) {
-        RLCHK(duse.alloc(M));
-        RLCHK(hipMemcpy(duse.p, use, M, hipMemcpyHostToDevice));
+        TD_HIPCHK(duse.alloc(M));
+        TD_HIPCHK(hipMemcpy(duse.p, use, M, hipMemcpyHostToDevice));
     }
-    RLCHK(hipMemset(out.p, 0, cells * sizeof(uint32_t)));
+    TD_HIPCHK(hipMemset(out.p, 0, cells * sizeof(uint32_t)));
     const uint32_t ntiles = (S + RL_TILE - 1) / RL_TILE;           // <= 256: ntiles (ntiles + 1) / 2 <= 32 896 in grid y
     const uint32_t chunks = (M + RL_KCHUNK - 1) / RL_KCHUNK;       // <= 65 536 in grid x
-    RLCHK(hipEventRecord(ev.e[0], 0));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     hipLaunchKernelGGL(k_relate, dim3(chunks, ntiles * (ntiles + 1) / 2), dim3(RL_THREADS), 0, 0, (const uint8_t *)d_calls, S, M,
                        use ? duse.p : nullptr, ntiles, out.p);
-    RLCHK(hipGetLastError());
-    RLCHK(hipEventRecord(ev.e[1], 0));
-    RLCHK(hipEventSynchronize(ev.e[1]));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
     if (ms) {
         float f = 0;
-        RLCHK(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
+        TD_HIPCHK(hipEventElapsedTime(&f, ev.e[0], ev.e[1]));
         *ms = f;
     }
-    if (joint_out) RLCHK(hipMemcpy(joint_out, out.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (joint_out) TD_HIPCHK(hipMemcpy(joint_out, out.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (d_joint_out) *d_joint_out = out.release();
     return TD_OK;
 }

@@ -34,6 +34,7 @@
 #include "gz_resolve.hpp"
 #include "gz_gpu.hpp"
 #include "piece_sink.hpp"
+#include "td_internal.hpp"                      // the hidden hooks defined below, as the other translation units see them
 
 namespace {
 
@@ -688,7 +689,7 @@ int build_barcode_blob(const std::vector<std::pair<std::string, uint32_t>> &entr
 extern "C" {
 
 const char *td_last_error(void) { return g_err.c_str(); }
-// for the library's other translation units (csrc/fragsize.hip); hidden: not part of the C-ABI
+// for the library's other translation units (td_internal.hpp declares these and the hooks below); hidden: not part of the C-ABI
 __attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg) { return fail(code, msg); }
 __attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h) { return h->device; }
 uint32_t td_last_bad_index(void) { return g_bad; }
@@ -698,10 +699,10 @@ namespace { inline int stage_threads(); }
 // for csrc/md5.hip (hidden): the "md5_piece" option and the number of staging threads
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h) { return h->md5_piece; }
 extern "C" __attribute__((visibility("hidden"))) int td_stage_thread_count(void) { return stage_threads(); }
-// for csrc/tagnet.hip (hidden): the "tagnet_max_compares" option, and the index td_last_bad_index reports
+// the "tagnet_max_compares" option (csrc/tagnet.hip), and the index td_last_bad_index reports
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_compares(const td_handle *h) { return h->tagnet_max_compares; }
 extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx) { g_bad = idx; }
-// for csrc/genocall.hip (hidden): every launch enqueued through this handle (they may be on its own streams) has finished
+// every launch enqueued through this handle (they may be on its own streams) has finished
 extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h) {
     hipError_t e = hipSetDevice(h->device);
     if (e == hipSuccess) e = hipStreamSynchronize(h->work_stream);
@@ -713,7 +714,6 @@ extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_hand
 extern "C" __attribute__((visibility("hidden"))) void **td_handle_census(td_handle *h) { return &h->census; }
 extern "C" __attribute__((visibility("hidden"))) void *td_handle_work_stream(const td_handle *h) { return (void *)h->work_stream; }
 extern "C" __attribute__((visibility("hidden"))) int td_handle_num_cu(const td_handle *h) { return h->num_cu; }
-extern "C" __attribute__((visibility("hidden"))) void td_census_release(td_handle *h);     // (census.hip)
 extern "C" __attribute__((visibility("hidden"))) int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
                                                                     uint8_t **blob_out, uint32_t *bytes, uint32_t *off_bmeta, uint32_t *off_bdir) {
     std::vector<std::string> bs(n_barcut);

@@ -34,16 +34,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tagdig.h"
 #include "radix_sort.hpp"
-
-// tagdig.hip (not exported): the error slot, the handle's device, the "tagnet_max_compares" option
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-__attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_compares(const td_handle *h);
-}
+#include "td_internal.hpp"
 
 struct td_tagnet {
     uint32_t n;
@@ -54,34 +46,16 @@ struct td_tagnet {
 
 namespace {
 
-#define TNCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
 constexpr int TN_TILE = TD_TAGNET_TILE;            // rows and columns of a tile = threads of a workgroup
 constexpr int TN_QUEUE = 1024;                     // edge records a workgroup collects in LDS
 constexpr uint64_t TN_KEPT = 1ull << 63;
 constexpr uint64_t TN_MAX_TILES = 0x7fffffffull;
 static_assert(TN_TILE == 256, "k_tn_compare is written for workgroups of 256 threads");
 
-template <typename T> struct TnBuf {
-    T *p = nullptr;
-    ~TnBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
-struct TnEvents {
-    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~TnEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 // one sorted order: what K3 prepares and K4 reads
 struct TnOrder {
-    TnBuf<uint64_t> lead, other, cnt;
-    TnBuf<uint32_t> idx, end, tile_off;
+    tdi::DevBuf<uint64_t> lead, other, cnt;
+    tdi::DevBuf<uint32_t> idx, end, tile_off;
     uint32_t ntiles = 0;
 };
 
@@ -263,26 +237,21 @@ __global__ __launch_bounds__(256) void k_tn_select(const uint64_t *edges, uint64
     }
 }
 
-float tn_elapsed(hipEvent_t a, hipEvent_t b) {
-    float f = 0;
-    return hipEventElapsedTime(&f, a, b) == hipSuccess ? f : 0.0f;
-}
-
 // K3 for one order: key = its two words (leading first); perm sorted by them
 int tn_prepare(const uint64_t *key, const uint64_t *counts, const uint32_t *perm, uint32_t n, uint32_t nrb, TnOrder &o,
                unsigned long long *d_compares) {
-    TNCHK(o.lead.alloc(n));
-    TNCHK(o.other.alloc(n));
-    TNCHK(o.cnt.alloc(n));
-    TNCHK(o.idx.alloc(n));
-    TNCHK(o.end.alloc(n));
-    TNCHK(o.tile_off.alloc(nrb + 1ull));
+    TD_HIPCHK(o.lead.alloc(n));
+    TD_HIPCHK(o.other.alloc(n));
+    TD_HIPCHK(o.cnt.alloc(n));
+    TD_HIPCHK(o.idx.alloc(n));
+    TD_HIPCHK(o.end.alloc(n));
+    TD_HIPCHK(o.tile_off.alloc(nrb + 1ull));
     const dim3 grid((n + 255) / 256), block(256);
     hipLaunchKernelGGL(k_tn_gather, grid, block, 0, 0, key, counts, perm, n, o.lead.p, o.other.p, o.cnt.p, o.idx.p);
     hipLaunchKernelGGL(k_tn_runs, grid, block, 0, 0, o.lead.p, n, o.end.p, d_compares);
     hipLaunchKernelGGL(k_tn_tiles, dim3((nrb + 1 + 255) / 256), block, 0, 0, o.end.p, n, nrb, o.tile_off.p);
     hipLaunchKernelGGL(tdrs::k_rs_scan, dim3(1), dim3(tdrs::RS_SCAN_THREADS), 0, 0, o.tile_off.p, (uint64_t)nrb + 1);
-    TNCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     return TD_OK;
 }
 
@@ -307,73 +276,73 @@ extern "C" int td_tagnet_build(td_handle *h, const char *seqs, const uint64_t *c
     uint64_t st[8] = {n, 0, 0, n, 0, 0, 0, 0};
 
     if (n) {
-        TNCHK(hipSetDevice(td_handle_device(h)));
-        TnEvents ev;
-        for (auto &e : ev.e) TNCHK(hipEventCreate(&e));
-        TnBuf<uint8_t> dseq;
-        TnBuf<uint64_t> key, dcnt, edges, pairs;
-        TnBuf<uint16_t> len;
-        TnBuf<uint32_t> flags, perm0, perm1, perm2, differ, hist, deg;
-        TnBuf<unsigned long long> ctr;                 // [0] compares, [1] edges, [2] pairs
+        TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+        tdi::Events<6> ev;
+        TD_HIPCHK(ev.create());
+        tdi::DevBuf<uint8_t> dseq;
+        tdi::DevBuf<uint64_t> key, dcnt, edges, pairs;
+        tdi::DevBuf<uint16_t> len;
+        tdi::DevBuf<uint32_t> flags, perm0, perm1, perm2, differ, hist, deg;
+        tdi::DevBuf<unsigned long long> ctr;                 // [0] compares, [1] edges, [2] pairs
         // ---- K1
-        TNCHK(dseq.alloc((uint64_t)n * L));
-        TNCHK(key.alloc(3ull * n));
-        TNCHK(dcnt.alloc(n));
-        TNCHK(flags.alloc(3));                         // [0] first bad tag, [1] first duplicate, [2] a write past a buffer
-        TNCHK(ctr.alloc(3));
-        TNCHK(hipMemcpy(dseq.p, seqs, (uint64_t)n * L, hipMemcpyHostToDevice));
-        TNCHK(hipMemcpy(dcnt.p, counts, (uint64_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+        TD_HIPCHK(dseq.alloc((uint64_t)n * L));
+        TD_HIPCHK(key.alloc(3ull * n));
+        TD_HIPCHK(dcnt.alloc(n));
+        TD_HIPCHK(flags.alloc(3));                         // [0] first bad tag, [1] first duplicate, [2] a write past a buffer
+        TD_HIPCHK(ctr.alloc(3));
+        TD_HIPCHK(hipMemcpy(dseq.p, seqs, (uint64_t)n * L, hipMemcpyHostToDevice));
+        TD_HIPCHK(hipMemcpy(dcnt.p, counts, (uint64_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
         const uint32_t finit[3] = {0xffffffffu, 0xffffffffu, 0u};
-        TNCHK(hipMemcpy(flags.p, finit, sizeof finit, hipMemcpyHostToDevice));
-        TNCHK(hipMemset(ctr.p, 0, 3 * sizeof(unsigned long long)));
+        TD_HIPCHK(hipMemcpy(flags.p, finit, sizeof finit, hipMemcpyHostToDevice));
+        TD_HIPCHK(hipMemset(ctr.p, 0, 3 * sizeof(unsigned long long)));
         const dim3 grid((n + 255) / 256), block(256);
-        TNCHK(hipEventRecord(ev.e[0], 0));
+        TD_HIPCHK(hipEventRecord(ev.e[0], 0));
         hipLaunchKernelGGL(k_tn_pack, grid, block, 0, 0, dseq.p, n, L, half, key.p, flags.p);
-        TNCHK(hipGetLastError());
-        TNCHK(hipEventRecord(ev.e[1], 0));
+        TD_HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipEventRecord(ev.e[1], 0));
         uint32_t fl[3];
-        TNCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
+        TD_HIPCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
         if (fl[0] != 0xffffffffu) {
             td_set_bad_index(fl[0]);
             return td_fail_internal(TD_E_ALPHABET, ("tag " + std::to_string(fl[0]) + " holds a byte outside ACGT").c_str());
         }
         if (n > 1) {
             // ---- K2
-            TNCHK(len.alloc(n));
-            TNCHK(perm0.alloc(n));
-            TNCHK(perm1.alloc(n));
-            TNCHK(perm2.alloc(n));
-            TNCHK(differ.alloc(3));
-            TNCHK(hist.alloc(256ull * tdrs::rs_blocks(n)));
-            TNCHK(hipMemset(len.p, 0, (uint64_t)n * sizeof(uint16_t)));
+            TD_HIPCHK(len.alloc(n));
+            TD_HIPCHK(perm0.alloc(n));
+            TD_HIPCHK(perm1.alloc(n));
+            TD_HIPCHK(perm2.alloc(n));
+            TD_HIPCHK(differ.alloc(3));
+            TD_HIPCHK(hist.alloc(256ull * tdrs::rs_blocks(n)));
+            TD_HIPCHK(hipMemset(len.p, 0, (uint64_t)n * sizeof(uint16_t)));
             std::vector<uint32_t> ident(n);
             for (uint32_t i = 0; i < n; ++i) ident[i] = i;
             uint32_t passes = 0;
             // (A, B): the result stays in perm0 / perm1; (B, A) then sorts in perm2 and the buffer that is left
-            TNCHK(hipMemcpy(perm0.p, ident.data(), (uint64_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            TNCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
-            TNCHK(tdrs::rs_sort(key.p, len.p, n, 2, &perm0.p, &perm1.p, differ.p, hist.p, &passes));
+            TD_HIPCHK(hipMemcpy(perm0.p, ident.data(), (uint64_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            TD_HIPCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
+            TD_HIPCHK(tdrs::rs_sort(key.p, len.p, n, 2, &perm0.p, &perm1.p, differ.p, hist.p, &passes));
             hipLaunchKernelGGL(k_tn_dup, grid, block, 0, 0, key.p, perm0.p, n, flags.p + 1);
-            TNCHK(hipGetLastError());
-            TNCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipGetLastError());
+            TD_HIPCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
             if (fl[1] != 0xffffffffu) {
                 td_set_bad_index(fl[1]);
                 return td_fail_internal(TD_E_OVERLAP, ("tag " + std::to_string(fl[1]) + " equals an earlier tag").c_str());
             }
-            TNCHK(hipMemcpy(perm2.p, ident.data(), (uint64_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            TNCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
-            TNCHK(tdrs::rs_sort(key.p + n, len.p, n, 2, &perm2.p, &perm1.p, differ.p, hist.p, &passes));
-            TNCHK(hipEventRecord(ev.e[2], 0));
+            TD_HIPCHK(hipMemcpy(perm2.p, ident.data(), (uint64_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            TD_HIPCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
+            TD_HIPCHK(tdrs::rs_sort(key.p + n, len.p, n, 2, &perm2.p, &perm1.p, differ.p, hist.p, &passes));
+            TD_HIPCHK(hipEventRecord(ev.e[2], 0));
             // ---- K3
             const uint32_t nrb = (n + TN_TILE - 1) / TN_TILE;
             TnOrder ord[2];
             int rc;
             if ((rc = tn_prepare(key.p, dcnt.p, perm0.p, n, nrb, ord[0], ctr.p))) return rc;
             if ((rc = tn_prepare(key.p + n, dcnt.p, perm2.p, n, nrb, ord[1], ctr.p))) return rc;
-            TNCHK(hipEventRecord(ev.e[3], 0));
+            TD_HIPCHK(hipEventRecord(ev.e[3], 0));
             unsigned long long compares = 0;
-            TNCHK(hipMemcpy(&compares, ctr.p, sizeof compares, hipMemcpyDeviceToHost));
-            for (auto &o : ord) TNCHK(hipMemcpy(&o.ntiles, o.tile_off.p + nrb, sizeof(uint32_t), hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(&compares, ctr.p, sizeof compares, hipMemcpyDeviceToHost));
+            for (auto &o : ord) TD_HIPCHK(hipMemcpy(&o.ntiles, o.tile_off.p + nrb, sizeof(uint32_t), hipMemcpyDeviceToHost));
             st[7] = compares;
             const uint64_t cap_opt = td_handle_tagnet_max_compares(h);
             const uint64_t max_compares = cap_opt ? cap_opt : (uint64_t)TD_TAGNET_DEFAULT_MAX_COMPARES;
@@ -388,20 +357,20 @@ extern "C" int td_tagnet_build(td_handle *h, const char *seqs, const uint64_t *c
             // ---- K4
             const uint64_t bound = (3ull * L * n + 1) / 2;
             const uint64_t ecap = std::min<uint64_t>(bound, compares);
-            TNCHK(deg.alloc(n));
-            TNCHK(hipMemset(deg.p, 0, (uint64_t)n * sizeof(uint32_t)));
-            TNCHK(edges.alloc(ecap));
-            TNCHK(pairs.alloc(n / 2 + 1ull));
+            TD_HIPCHK(deg.alloc(n));
+            TD_HIPCHK(hipMemset(deg.p, 0, (uint64_t)n * sizeof(uint32_t)));
+            TD_HIPCHK(edges.alloc(ecap));
+            TD_HIPCHK(pairs.alloc(n / 2 + 1ull));
             for (auto &o : ord) {
                 if (!o.ntiles) continue;
                 hipLaunchKernelGGL(k_tn_compare, dim3(o.ntiles), dim3(TN_TILE), 0, 0, o.other.p, o.cnt.p, o.idx.p, o.end.p,
                                    o.tile_off.p, nrb, n, ratio_ppm, edges.p, ecap, ctr.p + 1, deg.p, flags.p + 2);
-                TNCHK(hipGetLastError());
+                TD_HIPCHK(hipGetLastError());
             }
-            TNCHK(hipEventRecord(ev.e[4], 0));
+            TD_HIPCHK(hipEventRecord(ev.e[4], 0));
             unsigned long long nedges = 0;
-            TNCHK(hipMemcpy(&nedges, ctr.p + 1, sizeof nedges, hipMemcpyDeviceToHost));
-            TNCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(&nedges, ctr.p + 1, sizeof nedges, hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
             if (fl[2] || nedges > ecap)
                 return td_fail_internal(TD_E_INTERNAL, ("tag network: " + std::to_string(nedges) + " edges, more than the bound of " +
                                                         std::to_string(ecap)).c_str());
@@ -409,26 +378,26 @@ extern "C" int td_tagnet_build(td_handle *h, const char *seqs, const uint64_t *c
             if (nedges) {
                 hipLaunchKernelGGL(k_tn_select, dim3((uint32_t)((nedges + 255) / 256)), block, 0, 0, edges.p, (uint64_t)nedges, deg.p,
                                    pairs.p, n / 2 + 1ull, ctr.p + 2, flags.p + 2);
-                TNCHK(hipGetLastError());
+                TD_HIPCHK(hipGetLastError());
             }
-            TNCHK(hipEventRecord(ev.e[5], 0));
-            TNCHK(hipEventSynchronize(ev.e[5]));
+            TD_HIPCHK(hipEventRecord(ev.e[5], 0));
+            TD_HIPCHK(hipEventSynchronize(ev.e[5]));
             unsigned long long npairs = 0;
-            TNCHK(hipMemcpy(&npairs, ctr.p + 2, sizeof npairs, hipMemcpyDeviceToHost));
-            TNCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(&npairs, ctr.p + 2, sizeof npairs, hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(fl, flags.p, sizeof fl, hipMemcpyDeviceToHost));
             if (fl[2] || npairs > n / 2)
                 return td_fail_internal(TD_E_INTERNAL, "tag network: more pairs than half the tags");
             const auto t0 = std::chrono::steady_clock::now();
             net->edges.resize(nedges);
             net->pairs.resize(npairs);
-            if (nedges) TNCHK(hipMemcpy(net->edges.data(), edges.p, nedges * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            if (npairs) TNCHK(hipMemcpy(net->pairs.data(), pairs.p, npairs * sizeof(uint64_t), hipMemcpyDeviceToHost));
-            TNCHK(hipMemcpy(net->deg.data(), deg.p, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (nedges) TD_HIPCHK(hipMemcpy(net->edges.data(), edges.p, nedges * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (npairs) TD_HIPCHK(hipMemcpy(net->pairs.data(), pairs.p, npairs * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            TD_HIPCHK(hipMemcpy(net->deg.data(), deg.p, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
             std::sort(net->edges.begin(), net->edges.end(), tn_less);
             std::sort(net->pairs.begin(), net->pairs.end());
             if (ms) {
                 ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-                for (int k = 0; k < 5; ++k) ms[k] = tn_elapsed(ev.e[k], ev.e[k + 1]);
+                for (int k = 0; k < 5; ++k) ms[k] = ev.elapsed(k, k + 1);
             }
             st[1] = nedges;
             st[6] = npairs;
@@ -436,8 +405,8 @@ extern "C" int td_tagnet_build(td_handle *h, const char *seqs, const uint64_t *c
             for (uint64_t e : net->edges) st[2] += e >> 63;
             for (uint32_t d : net->deg) st[d == 0 ? 3 : d == 1 ? 4 : 5] += 1;
         } else {
-            TNCHK(hipEventSynchronize(ev.e[1]));
-            if (ms) ms[0] = tn_elapsed(ev.e[0], ev.e[1]);
+            TD_HIPCHK(hipEventSynchronize(ev.e[1]));
+            if (ms) ms[0] = ev.elapsed(0, 1);
         }
     }
     if (stats) for (int k = 0; k < 8; ++k) stats[k] = st[k];

@@ -20,14 +20,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tagdig.h"
 #include "radix_sort.hpp"
-
-// tagdig.hip (not exported): the library's error slot and the handle's device
-extern "C" {
-__attribute__((visibility("hidden"))) int td_fail_internal(int code, const char *msg);
-__attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h);
-}
+#include "td_internal.hpp"
 
 struct td_tagset {
     int device;
@@ -38,25 +32,7 @@ struct td_tagset {
 
 namespace {
 
-#define TSCHK(call)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
 constexpr int TS_MAXW = TD_TAGSET_MAX_LEN / 32;   // 8 words
-
-template <typename T> struct TsBuf {
-    T *p = nullptr;
-    ~TsBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
-struct TsEvents {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~TsEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 // ------------------------------------------------------------------ K1
 __device__ __forceinline__ uint32_t ts_code(uint32_t c, bool *bad) {
@@ -282,35 +258,30 @@ int ts_check_tags(const uint64_t *offs, uint32_t n, uint32_t *maxlen) {
 }
 
 // upload n tags and pack them (K1); W words per key
-int ts_pack(const char *seqs, const uint64_t *offs, uint32_t n, uint32_t W, TsBuf<uint8_t> &dseq, TsBuf<uint64_t> &doff,
-            TsBuf<uint64_t> &key, TsBuf<uint16_t> &len, TsBuf<uint32_t> &bad) {
+int ts_pack(const char *seqs, const uint64_t *offs, uint32_t n, uint32_t W, tdi::DevBuf<uint8_t> &dseq, tdi::DevBuf<uint64_t> &doff,
+            tdi::DevBuf<uint64_t> &key, tdi::DevBuf<uint16_t> &len, tdi::DevBuf<uint32_t> &bad) {
     const uint64_t nbytes = offs[n] - offs[0];
-    TSCHK(dseq.alloc(nbytes));
-    TSCHK(doff.alloc(n + 1ull));
-    TSCHK(key.alloc((uint64_t)W * n));
-    TSCHK(len.alloc(n));
-    TSCHK(bad.alloc(1));
-    if (nbytes) TSCHK(hipMemcpy(dseq.p, seqs + offs[0], nbytes, hipMemcpyHostToDevice));
+    TD_HIPCHK(dseq.alloc(nbytes));
+    TD_HIPCHK(doff.alloc(n + 1ull));
+    TD_HIPCHK(key.alloc((uint64_t)W * n));
+    TD_HIPCHK(len.alloc(n));
+    TD_HIPCHK(bad.alloc(1));
+    if (nbytes) TD_HIPCHK(hipMemcpy(dseq.p, seqs + offs[0], nbytes, hipMemcpyHostToDevice));
     std::vector<uint64_t> rel(n + 1ull);
     for (uint64_t i = 0; i <= n; ++i) rel[i] = offs[i] - offs[0];
-    TSCHK(hipMemcpy(doff.p, rel.data(), (n + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    TSCHK(hipMemset(bad.p, 0xff, sizeof(uint32_t)));
+    TD_HIPCHK(hipMemcpy(doff.p, rel.data(), (n + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemset(bad.p, 0xff, sizeof(uint32_t)));
     if (n) hipLaunchKernelGGL(k_tag_pack, dim3((n + 255) / 256), dim3(256), 0, 0, dseq.p, doff.p, n, W, key.p, len.p, bad.p);
-    TSCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     return TD_OK;
 }
 
-int ts_bad(const TsBuf<uint32_t> &bad) {
+int ts_bad(const tdi::DevBuf<uint32_t> &bad) {
     uint32_t b = 0;
-    TSCHK(hipMemcpy(&b, bad.p, sizeof b, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(&b, bad.p, sizeof b, hipMemcpyDeviceToHost));
     if (b != 0xffffffffu)
         return td_fail_internal(TD_E_ALPHABET, ("tag " + std::to_string(b) + " holds a byte outside ACGT").c_str());
     return TD_OK;
-}
-
-float ts_elapsed(hipEvent_t a, hipEvent_t b) {
-    float f = 0;
-    return hipEventElapsedTime(&f, a, b) == hipSuccess ? f : 0.0f;
 }
 
 }  // namespace
@@ -333,53 +304,47 @@ extern "C" int td_tagset_load(td_handle *h, const char *seqs, const uint64_t *of
         }
     }
     const uint32_t W = std::max<uint32_t>(1, (maxlen + 31) / 32);
-    TSCHK(hipSetDevice(td_handle_device(h)));
-    TsEvents ev;
-    for (auto &e : ev.e) TSCHK(hipEventCreate(&e));
-    TsBuf<uint8_t> dseq;
-    TsBuf<uint64_t> doff, key;
-    TsBuf<uint16_t> len;
-    TsBuf<uint32_t> bad, perm0, perm1, differ, hist;
-    TSCHK(hipEventRecord(ev.e[0], 0));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    tdi::Events<4> ev;
+    TD_HIPCHK(ev.create());
+    tdi::DevBuf<uint8_t> dseq;
+    tdi::DevBuf<uint64_t> doff, key;
+    tdi::DevBuf<uint16_t> len;
+    tdi::DevBuf<uint32_t> bad, perm0, perm1, differ, hist;
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     if ((rc = ts_pack(seqs, offs, n, W, dseq, doff, key, len, bad))) return rc;
-    TSCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
     if ((rc = ts_bad(bad))) return rc;
 
-    TSCHK(perm0.alloc(n));
-    TSCHK(perm1.alloc(n));
-    TSCHK(differ.alloc(3));
+    TD_HIPCHK(perm0.alloc(n));
+    TD_HIPCHK(perm1.alloc(n));
+    TD_HIPCHK(differ.alloc(3));
     std::vector<uint32_t> init(n);
     for (uint32_t i = 0; i < n; ++i) init[i] = order ? order[i] : i;
-    if (n) TSCHK(hipMemcpy(perm0.p, init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    TSCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
-    TSCHK(hipEventRecord(ev.e[2], 0));
+    if (n) TD_HIPCHK(hipMemcpy(perm0.p, init.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemset(differ.p, 0, 3 * sizeof(uint32_t)));
+    TD_HIPCHK(hipEventRecord(ev.e[2], 0));
     uint32_t npass = 0;
     if (n > 1) {
-        TSCHK(hist.alloc(256ull * tdrs::rs_blocks(n)));
-        TSCHK(tdrs::rs_sort(key.p, len.p, n, W, &perm0.p, &perm1.p, differ.p, hist.p, &npass));
+        TD_HIPCHK(hist.alloc(256ull * tdrs::rs_blocks(n)));
+        TD_HIPCHK(tdrs::rs_sort(key.p, len.p, n, W, &perm0.p, &perm1.p, differ.p, hist.p, &npass));
     }
-    td_tagset *s = new td_tagset{td_handle_device(h), n, W, nullptr, nullptr};
-    hipError_t e1 = hipMalloc(&s->key, std::max<size_t>(1, (size_t)W * n) * sizeof(uint64_t));
-    hipError_t e2 = hipMalloc(&s->len, std::max<size_t>(1, n) * sizeof(uint16_t));
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        td_tagset_free(h, s);
-        return td_fail_internal(TD_E_HIP, "hipMalloc of the sorted set failed");
-    }
-    if (n) hipLaunchKernelGGL(k_rs_gather, dim3((n + 255) / 256), dim3(256), 0, 0, key.p, len.p, perm0.p, n, W, s->key, s->len);
+    tdi::DevBuf<uint64_t> skey;                    // the sorted set: the caller's once everything has succeeded
+    tdi::DevBuf<uint16_t> slen;
+    const hipError_t e1 = skey.alloc((size_t)W * n), e2 = slen.alloc(n);
+    if (e1 != hipSuccess || e2 != hipSuccess) return td_fail_internal(TD_E_HIP, "hipMalloc of the sorted set failed");
+    if (n) hipLaunchKernelGGL(k_rs_gather, dim3((n + 255) / 256), dim3(256), 0, 0, key.p, len.p, perm0.p, n, W, skey.p, slen.p);
     hipError_t e3 = hipGetLastError();
     if (e3 == hipSuccess) e3 = hipEventRecord(ev.e[3], 0);
     if (e3 == hipSuccess) e3 = hipEventSynchronize(ev.e[3]);
     if (e3 == hipSuccess && n) e3 = hipMemcpy(perm_out, perm0.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e3 != hipSuccess) {
-        td_tagset_free(h, s);
-        return td_fail_internal(TD_E_HIP, (std::string("td_tagset_load: ") + hipGetErrorString(e3)).c_str());
-    }
+    if (e3 != hipSuccess) return td_fail_internal(TD_E_HIP, (std::string("td_tagset_load: ") + hipGetErrorString(e3)).c_str());
     if (ms) {
-        ms[0] = ts_elapsed(ev.e[0], ev.e[1]);
-        ms[1] = ts_elapsed(ev.e[2], ev.e[3]);
+        ms[0] = ev.elapsed(0, 1);
+        ms[1] = ev.elapsed(2, 3);
     }
     if (passes) *passes = npass;
-    *out = s;
+    *out = new td_tagset{td_handle_device(h), n, W, skey.release(), slen.release()};
     return TD_OK;
 }
 
@@ -403,25 +368,25 @@ extern "C" int td_tagset_lookup(td_handle *h, const td_tagset *s, const char *se
     if (rc) return rc;
     if (!nq) return TD_OK;
     const uint32_t Wq = std::max<uint32_t>(1, (maxlen + 31) / 32);
-    TSCHK(hipSetDevice(s->device));
-    TsEvents ev;
-    for (auto &e : ev.e) TSCHK(hipEventCreate(&e));
-    TsBuf<uint8_t> dseq;
-    TsBuf<uint64_t> doff, key;
-    TsBuf<uint16_t> len;
-    TsBuf<uint32_t> bad;
-    TsBuf<int4> dout;
+    TD_HIPCHK(hipSetDevice(s->device));
+    tdi::Events<4> ev;
+    TD_HIPCHK(ev.create());
+    tdi::DevBuf<uint8_t> dseq;
+    tdi::DevBuf<uint64_t> doff, key;
+    tdi::DevBuf<uint16_t> len;
+    tdi::DevBuf<uint32_t> bad;
+    tdi::DevBuf<int4> dout;
     if ((rc = ts_pack(seqs, offs, nq, Wq, dseq, doff, key, len, bad))) return rc;
     if ((rc = ts_bad(bad))) return rc;
-    TSCHK(dout.alloc(nq));
-    TSCHK(hipEventRecord(ev.e[0], 0));
+    TD_HIPCHK(dout.alloc(nq));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     hipLaunchKernelGGL(k_tag_lookup, dim3((nq + 255) / 256), dim3(256), 0, 0, s->key, s->len, s->n, s->W, key.p, len.p, nq, Wq,
                        allow_diff_lengths ? 1 : 0, dout.p);
-    TSCHK(hipGetLastError());
-    TSCHK(hipEventRecord(ev.e[1], 0));
-    TSCHK(hipEventSynchronize(ev.e[1]));
-    if (ms) *ms = ts_elapsed(ev.e[0], ev.e[1]);
-    TSCHK(hipMemcpy(out, dout.p, nq * sizeof(int4), hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
+    if (ms) *ms = ev.elapsed(0, 1);
+    TD_HIPCHK(hipMemcpy(out, dout.p, nq * sizeof(int4), hipMemcpyDeviceToHost));
     return TD_OK;
 }
 
@@ -442,34 +407,34 @@ extern "C" int td_tagset_varsites(td_handle *h, const char *seqs, const uint64_t
     if (!idx) return td_fail_internal(TD_E_ARG, "NULL argument");
     for (uint64_t t = 0; t < nidx; ++t)
         if (idx[t] >= ntags) return td_fail_internal(TD_E_ARG, "tag index out of range");
-    TSCHK(hipSetDevice(td_handle_device(h)));
-    TsEvents ev;
-    for (int i = 0; i < 2; ++i) TSCHK(hipEventCreate(&ev.e[i]));
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    tdi::Events<2> ev;
+    TD_HIPCHK(ev.create());
     const uint64_t nbytes = offs[ntags] - offs[0];
-    TsBuf<uint8_t> dseq, dbad;
-    TsBuf<uint64_t> doff, dgoff, dmask;
-    TsBuf<uint32_t> didx;
-    TSCHK(dseq.alloc(nbytes));
-    TSCHK(doff.alloc(ntags + 1ull));
-    TSCHK(didx.alloc(nidx));
-    TSCHK(dgoff.alloc(ngroups + 1ull));
-    TSCHK(dmask.alloc(4ull * ngroups));
-    TSCHK(dbad.alloc(ngroups));
-    if (nbytes) TSCHK(hipMemcpy(dseq.p, seqs + offs[0], nbytes, hipMemcpyHostToDevice));
+    tdi::DevBuf<uint8_t> dseq, dbad;
+    tdi::DevBuf<uint64_t> doff, dgoff, dmask;
+    tdi::DevBuf<uint32_t> didx;
+    TD_HIPCHK(dseq.alloc(nbytes));
+    TD_HIPCHK(doff.alloc(ntags + 1ull));
+    TD_HIPCHK(didx.alloc(nidx));
+    TD_HIPCHK(dgoff.alloc(ngroups + 1ull));
+    TD_HIPCHK(dmask.alloc(4ull * ngroups));
+    TD_HIPCHK(dbad.alloc(ngroups));
+    if (nbytes) TD_HIPCHK(hipMemcpy(dseq.p, seqs + offs[0], nbytes, hipMemcpyHostToDevice));
     std::vector<uint64_t> rel(ntags + 1ull);
     for (uint64_t i = 0; i <= ntags; ++i) rel[i] = offs[i] - offs[0];
-    TSCHK(hipMemcpy(doff.p, rel.data(), (ntags + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    TSCHK(hipMemcpy(didx.p, idx, nidx * sizeof(uint32_t), hipMemcpyHostToDevice));
-    TSCHK(hipMemcpy(dgoff.p, goff, (ngroups + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    TSCHK(hipEventRecord(ev.e[0], 0));
+    TD_HIPCHK(hipMemcpy(doff.p, rel.data(), (ntags + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(didx.p, idx, nidx * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(dgoff.p, goff, (ngroups + 1ull) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TD_HIPCHK(hipEventRecord(ev.e[0], 0));
     const uint32_t grid = (ngroups + 3) / 4;
     hipLaunchKernelGGL(k_tag_varsites, dim3(grid), dim3(256), 0, 0, dseq.p, doff.p, didx.p, dgoff.p, ngroups, ntags, trim ? 1 : 0,
                        dmask.p, dbad.p);
-    TSCHK(hipGetLastError());
-    TSCHK(hipEventRecord(ev.e[1], 0));
-    TSCHK(hipEventSynchronize(ev.e[1]));
-    if (ms) *ms = ts_elapsed(ev.e[0], ev.e[1]);
-    TSCHK(hipMemcpy(mask_out, dmask.p, 4ull * ngroups * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    TSCHK(hipMemcpy(nonacgt_out, dbad.p, ngroups, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipEventRecord(ev.e[1], 0));
+    TD_HIPCHK(hipEventSynchronize(ev.e[1]));
+    if (ms) *ms = ev.elapsed(0, 1);
+    TD_HIPCHK(hipMemcpy(mask_out, dmask.p, 4ull * ngroups * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(nonacgt_out, dbad.p, ngroups, hipMemcpyDeviceToHost));
     return TD_OK;
 }

@@ -1,0 +1,95 @@
+// What the library's translation units share on the host side and the C-ABI does not show ("The modules
+// beside tagdig.hip"): the hooks into the handle that tagdig.hip and census.hip define, the check macro for HIP calls,
+// and the owners of the device buffers, pinned buffers and events that an entry point holds while it runs.  Every
+// module beside tagdig.hip includes this header; tagdig.hip and census.hip include it too, so that a hook's definition
+// is checked against the declaration its callers see.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/tagdig.h"
+
+struct td_piece_sink;                             // piece_sink.hpp
+
+#define TD_HIDDEN __attribute__((visibility("hidden")))
+extern "C" {
+// tagdig.hip: the calling thread's error slot (returns `code`) and the index td_last_bad_index reports
+TD_HIDDEN int td_fail_internal(int code, const char *msg);
+TD_HIDDEN void td_set_bad_index(uint32_t idx);
+// tagdig.hip: the handle's device, work stream and CU count; its options "md5_piece" and "tagnet_max_compares"; the
+// number of staging threads
+TD_HIDDEN int td_handle_device(const td_handle *h);
+TD_HIDDEN void *td_handle_work_stream(const td_handle *h);
+TD_HIDDEN int td_handle_num_cu(const td_handle *h);
+TD_HIDDEN uint64_t td_handle_md5_piece(const td_handle *h);
+TD_HIDDEN uint64_t td_handle_tagnet_max_compares(const td_handle *h);
+TD_HIDDEN int td_stage_thread_count(void);
+// tagdig.hip: every launch enqueued through this handle (they may be on its own streams) has finished
+TD_HIDDEN int td_handle_wait_work(td_handle *h);
+// tagdig.hip, for census.hip: the census' place on the handle; the barcode + cut-site index by td_set_index's rules
+// (*blob_out is malloc'ed); terminators before the end of every 16 KiB tile -> *prefix (the handle's scratch, good until
+// its next launch), their total -> *d_total, asynchronous on `s`; a file's pieces through the handle's readers to `sink`
+TD_HIDDEN void **td_handle_census(td_handle *h);
+TD_HIDDEN int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff, uint8_t **blob_out,
+                             uint32_t *bytes, uint32_t *off_bmeta, uint32_t *off_bdir);
+TD_HIDDEN int td_line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, void *s, const uint64_t **prefix, unsigned long long *d_total);
+TD_HIDDEN int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink);
+// census.hip, for td_destroy: frees the handle's census, if any
+TD_HIDDEN void td_census_release(td_handle *h);
+}
+
+// a failed HIP call ends the calling function with TD_E_HIP and "<the call as written>: <HIP's text>"
+#define TD_HIPCHK(call)                                                                      \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return td_fail_internal(TD_E_HIP, (std::string(#call) + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
+
+namespace [[gnu::visibility("hidden")]] tdi {
+
+// max(n, 1) elements of device memory, freed with the object unless released
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)); }
+    T *release() { T *q = p; p = nullptr; return q; }
+};
+
+// the same in pinned host memory
+template <typename T> struct PinBuf {
+    T *p = nullptr;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t n) { return hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault); }
+};
+
+// N events, destroyed with the object
+template <int N> struct Events {
+    hipEvent_t e[N] = {};
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipError_t create() {                         // in order; stops at the first error
+        for (hipEvent_t &x : e) {
+            const hipError_t err = hipEventCreate(&x);
+            if (err != hipSuccess) return err;
+        }
+        return hipSuccess;
+    }
+    float elapsed(int a, int b) const {           // device ms from e[a] to e[b], both completed (0 where HIP cannot tell)
+        float f = 0;
+        return hipEventElapsedTime(&f, e[a], e[b]) == hipSuccess ? f : 0.0f;
+    }
+};
+
+}  // namespace tdi

@@ -7,6 +7,7 @@ lists to libtagdig (td_set_index), which builds the flat device index.  The
 record loop (:239-277) runs on the GPU.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 import math
@@ -504,7 +505,7 @@ class Engine:
         rc = self._L.td_tagnet_build(self._h, buf.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), n, int(taglen),
                                      int(ratio_ppm), C.byref(out), st, ms)
         if rc:
-            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err = self._error(rc)
             err.bad_index = self._L.td_last_bad_index() if rc in (-3, -6) else None
             err.stats = dict(zip(TAGNET_STATS, (int(x) for x in st)))
             raise err
@@ -539,6 +540,49 @@ class Engine:
     def tagnet_free(self, net):
         net.close()
 
+    # ------------------------------------------------------------------ what the matrix calls below share
+    @contextlib.contextmanager
+    def _device_matrix(self, matrix, shape, dtype, columns, none_ok=True):
+        """(device pointer, rows, columns) of an input matrix: a device pointer (None or 0 where none_ok: a null
+        pointer) with shape=(rows, columns), taken where it lies, or a host matrix of `dtype` (uint8, or uint32 by
+        counts_as_uint32), uploaded and freed on exit.  `columns` names the second axis in the messages."""
+        import numpy as np
+        if isinstance(matrix, int) or (none_ok and matrix is None):
+            if shape is None:
+                raise ValueError("a device pointer needs shape=(samples, {})".format(columns))
+            rows, cols = (int(x) for x in shape)
+            yield matrix or 0, rows, cols
+            return
+        if dtype == np.uint32:
+            host = counts_as_uint32(matrix)
+        else:
+            host = np.ascontiguousarray(matrix)
+            if host.ndim != 2 or host.dtype != np.uint8:
+                raise ValueError("the call matrix must be a uint8 matrix (samples x {})".format(columns))
+        d = self.dev_alloc(host.nbytes) if host.size else 0
+        try:
+            if host.size:
+                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d), host.ctypes.data_as(C.c_void_p), host.nbytes))
+            yield (d,) + host.shape
+        finally:
+            if d:
+                self.dev_free(d)
+
+    @staticmethod
+    def _marker_mask(use, M):
+        """The marker mask as M bytes 0 / 1 (a marker takes part iff its entry is not zero); None for none or M == 0."""
+        import numpy as np
+        if use is None:
+            return None
+        use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+        if use.shape != (M,):
+            raise ValueError("use must have one entry per marker")
+        return use if M else None
+
+    def _error(self, rc):
+        """The TagdigError of a call that answered rc, from the library's error slot; the caller adds its attributes."""
+        return B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+
     # ------------------------------------------------------------------ genotype calls (td_geno_call; csrc/genocall.hip)
     def geno_call(self, counts, i0, i1, het_min, shape=None, rule=0, err_ppm=10000, min_depth=1, min_call_ppm=0,
                   min_maf_ppm=0, max_het_ppm=1000000, fetch_calls=True, keep_device=False):
@@ -557,19 +601,7 @@ class Engine:
         if het.shape != (GENO_TABLE,):
             raise ValueError("het_min must have {} entries".format(GENO_TABLE))
         M = len(i0)
-        uploaded = None
-        if isinstance(counts, int):
-            if shape is None:
-                raise ValueError("a device pointer needs shape=(samples, tags)")
-            S, T = (int(x) for x in shape)
-            d_counts = counts
-        else:
-            host = counts_as_uint32(counts)
-            S, T = host.shape
-            d_counts = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
-            if host.size:
-                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_counts), host.ctypes.data_as(C.c_void_p), host.nbytes))
-        try:
+        with self._device_matrix(counts, shape, np.uint32, "tags", none_ok=False) as (d_counts, S, T):
             par = B.GenoParams(int(rule), int(err_ppm), int(min_depth), int(min_call_ppm), int(min_maf_ppm), int(max_het_ppm), 0)
             calls = np.zeros((S, M), dtype=np.uint8) if fetch_calls else None
             stats = np.zeros((max(1, M), len(GENO_STATS)), dtype=np.uint64)
@@ -582,11 +614,8 @@ class Engine:
                                       calls.ctypes.data_as(C.c_void_p) if fetch_calls and calls.size else None,
                                       C.byref(d_calls) if keep_device else None, stats.ctypes.data_as(C.c_void_p),
                                       mask.ctypes.data_as(C.c_void_p), C.byref(passed), C.byref(ms))
-        finally:
-            if uploaded:
-                self.dev_free(uploaded)
         if rc:
-            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err = self._error(rc)
             err.bad_index = self._L.td_last_bad_index() if rc == -2 and err.detail.startswith("marker ") else None
             raise err
         return GenoCalls(calls, {k: stats[:M, j].copy() for j, k in enumerate(GENO_STATS)}, mask[:M].astype(bool),
@@ -601,27 +630,8 @@ class Engine:
         fetch=False leaves the table on the device; keep_device=True hands its device buffer out as `.d_joint`.
         Returns a RelateJoint.  A failure raises TagdigError."""
         import numpy as np
-        uploaded = None
-        if calls is None or isinstance(calls, int):
-            if shape is None:
-                raise ValueError("a device pointer needs shape=(samples, markers)")
-            S, M = (int(x) for x in shape)
-            d_calls = calls or 0
-        else:
-            host = np.ascontiguousarray(calls)
-            if host.ndim != 2 or host.dtype != np.uint8:
-                raise ValueError("the call matrix must be a uint8 matrix (samples x markers)")
-            S, M = host.shape
-            d_calls = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
-            if host.size:
-                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_calls), host.ctypes.data_as(C.c_void_p), host.nbytes))
-        try:
-            if use is not None:
-                use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
-                if use.shape != (M,):
-                    raise ValueError("use must have one entry per marker")
-                if not M:
-                    use = None
+        with self._device_matrix(calls, shape, np.uint8, "markers") as (d_calls, S, M):
+            use = self._marker_mask(use, M)
             in_range = S <= RELATE_MAX_SAMPLES and M < 1 << 31     # (the library answers TD_E_ARG otherwise)
             joint = np.zeros((S, S, 3, 3), dtype=np.uint32) if fetch and in_range else None
             ms, d_joint = C.c_double(0), C.c_void_p()
@@ -629,9 +639,6 @@ class Engine:
                                          use.ctypes.data_as(C.c_void_p) if use is not None else None,
                                          joint.ctypes.data_as(C.c_void_p) if joint is not None and joint.size else None,
                                          C.byref(d_joint) if keep_device else None, C.byref(ms))
-        finally:
-            if uploaded:
-                self.dev_free(uploaded)
         B.check(rc)
         return RelateJoint(joint, ms.value, d_joint.value if keep_device else None)
 
@@ -647,27 +654,8 @@ class Engine:
         `.degree` and `.called`.  count_only=True passes no buffer: no edges, but n, degree and called.  Returns an
         LDPairs.  A failure raises TagdigError."""
         import numpy as np
-        uploaded = None
-        if calls is None or isinstance(calls, int):
-            if shape is None:
-                raise ValueError("a device pointer needs shape=(samples, markers)")
-            S, M = (int(x) for x in shape)
-            d_calls = calls or 0
-        else:
-            host = np.ascontiguousarray(calls)
-            if host.ndim != 2 or host.dtype != np.uint8:
-                raise ValueError("the call matrix must be a uint8 matrix (samples x markers)")
-            S, M = host.shape
-            d_calls = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
-            if host.size:
-                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_calls), host.ctypes.data_as(C.c_void_p), host.nbytes))
-        try:
-            if use is not None:
-                use = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
-                if use.shape != (M,):
-                    raise ValueError("use must have one entry per marker")
-                if not M:
-                    use = None
+        with self._device_matrix(calls, shape, np.uint8, "markers") as (d_calls, S, M):
+            use = self._marker_mask(use, M)
             in_range = M < 1 << 31                               # (the library answers TD_E_ARG otherwise)
             degree = np.zeros(max(1, M if in_range else 1), dtype=np.uint32)
             called = np.zeros(max(1, M if in_range else 1), dtype=np.uint32)
@@ -684,11 +672,8 @@ class Engine:
                     capacity = n.value
                     continue
                 break
-        finally:
-            if uploaded:
-                self.dev_free(uploaded)
         if rc:
-            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err = self._error(rc)
             err.n, err.degree, err.called = n.value, degree[:M], called[:M]
             raise err
         t = (C.c_double * 3)()
@@ -708,21 +693,7 @@ class Engine:
         nbr = np.ascontiguousarray(nbr, dtype=np.int32)
         if nbr.ndim != 2:
             raise ValueError("the neighbour table must have two dimensions (markers x neighbours)")
-        uploaded = None
-        if calls is None or isinstance(calls, int):
-            if shape is None:
-                raise ValueError("a device pointer needs shape=(samples, markers)")
-            S, M = (int(x) for x in shape)
-            d_calls = calls or 0
-        else:
-            host = np.ascontiguousarray(calls)
-            if host.ndim != 2 or host.dtype != np.uint8:
-                raise ValueError("the call matrix must be a uint8 matrix (samples x markers)")
-            S, M = host.shape
-            d_calls = uploaded = self.dev_alloc(host.nbytes) if host.size else 0
-            if host.size:
-                B.check(self._L.td_memcpy_h2d(self._h, C.c_void_p(d_calls), host.ctypes.data_as(C.c_void_p), host.nbytes))
-        try:
+        with self._device_matrix(calls, shape, np.uint8, "markers") as (d_calls, S, M):
             in_range = S <= IMPUTE_MAX_SAMPLES and M < 1 << 31     # (the library answers TD_E_ARG otherwise)
             if in_range and nbr.shape[0] != M:
                 raise ValueError("the neighbour table must have one row per marker")
@@ -734,11 +705,8 @@ class Engine:
                                        nbr.ctypes.data_as(C.c_void_p) if nbr.size else None, C.byref(par),
                                        out.ctypes.data_as(C.c_void_p) if out is not None and out.size else None,
                                        C.byref(d_out) if keep_device else None, stats.ctypes.data_as(C.c_void_p), C.byref(ms))
-        finally:
-            if uploaded:
-                self.dev_free(uploaded)
         if rc:
-            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err = self._error(rc)
             err.bad_index = self._L.td_last_bad_index() if rc == -2 and err.detail.startswith("neighbours of marker ") else None
             raise err
         t = (C.c_double * 2)()
@@ -866,7 +834,7 @@ class Engine:
         bad, ms = C.c_uint32(0), (C.c_double * 3)()
         rc = self._L.td_md5_files(self._h, arr, n, out.ctypes.data_as(C.c_void_p), C.byref(bad), ms)
         if rc == -11:
-            err = B.TagdigError(rc, (self._L.td_last_error() or b"").decode("utf-8", "replace"))
+            err = self._error(rc)
             err.bad_index = bad.value
             raise err
         B.check(rc)

@@ -289,3 +289,22 @@ def test_cli_impute_from_tag_calls(tmp_path, capsys):
         data = [open(f[k], "rb").read() for k in names]
         assert all(d == data[0] for d in data) and data[0].count(b"\n") > 2, names
     assert open(f["imp1.csv"], "rb").read() != open(f["calls1.csv"], "rb").read()
+
+
+def test_shared_transpose_counts_the_called_samples(eng):
+    """k_calls_transpose (csrc/calls_transpose.hpp) is one kernel with two instantiations: td_ld_pairs gathers the
+    participating columns through the mask's index list, td_impute_knn takes every column.  Both count the samples called
+    per marker in the same pass; the three ways to ask for that number agree with numpy at the tile and step tails of
+    both axes.  (A table of -1 makes k_impute leave at once after its statistics: the pre-pass alone is exercised.)"""
+    rng = np.random.default_rng(20261019)
+    codes = np.array([0, 1, 2, 3, 9, 255], dtype=np.uint8)
+    for S in (1, 63, 64, 65):
+        for M in (2, 63, 64, 65, 130):
+            calls = codes[rng.integers(0, len(codes), size=(S, M))]
+            want = (calls <= 2).sum(axis=0)
+            keep = np.arange(M) % 3 != 2                           # drops every third marker; at least two stay
+            assert np.array_equal(eng.ld_pairs(calls, count_only=True).called, want), (S, M)
+            masked = eng.ld_pairs(calls, use=keep, count_only=True).called
+            assert np.array_equal(masked[keep], want[keep]) and not masked[~keep].any(), (S, M)
+            stats = eng.impute_knn(calls, np.full((M, 1), -1, dtype=np.int32)).stats
+            assert np.array_equal(S - stats[:, 0].astype(np.int64), want), (S, M)

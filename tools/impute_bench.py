@@ -55,7 +55,7 @@ def main(argv=None):
 
     kw = dict(l=20, k=10, min_overlap=4, min_conf=0.6, min_r2=0.5, ld_min_shared=50)
     say("LD-kNN imputation, tools/impute_bench.py; l 20, k 10, min_overlap 4, min_conf 0.6, neighbours at r^2 >= 0.5 over >= 50 samples")
-    say("device ms: HIP events around k_imp_transpose and k_impute inside td_impute_knn")
+    say("device ms: HIP events around k_calls_transpose<false> and k_impute inside td_impute_knn")
     for shape in args.shapes.split(","):
         S, M = (int(x) for x in shape.split("x"))
         calls = structured(rng, S, M)

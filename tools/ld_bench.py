@@ -64,7 +64,7 @@ def main(argv=None):
         lines.append(text)
 
     clock = args.clock_ghz or 2.4
-    say("marker LD, tools/ld_bench.py; TILE %d; device ms: HIP events around k_ld_transpose and k_ld_pairs inside td_ld_pairs" % LD_TILE)
+    say("marker LD, tools/ld_bench.py; TILE %d; device ms: HIP events around k_calls_transpose<true> and k_ld_pairs inside td_ld_pairs" % LD_TILE)
     say("MFMA floor at %.3f GHz %s" % (clock, "(measured under k_relate's int8 MFMA loop, tools/relate_clock.hip)" if args.clock_ghz else
                                        "(the specification's clock: the clock under load was NOT measured)"))
 
