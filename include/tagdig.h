@@ -622,6 +622,53 @@ int td_impute_knn(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, con
                   void **d_calls_out /* or NULL; the caller's, td_dev_free */, uint32_t *stats_out /* HOST, M*4, or NULL */, double *ms);
 int td_impute_last_times(td_handle *h, double *out2 /* transpose ms, vote kernel ms of this thread's last td_impute_knn */);
 
+/* ---- parent pairs by Mendelian trio counts (csrc/parent.hip; tagdigger_amd/tagdigger_fun.py parentage drives it) --------
+ *
+ * Which two samples are the parents of this one.  d_calls, the codes and use are those of
+ * td_relate_joint: S x M uint8, row-major, in DEVICE memory, rows exactly M bytes apart, 0 / 1 / 2 copies of allele 1, ANY
+ * byte above 2 missing; marker m takes part iff use == NULL or use[m] != 0 (HOST, M bytes).  offspring (HOST, O sample
+ * indices) names the rows of the job; cand (HOST, O x C int32) gives row i its candidate slots 0 .. C - 1: a sample index
+ * or -1 (an empty slot, anywhere in the row), never the row's own offspring, none twice in a row.  The rule, in integers
+ * only.  TRIO COUNT: for an offspring o and two parents p, q, over the participating markers at which all three are called,
+ *   n = their number,
+ *   e = those among them at which the offspring's call is not one that parents (p, q) can produce; the allowed sets are
+ *       (0,0) -> {0}, (0,1) -> {0,1}, (0,2) -> {1}, (1,1) -> {0,1,2}, (1,2) -> {1,2}, (2,2) -> {2}, symmetric in the parents.
+ * With the one-hot bit planes C (called and used), H0, H1, H2 of 64 markers a word this is
+ *   n = popc(Co & Cp & Cq),  e = popc(Cp & Cq & ((o2 & (p0 | q0)) | (o0 & (p2 | q2)) | (o1 & ((p0 & q0) | (p2 & q2))))).
+ * TRIO NUMBERING: the trios of a row are its slot pairs (a, b), a <= b with TD_PARENT_SELFING in flags and a < b without,
+ * numbered t = 0 .. T - 1 row-major, a ascending, then b ascending: T = C (C + 1) / 2 or C (C - 1) / 2.  A pair with an
+ * empty slot has n = e = 0.  RANKING: only trios with n >= min_shared are ranked (min_shared >= 1).  Trio x comes before
+ * trio y iff e_x n_y < e_y n_x (64-bit products; n, e < 2^31); if those are equal the larger n comes first; if those are
+ * equal too the lower t.
+ * best_out (HOST, O x K records) receives the first K ranked trios of every row, p = cand[a], q = cand[b]; where fewer than
+ * K rank the rest are p = q = 0xFFFFFFFF, n = e = 0.  table_out (optional, HOST, O x T x 2 uint32) receives (n, e) of every
+ * trio.  Accumulators are 32 bits wide (M < 2^31), every (n, e) is written exactly once and nothing is combined with
+ * atomics: the same bytes on every run.  ms (optional): device time of the three kernels; td_parent_last_times gives the
+ * pack, trio and rank kernel of the CALLING THREAD's last td_parent_trios apart.  No byte beyond calls[S M - 1] or
+ * use[M - 1] is read.
+ * Synchronous; waits for the work enqueued through this handle first.  Checked before anything is read on the device,
+ * allocated or launched, TD_E_ARG each: S <= TD_PARENT_MAX_SAMPLES, M < 2^31, C in 1 .. TD_PARENT_MAX_CAND, K in
+ * 1 .. TD_PARENT_MAX_TOP, min_shared >= 1, no flag bit but TD_PARENT_SELFING, no NULL matrix with S M > 0, no NULL list or
+ * best_out with O > 0, every offspring index below S, every candidate in -1 .. S - 1, not the row's offspring and not named
+ * twice in its row (for a bad offspring or candidate entry td_last_bad_index gives the row and the message the entry).
+ * After that O = 0 succeeds without a launch, and M = 0 gives all-zero tables and unranked records without a launch (S = 0
+ * admits no offspring). */
+enum {
+    TD_PARENT_MAX_SAMPLES = 16384,
+    TD_PARENT_MAX_CAND = 128,
+    TD_PARENT_MAX_TOP = 8,
+    TD_PARENT_BLOCK = 64,     /* candidate slots along a workgroup's block edge (half of it up to 64 candidates) */
+    TD_PARENT_WCHUNK = 16,    /* 64-marker words of the candidates' planes staged in LDS at a time         */
+    TD_PARENT_SELFING = 1     /* flags bit 0: the pairs (a, a) are trios too                              */
+};
+typedef struct td_parent_trio { uint32_t p, q, n, e; } td_parent_trio;   /* 16 bytes; p = cand[a], q = cand[b] */
+int td_parent_trios(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const uint8_t *use /* HOST, M bytes, or NULL */,
+                    const uint32_t *offspring /* HOST, O sample indices */, uint32_t O,
+                    const int32_t *cand /* HOST, O*C, -1 = empty */, uint32_t C, uint32_t flags, uint32_t K, uint32_t min_shared,
+                    td_parent_trio *best_out /* HOST, O*K; p = q = 0xFFFFFFFF, n = e = 0 where fewer than K rank */,
+                    uint32_t *table_out /* HOST, O*T*2 (n, e), or NULL */, double *ms);
+int td_parent_last_times(td_handle *h, double *out3 /* pack, trio, rank: device ms of this thread's last call */);
+
 /* ---- results ---------------------------------------------------------------
  * Both synchronise with all work enqueued through this handle first and
  * return TD_E_NONASCII / TD_E_INTERNAL if a kernel flagged a problem. */

@@ -180,6 +180,8 @@ def load():
     sig("td_ld_last_times", i32, vp, dp)
     sig("td_impute_knn", i32, vp, vp, u32, u32, vp, C.POINTER(ImputeParams), vp, C.POINTER(vp), vp, dp)
     sig("td_impute_last_times", i32, vp, dp)
+    sig("td_parent_trios", i32, vp, vp, u32, u32, vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, dp)
+    sig("td_parent_last_times", i32, vp, dp)
     _lib = L
     return L
 
@@ -201,6 +203,7 @@ EXPORTS = [
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
     "td_geno_call", "td_relate_joint", "td_ld_pairs", "td_ld_last_times",
     "td_impute_knn", "td_impute_last_times",
+    "td_parent_trios", "td_parent_last_times",
 ]
 
 

@@ -146,6 +146,23 @@ class RelateJoint(collections.namedtuple("RelateJoint", "joint ms d_joint")):
     __slots__ = ()
 
 
+PARENT_MAX_SAMPLES = 16384  # TD_PARENT_MAX_SAMPLES
+PARENT_MAX_CAND = 128       # TD_PARENT_MAX_CAND: candidate slots of an offspring row
+PARENT_MAX_TOP = 8          # TD_PARENT_MAX_TOP: ranked trios returned per offspring row
+PARENT_BLOCK = 64           # TD_PARENT_BLOCK: candidate slots along a workgroup's block edge of csrc/parent.hip
+PARENT_WCHUNK = 16          # TD_PARENT_WCHUNK: 64-marker words staged in LDS at a time by csrc/parent.hip
+PARENT_SELFING = 1          # TD_PARENT_SELFING: flags bit 0
+PARENT_TRIO = [("p", "<u4"), ("q", "<u4"), ("n", "<u4"), ("e", "<u4")]    # td_parent_trio
+PARENT_NONE = 0xFFFFFFFF    # p and q of a record where fewer than `top` trios rank
+
+
+class ParentTrios(collections.namedtuple("ParentTrios", "best table ms times")):
+    """What Engine.parent_trios returns: best (structured array [O, top] with the fields of td_parent_trio; p = q =
+    PARENT_NONE where fewer trios rank), table (uint32 [O, T, 2] of (n, e) per trio; None when it was not fetched), ms
+    (device time of the three kernels), times (dict: pack_ms, trio_ms, rank_ms)."""
+    __slots__ = ()
+
+
 LD_MAX_SAMPLES = 16384      # TD_LD_MAX_SAMPLES: cov and var of a pair of markers fit 32 bits
 LD_MAX_MARKERS = 1 << 20    # TD_LD_MAX_MARKERS: participating markers of one call
 LD_TILE = 64                # TD_LD_TILE: markers along a workgroup's tile edge of csrc/ld.hip
@@ -712,6 +729,44 @@ class Engine:
         t = (C.c_double * 2)()
         B.check(self._L.td_impute_last_times(self._h, t))
         return ImputeKnn(out, stats[:M], ms.value, dict(transpose_ms=t[0], vote_ms=t[1]), d_out.value if keep_device else None)
+
+    # ------------------------------------------------------------------ parent pairs (td_parent_trios; csrc/parent.hip)
+    def parent_trios(self, calls, offspring, cand, shape=None, use=None, selfing=True, top=2, min_shared=50, fetch_table=False):
+        """td_parent_trios: for every offspring row and every pair of its candidate slots, n = the participating markers
+        at which offspring and both candidates are called and e = those at which the offspring's call is none the two can
+        produce; the first `top` trios with n >= min_shared by (e / n ascending, n descending, trio number ascending)
+        (include/tagdig.h has the rule).  calls is a numpy uint8 matrix [S, M] (uploaded) or a device pointer with
+        shape=(S, M).  offspring: O sample indices.  cand: int32 [O, C], row i the candidate parents of offspring[i], -1
+        for an empty slot.  use: M bytes, a marker takes part iff its byte is not zero (None: all).  selfing: the pairs
+        (a, a) are trios too.  fetch_table=True brings the whole table to the host as well.  Returns a ParentTrios.  A
+        failure raises TagdigError; `.bad_index` holds the row for a bad offspring or candidate entry."""
+        import numpy as np
+        offspring = np.ascontiguousarray(offspring, dtype=np.uint32)
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        if offspring.ndim != 1 or cand.ndim != 2 or cand.shape[0] != len(offspring):
+            raise ValueError("cand must have one row of candidate slots per offspring")
+        O, Cn, K = len(offspring), cand.shape[1], int(top)
+        with self._device_matrix(calls, shape, np.uint8, "markers") as (d_calls, S, M):
+            use = self._marker_mask(use, M)
+            in_range = 1 <= Cn <= PARENT_MAX_CAND and 1 <= K <= PARENT_MAX_TOP     # (the library answers TD_E_ARG otherwise)
+            T = (Cn * (Cn + 1) // 2 if selfing else Cn * (Cn - 1) // 2) if in_range else 0
+            best = np.zeros((O, K if in_range else 1), dtype=PARENT_TRIO)
+            table = np.zeros((O, T, 2), dtype=np.uint32) if fetch_table else None
+            ms = C.c_double(0)
+            rc = self._L.td_parent_trios(self._h, C.c_void_p(d_calls) if d_calls else None, S, M,
+                                         use.ctypes.data_as(C.c_void_p) if use is not None else None,
+                                         offspring.ctypes.data_as(C.c_void_p) if O else None, O,
+                                         cand.ctypes.data_as(C.c_void_p) if cand.size else None, Cn,
+                                         PARENT_SELFING if selfing else 0, max(0, K), int(min_shared),
+                                         best.ctypes.data_as(C.c_void_p) if best.size else None,
+                                         table.ctypes.data_as(C.c_void_p) if fetch_table and table.size else None, C.byref(ms))
+        if rc:
+            err = self._error(rc)
+            err.bad_index = self._L.td_last_bad_index() if rc == -2 and err.detail.startswith(("offspring row ", "candidates of row ")) else None
+            raise err
+        t = (C.c_double * 3)()
+        B.check(self._L.td_parent_last_times(self._h, t))
+        return ParentTrios(best, table, ms.value, dict(pack_ms=t[0], trio_ms=t[1], rank_ms=t[2]))
 
     # ------------------------------------------------------------------ expected fragment sizes (exp_frag_size)
     def fasta_frame_device(self, d_text, nbytes, d_out, rec_cap):

@@ -8,6 +8,7 @@ heterozygosity.
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --relations pairs.csv --relations-matrix dist.csv
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --ld ld_pairs.csv --ld-keep keep.txt --relations pairs.csv --relations-ld-pruned
     python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --impute imputed.csv --impute-stats impute_stats.csv
+    python -m tagdigger_amd.tag_calls -i counts.csv -o calls.csv --min-call-rate 0.8 --parentage parentage.csv --parentage-parents founders.txt
 
 The input is the counter's CSV (samples in rows, tag names Marker_..._0 / Marker_..._1 in the header), or the
 libraries of a key file, which are counted first: every library's barcode rows are folded into one samples x tags
@@ -17,6 +18,8 @@ checks the samples themselves over the markers that pass (tag_relate's table; th
 --ld, --ld-groups and --ld-keep check those markers against each other (tag_ld's files, from the same calls on the
 device); --relations-ld-pruned then restricts the relations to the LD-pruned markers.  --impute fills the holes of the
 passing markers by LD-kNN imputation (tag_impute's file, from the same calls on the device) and writes them beside -o.
+--parentage finds the parent pairs of the samples over the markers that pass (tag_parentage's files and defaults, from the
+same calls on the device).
 """
 import argparse
 import csv
@@ -58,6 +61,10 @@ def build_parser():
     ap.add_argument("--impute-stats", metavar="FILE", help="--impute: per-marker CSV to write (missing, imputed, no_donor, undecided, neighbours)")
     from .tag_impute import add_tuning
     add_tuning(ap.add_argument_group("--impute (its LD shares --ld-min-shared)"), prefix="impute-", min_r2="--impute-min-r2", ld_min_shared=False)
+    ap.add_argument("--parentage", metavar="FILE", help="parentage CSV to write: the samples' parent pairs over the markers that pass (see tag_parentage)")
+    ap.add_argument("--parentage-offspring", metavar="FILE", help="--parentage: names of the samples to find parents for, one per line (default: all)")
+    ap.add_argument("--parentage-parents", metavar="FILE", help="--parentage: names of the samples that may be parents, one per line (default: all)")
+    ap.add_argument("--parentage-trios", metavar="FILE", help="--parentage: trios CSV to write (one row per ranked trio)")
     ap.add_argument("--rule", choices=list(tf.GENO_RULES), default="likelihood",
                     help="likelihood: heterozygous when the rarer allele's reads are too many for errors; presence: when both were seen")
     ap.add_argument("--err", type=float, default=0.01, help="sequencing error rate of the likelihood rule")
@@ -141,7 +148,10 @@ def main(argv=None):
     if args.impute_stats is not None and args.impute is None:
         raise Exception("--impute-stats goes with --impute.")
     impute = args.impute is not None
-    eng = d_counts = d_calls = relations = ldres = ld_keep = imputed = None
+    if args.parentage is None and any(x is not None for x in (args.parentage_offspring, args.parentage_parents, args.parentage_trios)):
+        raise Exception("--parentage-offspring, --parentage-parents and --parentage-trios go with --parentage.")
+    parent = args.parentage is not None
+    eng = d_counts = d_calls = relations = ldres = ld_keep = imputed = parents = None
     if args.counts is not None:
         if args.counts_out is not None:
             raise Exception("--counts-out goes with counting (-b); -i is that file already.")
@@ -171,7 +181,7 @@ def main(argv=None):
         samples, d_counts = count_on_device(eng, keys, sequences, site, args.maxreads)
         counts, backend = d_counts, "gpu"
     try:
-        keep = (relate or ld or impute) and backend == "gpu"       # relations, LD and imputation read the calls where the call kernel wrote them
+        keep = (relate or ld or impute or parent) and backend == "gpu"     # relations, LD, imputation and parentage read the calls where the call kernel wrote them
         result = tf.call_genotypes(counts, samples, names, backend=backend, keep_device=keep, **params)
         d_calls = result.d_calls
         if d_counts is not None and args.counts_out is not None:
@@ -186,6 +196,10 @@ def main(argv=None):
             relations = tf.sample_relations(d_calls if keep else result.calls, samples,
                                             mask=result.mask & ld_keep if args.relations_ld_pruned else result.mask, max_dist=args.max_dist,
                                             min_shared=args.min_shared, device=args.td_device, backend=backend)
+        if parent:
+            from .tag_parentage import read_names
+            parents = tf.parentage(d_calls if keep else result.calls, samples, offspring=read_names(args.parentage_offspring),
+                                   parents=read_names(args.parentage_parents), mask=result.mask, device=args.td_device, backend=backend)
         if impute:
             from .tag_impute import tuning
             imputed = tf.impute_calls(d_calls if keep else result.calls, result.markers, mask=result.mask, device=args.td_device,
@@ -224,10 +238,17 @@ def main(argv=None):
                                                      result.columns), passing_only=True)
         if args.impute_stats is not None:
             tf.writeImputeStats(args.impute_stats, imputed)
+    if parent:
+        tf.writeParentage(args.parentage, parents)
+        if args.parentage_trios is not None:
+            tf.writeTrios(args.parentage_trios, parents)
     print(stats_line(result))
     if impute:
         from .tag_impute import summary_line
         print(summary_line(imputed))
+    if parent:
+        from .tag_parentage import summary_line as parentage_line
+        print(parentage_line(parents))
     return 0
 
 

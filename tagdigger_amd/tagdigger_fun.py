@@ -1936,6 +1936,298 @@ def writeImputeStats(filename, result):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Parent pairs by Mendelian exclusion: which two samples are the parents of this one.  For an offspring o and
+# two candidate parents p, q, over the participating markers at which all three are called: n = their number, e = those at
+# which o's call is none that (p, q) can produce.  Candidates come from the pair table of sample_relations (n2 = markers
+# called in both, e2 = opposing homozygotes), the decision from the trios ranked by e / n.  Integers only; csrc/parent.hip
+# counts the trios with bit planes and popcounts from the calls where they lie, _parentage_host restates it in numpy.
+PARENT_MAX_SAMPLES = 16384
+PARENT_MAX_CAND = 128
+PARENT_MAX_TOP = 8
+PARENT_NONE = 0xFFFFFFFF
+PARENT_TRIO = [("p", "<u4"), ("q", "<u4"), ("n", "<u4"), ("e", "<u4")]
+PARENT_STATUS = ("trio", "ambiguous", "single", "none")
+_PARENT_HOST_BLOCK = 1 << 16    # markers of one block of _parentage_host: float32 planes of C times this size at a time
+
+
+class ParentageResult:
+    """What parentage returns: `.samples` (all names), `.offspring` (the sample indices asked about, in order) and, per
+    offspring, `.status` ("trio", "ambiguous", "single" or "none"), `.trios` (the first `top` ranked trios as tuples
+    (p, q, n, e) of sample indices and counts, best first), `.passes` (whether each of them passes max_trio_err),
+    `.single` ((p, n2, e2) of the first candidate when the status is "single", else None) and `.candidates` (how many
+    candidate parents the pair test left); `.stats` (backend, ms, markers, used and the thresholds)."""
+
+    def __init__(self, samples, offspring, status, trios, passes, single, candidates, stats):
+        self.samples, self.offspring, self.status, self.trios = samples, offspring, status, trios
+        self.passes, self.single, self.candidates, self.stats = passes, single, candidates, stats
+
+    def counts(self):
+        """How many offspring have each status, in the order of PARENT_STATUS."""
+        return [sum(1 for s in self.status if s == k) for k in PARENT_STATUS]
+
+
+def _parent_pairs(C, selfing):
+    """The slot pairs (a, b) of C slots in trio order: a ascending, then b ascending; a <= b with selfing, else a < b."""
+    import numpy as np
+    return np.triu_indices(C, 0 if selfing else 1)
+
+
+def _parent_first(n, e, live):
+    """The index of the first trio among `live` by (e / n ascending by cross-multiplication, n descending, index
+    ascending); n, e int64 below 2^31, n > 0 where live.  -1 when none is live."""
+    import numpy as np
+    idx = np.flatnonzero(live)
+    if not len(idx):
+        return -1
+    b = int(idx[np.argmin(e[idx] / n[idx])])
+    while True:                                    # the float minimum is a start; the exact rule decides
+        l, r = e[idx] * n[b], e[b] * n[idx]
+        better = (l < r) | ((l == r) & ((n[idx] > n[b]) | ((n[idx] == n[b]) & (idx < b))))
+        if not better.any():
+            return b
+        sub = idx[better]
+        b = int(sub[np.argmin(e[sub] / n[sub])])
+
+
+def _parent_rank(table, cand, selfing, K, min_shared):
+    """The first K trios of every row of a table [O, T, 2] by the ranking of DESIGN 4.18, as td_parent_trio records [O, K]."""
+    import numpy as np
+    O, C = cand.shape
+    ia, ib = _parent_pairs(C, selfing)
+    best = np.zeros((O, K), dtype=PARENT_TRIO)
+    best["p"] = best["q"] = PARENT_NONE
+    for i in range(O):
+        n, e = table[i, :, 0].astype(np.int64), table[i, :, 1].astype(np.int64)
+        live = n >= min_shared
+        for k in range(K):
+            t = _parent_first(n, e, live)
+            if t < 0:
+                break
+            best[i, k] = (cand[i, ia[t]], cand[i, ib[t]], n[t], e[t])
+            live[t] = False
+    return best
+
+
+def _parentage_host(calls, use, offspring, cand, selfing, K, min_shared):
+    """The trio counts and their ranking of DESIGN 4.18 in numpy.  n and e of every slot pair are sums of Gram products of
+    0 / 1 planes over the markers -- with A = called in offspring and parent, n = A A'; where the offspring is 0 the errors
+    are the trios with a parent called 2, i.e. all minus those with neither; likewise at 2; where it is 1 they are the
+    trios with both parents 0 or both 2 -- taken in float32 over blocks of markers short enough to be exact (< 2^24) and
+    summed in int64.  Returns (best [O, K] records, table uint32 [O, T, 2])."""
+    import numpy as np
+    calls = np.asarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    offspring, cand = np.asarray(offspring, dtype=np.int64), np.asarray(cand, dtype=np.int64)
+    O, C = cand.shape
+    ia, ib = _parent_pairs(C, selfing)
+    cols = np.arange(M) if use is None else np.nonzero(np.asarray(use) != 0)[0]
+    N, E = np.zeros((O, C, C), dtype=np.int64), np.zeros((O, C, C), dtype=np.int64)
+    for lo in range(0, len(cols), _PARENT_HOST_BLOCK):
+        part = calls[:, cols[lo:lo + _PARENT_HOST_BLOCK]]
+        for i in range(O):
+            own = part[offspring[i]]
+            P = part[np.maximum(cand[i], 0)]
+            P = np.where((cand[i] >= 0)[:, None], P, 3)            # an empty slot is called nowhere
+            both = (P <= 2) & (own <= 2)[None, :]
+
+            def gram(X):
+                X = X.astype(np.float32)
+                return np.rint(X @ X.T).astype(np.int64)
+
+            o0, o1, o2 = both & (own == 0), both & (own == 1), both & (own == 2)
+            N[i] += gram(both)
+            E[i] += gram(o0) - gram(o0 & (P != 2)) + gram(o2) - gram(o2 & (P != 0)) + gram(o1 & (P == 0)) + gram(o1 & (P == 2))
+    table = np.stack([N[:, ia, ib], E[:, ia, ib]], axis=2).astype(np.uint32).reshape(O, len(ia), 2)
+    return _parent_rank(table, cand, selfing, K, min_shared), table
+
+
+def _parent_candidates(n2, e2, allowed, min_shared, max_pair_err_ppm, max_candidates):
+    """The candidate parents of one offspring from its row of the pair table (n2, e2 int64 [S]; allowed bool [S]): those
+    with n2 >= min_shared and e2 10^6 <= max_pair_err_ppm n2, ordered by e2 / n2 ascending (cross-multiplied), n2
+    descending, index ascending; the first max_candidates."""
+    import functools
+    import numpy as np
+    idx = np.flatnonzero(allowed & (n2 >= min_shared) & (e2 * 1000000 <= max_pair_err_ppm * n2))
+    if len(idx) > 1:
+        n, e = n2[idx], e2[idx]
+        order = np.lexsort((idx, -n, e / n))       # a float key first; the neighbours are then checked exactly
+        idx, n, e = idx[order], n[order], e[order]
+        l, r = e[:-1] * n[1:], e[1:] * n[:-1]
+        in_order = (l < r) | ((l == r) & ((n[:-1] > n[1:]) | ((n[:-1] == n[1:]) & (idx[:-1] < idx[1:]))))
+        if not in_order.all():
+
+            def cmp(x, y):
+                l, r = int(e2[x]) * int(n2[y]), int(e2[y]) * int(n2[x])
+                return -1 if (l, -int(n2[x]), x) < (r, -int(n2[y]), y) else 1
+
+            idx = np.array(sorted(idx.tolist(), key=functools.cmp_to_key(cmp)), dtype=np.int64)
+    return idx[:max_candidates]
+
+
+def _name_indices(names, where, what):
+    out = []
+    for name in names:
+        if name not in where:
+            raise ValueError("{} {!r} is not a sample of the call matrix".format(what, name))
+        out.append(where[name])
+    return out
+
+
+def parentage(calls, samnames, offspring=None, parents=None, mask=None, max_pair_err=0.03, max_trio_err=0.03, min_shared=50,
+              max_candidates=32, top=2, selfing=True, device=0, backend="gpu"):
+    """Parent pairs of the samples by Mendelian exclusion.
+
+    calls, samnames and mask are sample_relations': a samples x markers matrix of codes 0, 1, 2 and 3 (missing) -- numpy
+    or lists -- or a DeviceCalls (backend="gpu" only; there any byte above 2 is missing); a marker takes part iff its
+    entry of mask is true (None: all).  offspring, parents: lists of sample names, the samples asked about and the samples
+    that may be parents (None: all samples).  Sample p is a candidate parent of o iff it is in parents, is not o, shares
+    n2 >= min_shared called markers with o and is an opposing homozygote at e2 of them with e2 10^6 <= max_pair_err_ppm
+    n2; the first max_candidates by (e2 / n2 ascending, n2 descending, index ascending) are kept.  For every pair of an
+    offspring's candidates (one twice included, with selfing) the trio is counted: n markers called in all three, e of
+    them at which the offspring's call is none the pair can produce.  Trios with n >= min_shared are ranked by (e / n
+    ascending, n descending, slot pair ascending); one passes iff e 10^6 <= max_trio_err_ppm n.  Status: "trio" -- the
+    best passes and the second does not; "ambiguous" -- two pass; "single" -- none passes but there is a candidate (the
+    first is reported); "none".  The rates are taken in parts per million.  Nothing is promised about accuracy: the
+    thresholds are the user's to set for the error rate of their calls.  backend="gpu" runs csrc/relate.hip and
+    csrc/parent.hip on the calls where they lie; backend="host" is the numpy restatement: the same result.  Returns a
+    ParentageResult."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    pair_ppm = _ppm(max_pair_err, 0, 1000000, "max_pair_err")
+    trio_ppm = _ppm(max_trio_err, 0, 1000000, "max_trio_err")
+    for name, v, lo, hi in (("min_shared", min_shared, 1, (1 << 31) - 1), ("max_candidates", max_candidates, 1, PARENT_MAX_CAND),
+                            ("top", top, 1, PARENT_MAX_TOP)):
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("{} must be an integer in {} .. {}".format(name, lo, hi))
+    min_shared, max_candidates, top, selfing = int(min_shared), int(max_candidates), int(top), bool(selfing)
+    on_device = isinstance(calls, DeviceCalls)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCalls matrix needs backend='gpu'")
+    samnames = list(samnames)
+    if not on_device:
+        calls = np.asarray(calls if len(calls) else np.zeros((0, 0 if mask is None else len(mask)), dtype=np.uint8))
+        if calls.ndim != 2:
+            raise ValueError("the call matrix must have two dimensions (samples x markers)")
+        if calls.dtype.kind not in "iub":
+            raise ValueError("the call matrix must hold the integer codes 0 .. 3, not {}".format(calls.dtype))
+        if calls.size and (int(calls.min()) < 0 or int(calls.max()) > 3):
+            raise ValueError("the call matrix must hold 0, 1, 2 or 3 (missing) only")
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    if len(samnames) != S:
+        raise ValueError("samnames must name every row of the call matrix")
+    if S > PARENT_MAX_SAMPLES:
+        raise ValueError("at most {} samples".format(PARENT_MAX_SAMPLES))
+    if M >= 1 << 31:
+        raise ValueError("markers must number below 2^31")
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (M,):
+            raise ValueError("mask must have one entry per marker")
+        mask = mask != 0
+    where = {}
+    for k, name in enumerate(samnames):
+        where.setdefault(name, k)
+    off = list(range(S)) if offspring is None else _name_indices(offspring, where, "offspring")
+    allowed = np.ones(S, dtype=bool)
+    if parents is not None:
+        allowed[:] = False
+        allowed[_name_indices(parents, where, "parent")] = True
+    K, O = max(2, top), len(off)
+    eng = d_own = None
+    ms = 0.0
+    try:
+        if backend == "host":
+            joint = _relations_host(calls, mask)
+        else:
+            eng = default_engine(device)
+            if on_device:
+                ptr = calls.ptr or None
+            else:                                  # one upload serves both kernels
+                ptr = d_own = eng.dev_alloc(calls.nbytes) if calls.size else None
+                if d_own:
+                    eng.h2d(d_own, calls.tobytes())
+            rel = eng.relate_joint(ptr, shape=(S, M), use=mask)
+            joint, ms = rel.joint, rel.ms
+        J = joint[off].astype(np.int64) if O else np.zeros((0, S, 3, 3), dtype=np.int64)
+        n2, e2 = J.sum(axis=(2, 3)), J[:, :, 0, 2] + J[:, :, 2, 0]
+        lists = []
+        for i, o in enumerate(off):
+            ok = allowed.copy()
+            ok[o] = False
+            lists.append(_parent_candidates(n2[i], e2[i], ok, min_shared, pair_ppm, max_candidates))
+        Cn = max([1] + [len(x) for x in lists])
+        cand = np.full((O, Cn), -1, dtype=np.int32)
+        for i, x in enumerate(lists):
+            cand[i, :len(x)] = x
+        if backend == "host":
+            best = _parentage_host(calls, mask, off, cand, selfing, K, min_shared)[0] if O else np.zeros((0, K), dtype=PARENT_TRIO)
+        else:
+            res = eng.parent_trios(ptr, off, cand, shape=(S, M), use=mask, selfing=selfing, top=K, min_shared=min_shared)
+            best, ms = res.best, ms + res.ms
+    finally:
+        if d_own:
+            eng.dev_free(d_own)
+    status, trios, passes, single = [], [], [], []
+    for i in range(O):
+        ranked = [(int(r["p"]), int(r["q"]), int(r["n"]), int(r["e"])) for r in best[i] if r["p"] != PARENT_NONE]
+        ok = [e * 1000000 <= trio_ppm * n for _, _, n, e in ranked]
+        if ok[:1] == [True]:
+            status.append("ambiguous" if ok[1:2] == [True] else "trio")
+        else:
+            status.append("single" if len(lists[i]) else "none")
+        first = int(lists[i][0]) if status[-1] == "single" else None
+        single.append(None if first is None else (first, int(n2[i, first]), int(e2[i, first])))
+        trios.append(ranked[:top])
+        passes.append(ok[:top])
+    used = M if mask is None else int(mask.sum())
+    stats = dict(backend=backend, ms=ms, markers=M, used=used, max_pair_err_ppm=pair_ppm, max_trio_err_ppm=trio_ppm, min_shared=min_shared,
+                 max_candidates=max_candidates, top=top, selfing=selfing)
+    return ParentageResult(samnames, off, status, trios, passes, single, [len(x) for x in lists], stats)
+
+
+def _rate_text(e, n):
+    return "NA" if n == 0 else format(e / n, ".6f")
+
+
+PARENTAGE_COLUMNS = ("offspring", "status", "parent1", "parent2", "shared", "errors", "error_rate", "single_parent", "pair_shared",
+                     "pair_errors", "pair_error_rate", "candidates")
+PARENT_TRIO_COLUMNS = ("offspring", "rank", "parent1", "parent2", "shared", "errors", "error_rate", "pass")
+
+
+def writeParentage(filename, result):
+    """One row per offspring: its name, the status, for "trio" and "ambiguous" the best trio (the parents' names, the
+    markers called in all three, the Mendelian errors among them and their share, six decimals), for "single" the first
+    candidate (name, markers called in both, opposing homozygotes and their share), and the number of candidates; cells
+    that do not apply are empty.  CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(PARENTAGE_COLUMNS)
+        for i, o in enumerate(result.offspring):
+            trio, one = [""] * 5, [""] * 4
+            if result.status[i] in ("trio", "ambiguous"):
+                p, q, n, e = result.trios[i][0]
+                trio = [result.samples[p], result.samples[q], n, e, _rate_text(e, n)]
+            if result.single[i] is not None:
+                p, n, e = result.single[i]
+                one = [result.samples[p], n, e, _rate_text(e, n)]
+            out.writerow([result.samples[o], result.status[i]] + trio + one + [result.candidates[i]])
+
+
+def writeTrios(filename, result):
+    """One row per ranked trio that parentage kept (the first `top` of every offspring): offspring, rank from 1, the
+    parents' names, shared, errors, their share (six decimals) and pass (1 / 0); CSV with a header row, CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(PARENT_TRIO_COLUMNS)
+        for i, o in enumerate(result.offspring):
+            for k, (p, q, n, e) in enumerate(result.trios[i]):
+                out.writerow([result.samples[o], k + 1, result.samples[p], result.samples[q], n, e, _rate_text(e, n),
+                              1 if result.passes[i][k] else 0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Tag Manager (reference tagdigger_fun.py:1389-1905 and the prompts of :936-1028, :1182-1200).
 #
 # Every function keeps the reference's signature, return values, printed lines, files and exceptions.  Those with a
