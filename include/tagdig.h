@@ -410,6 +410,50 @@ int td_census_stats(td_handle *h, uint64_t out[8]);
 int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *counts_out, uint64_t capacity, uint64_t *n_out);
 int td_census_end(td_handle *h);
 
+/* ---- library QC (csrc/qc.hip; tagdigger_amd/tagdigger_fun.py library_qc drives these) ----------------------------------
+ *
+ * The first questions about a sequenced library, in one pass over all bytes of its sequence and quality lines
+ * (DESIGN.md 4.19): reads, bases and reads with a non-ACGT character per barcode; base composition, quality values and
+ * read lengths per cycle; the reads' mean quality.  Lines are the counter's; record r is lines 4r .. 4r + 3; records
+ * r >= max_reads are not looked at; every line is decided on its own.  C = max_cycles; row C of a per-cycle table is
+ * the overflow row for positions >= C.  Every counter is a uint64_t.
+ *
+ * td_qc_begin: the barcode + cut-site index as td_census_begin builds it (same list, same errors, baroff[barnum] =
+ *   len(barcode), at most 32); max_cycles 1 .. TD_QC_MAX_CYCLES.  Zeroed tables; a QC begun before is dropped.
+ * td_qc_device: one pass over a resident buffer whose first line has index first_line (it may start inside a record).
+ *   Asynchronous, accumulates; ONE stream in flight per handle.
+ * td_qc_file: a whole file, plain, gzip or BGZF, through td_count_file's readers, which are asked for one record more
+ *   than max_reads so that the last record's quality line arrives.  Synchronous, accumulates.
+ * td_qc_stats: out[TD_QC_*], cumulative since td_qc_begin.  Synchronises.
+ * td_qc_fetch: the tables, each pointer may be NULL:
+ *     barcode_out     [(B + 1) * 3]   row b: reads, bases, reads with a non-ACGT character; row B: no barcode + cut site
+ *     base_cycle_out  [(C + 1) * 6]   row min(i, C): A, C, G, T, N, anything else
+ *     qual_cycle_out  [(C + 1) * 95]  row min(i, C): byte values 33 .. 126 as 0 .. 93, column 94: any other byte
+ *     length_out      [C + 1]         reads of length min(n, C)
+ *     meanq_out       [94]            quality lines by floor(sum / count) of their valid values
+ * td_qc_end: frees the QC.
+ * Options (td_set_option): "qc_flush_tiles", the tiles after which a workgroup merges its LDS tables into device
+ *   memory (0: the built-in 4096; at most 2^20); "max_grid" caps the grid.  Every setting gives the same result.
+ * Errors: TD_E_NONASCII as the counter's.  After it, and after a td_qc_file that failed part-way, every call answers
+ *   with that error until td_qc_begin. */
+enum {
+    TD_QC_READS = 0,          /* sequence lines looked at                                               */
+    TD_QC_BARCUT = 1,         /* ... with barcode + cut site                                            */
+    TD_QC_QUAL_LINES = 2,     /* quality lines looked at                                                */
+    TD_QC_BASES = 3,          /* characters of the stripped sequence lines                              */
+    TD_QC_QUAL_BASES = 4,     /* bytes 33 .. 126 of the stripped quality lines                          */
+    TD_QC_QUAL_INVALID = 5,   /* their other bytes                                                      */
+    TD_QC_EMPTY_QUAL = 6,     /* quality lines without a valid byte                                     */
+    TD_QC_CYCLES = 7,         /* max_cycles of td_qc_begin                                              */
+    TD_QC_MAX_CYCLES = 1024
+};
+int td_qc_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *baroff, uint32_t max_cycles);
+int td_qc_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream);
+int td_qc_file(td_handle *h, const char *path, uint64_t max_reads);
+int td_qc_stats(td_handle *h, uint64_t out[8]);
+int td_qc_fetch(td_handle *h, uint64_t *barcode_out, uint64_t *base_cycle_out, uint64_t *qual_cycle_out, uint64_t *length_out, uint64_t *meanq_out);
+int td_qc_end(td_handle *h);
+
 /* ---- tag network (csrc/tagnet.hip; tagdigger_amd/tagdigger_fun.py tag_network and census_markers drive these) --------
  *
  * From a census to markers without a reference genome (the UNEAK network filter).  Input: n tags of one

@@ -168,6 +168,12 @@ def load():
     sig("td_census_stats", i32, vp, C.POINTER(u64))
     sig("td_census_fetch", i32, vp, u64, vp, vp, u64, C.POINTER(u64))
     sig("td_census_end", i32, vp)
+    sig("td_qc_begin", i32, vp, pp, u32, u32, C.POINTER(u32), u32)
+    sig("td_qc_device", i32, vp, vp, u64, u64, u64, vp)
+    sig("td_qc_file", i32, vp, C.c_char_p, u64)
+    sig("td_qc_stats", i32, vp, C.POINTER(u64))
+    sig("td_qc_fetch", i32, vp, vp, vp, vp, vp, vp)
+    sig("td_qc_end", i32, vp)
     sig("td_tagnet_build", i32, vp, vp, vp, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), dp)
     sig("td_tagnet_edges", i32, vp, vp, i32, vp, u64, C.POINTER(u64))
     sig("td_tagnet_pairs", i32, vp, vp, vp, u64, C.POINTER(u64))
@@ -200,6 +206,7 @@ EXPORTS = [
     "td_tagset_load", "td_tagset_free", "td_tagset_lookup", "td_tagset_varsites",
     "td_md5_device", "td_md5_files",
     "td_census_begin", "td_census_device", "td_census_file", "td_census_stats", "td_census_fetch", "td_census_end",
+    "td_qc_begin", "td_qc_device", "td_qc_file", "td_qc_stats", "td_qc_fetch", "td_qc_end",
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
     "td_geno_call", "td_relate_joint", "td_ld_pairs", "td_ld_last_times",
     "td_impute_knn", "td_impute_last_times",

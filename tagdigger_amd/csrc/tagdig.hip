@@ -152,6 +152,8 @@ struct td_handle {
     int device = 0;
     const td_piece_sink *sink = nullptr;
     void *census = nullptr;                   // csrc/census.hip's state (td_census_begin .. td_census_end)
+    void *qc = nullptr;                       // csrc/qc.hip's state (td_qc_begin .. td_qc_end)
+    uint32_t qc_flush_tiles = 0;              // (tests: tiles between two merges of k_qc's LDS tables; 0 = the built-in 4096)
     int num_cu = 256;
     hipStream_t copy_stream = nullptr, work_stream = nullptr;
     // (one copy engine moves 22-30 GB/s out of pinned memory that lies on the far socket, two or three together 50: large
@@ -712,6 +714,10 @@ extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_hand
 // for csrc/census.hip (hidden): its state's place on the handle, the work stream, the CU count; the barcode + cut-site
 // index by td_set_index's rules; the handle's line counting and tile scan
 extern "C" __attribute__((visibility("hidden"))) void **td_handle_census(td_handle *h) { return &h->census; }
+// for csrc/qc.hip (hidden): its state's place on the handle, and the options "qc_flush_tiles" and "max_grid"
+extern "C" __attribute__((visibility("hidden"))) void **td_handle_qc(td_handle *h) { return &h->qc; }
+extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_qc_flush_tiles(const td_handle *h) { return h->qc_flush_tiles; }
+extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_max_grid(const td_handle *h) { return h->max_grid; }
 extern "C" __attribute__((visibility("hidden"))) void *td_handle_work_stream(const td_handle *h) { return (void *)h->work_stream; }
 extern "C" __attribute__((visibility("hidden"))) int td_handle_num_cu(const td_handle *h) { return h->num_cu; }
 extern "C" __attribute__((visibility("hidden"))) int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
@@ -782,6 +788,7 @@ void td_destroy(td_handle *h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     td_census_release(h);
+    td_qc_release(h);
     h->d_bblob.release(); h->d_slots.release(); h->d_shorts.release(); h->d_counts.release();
     if (h->pin_cursor) (void)hipHostFree(h->pin_cursor);
     h->d_win.release(); h->d_tilesums.release(); h->d_f4np.release(); h->d_sp_entries16.release(); h->d_sp_e8.release(); h->d_sp_pool2.release();
@@ -2814,6 +2821,8 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
         h->stage_kb = value > 0 ? (uint32_t)std::max<int64_t>(64, std::min<int64_t>(value, 32768)) : 0;
     else if (n == "max_grid")                   // (tests: few workgroups take the whole buffer, each through many runs of its ring; 0 = no cap)
         h->max_grid = value > 0 ? (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF) : 0;
+    else if (n == "qc_flush_tiles")             // (tests: k_qc merges its LDS tables after this many tiles; 0 = the built-in 4096)
+        h->qc_flush_tiles = value > 0 ? (uint32_t)std::min<int64_t>(value, 1 << 20) : 0;
     else if (n == "debug_ablate") h->debug_ablate = (uint32_t)value;   // timing-only ablations, wrong results
     else return fail(TD_E_ARG, "unknown option " + n);
     return TD_OK;

@@ -39,6 +39,12 @@ TD_HIDDEN int td_line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes,
 TD_HIDDEN int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink);
 // census.hip, for td_destroy: frees the handle's census, if any
 TD_HIDDEN void td_census_release(td_handle *h);
+// tagdig.hip, for qc.hip: the QC's place on the handle; the options "qc_flush_tiles" and "max_grid" (0: not set)
+TD_HIDDEN void **td_handle_qc(td_handle *h);
+TD_HIDDEN uint32_t td_handle_qc_flush_tiles(const td_handle *h);
+TD_HIDDEN uint32_t td_handle_max_grid(const td_handle *h);
+// qc.hip, for td_destroy: frees the handle's QC state, if any
+TD_HIDDEN void td_qc_release(td_handle *h);
 }
 
 // a failed HIP call ends the calling function with TD_E_HIP and "<the call as written>: <HIP's text>"

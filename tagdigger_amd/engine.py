@@ -56,6 +56,7 @@ def census_index(barcodes, cutsite):
 INDEX_INFO = ("W", "m_bases", "buckets", "spb", "nshort", "displaced", "longest", "wrapped", "nch", "nch2")     # TD_INDEX_* slots
 
 CENSUS_STATS = ("reads", "barcut", "short", "ambiguous", "counted", "distinct", "slots", "max_keys")
+QC_STATS = ("reads", "barcut", "qual_lines", "bases", "qual_bases", "qual_invalid", "empty_qual", "max_cycles")     # TD_QC_* slots
 
 
 def effective_maxreads(maxreads):
@@ -504,6 +505,42 @@ class Engine:
     def census_end(self):
         B.check(self._L.td_census_end(self._h))
         self._census_taglen = 0
+
+    # ------------------------------------------------------------------ library QC (td_qc_*; csrc/qc.hip)
+    def qc_begin(self, barcodes, cutsite="TGCAG", max_cycles=160):
+        """Fresh QC tables for these barcodes: per-cycle rows 0 .. max_cycles - 1 and one overflow row."""
+        barcut, barnum, baroff = census_index(barcodes, cutsite)
+        B.check(self._L.td_qc_begin(self._h, _c_strings(barcut), len(barcut), barnum,
+                                    (C.c_uint32 * max(1, barnum))(*baroff), int(max_cycles)))
+        self._qc_shape = (barnum, int(max_cycles))
+
+    def qc_device(self, d_ptr, nbytes, first_line=0, maxreads=5e9, stream=0):
+        """Enqueue one QC pass over a FASTQ buffer already in HBM (asynchronous, accumulates)."""
+        B.check(self._L.td_qc_device(self._h, C.c_void_p(d_ptr), nbytes, first_line, effective_maxreads(maxreads),
+                                     C.c_void_p(stream) if stream else None))
+
+    def qc_file(self, path, maxreads=5e9):
+        """The QC over a file, plain or gzip by name, through count_file's readers (accumulates)."""
+        open(path, 'rb').close()
+        B.check(self._L.td_qc_file(self._h, os.fsencode(path), effective_maxreads(maxreads)))
+
+    def qc_stats(self):
+        """{reads, barcut, qual_lines, bases, qual_bases, qual_invalid, empty_qual, max_cycles}, cumulative since qc_begin."""
+        st = (C.c_uint64 * 8)()
+        B.check(self._L.td_qc_stats(self._h, st))
+        return dict(zip(QC_STATS, (int(x) for x in st)))
+
+    def qc_fetch(self):
+        """(barcodes (B+1, 3), base_cycle (C+1, 6), qual_cycle (C+1, 95), lengths (C+1), meanq (94)) as numpy uint64."""
+        import numpy as np
+        barnum, cyc = getattr(self, "_qc_shape", (0, 0))
+        out = [np.zeros(shape, dtype=np.uint64) for shape in ((barnum + 1, 3), (cyc + 1, 6), (cyc + 1, 95), (cyc + 1,), (94,))]
+        B.check(self._L.td_qc_fetch(self._h, *[C.c_void_p(a.ctypes.data) for a in out]))
+        return tuple(out)
+
+    def qc_end(self):
+        B.check(self._L.td_qc_end(self._h))
+        self._qc_shape = (0, 0)
 
     # ------------------------------------------------------------------ tag network (td_tagnet_*; csrc/tagnet.hip)
     def tagnet_build(self, seqs, counts, taglen, ratio_ppm):

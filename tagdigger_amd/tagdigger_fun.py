@@ -2228,6 +2228,214 @@ def writeTrios(filename, result):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Library QC: what one asks of a freshly sequenced library before anything else is worth running.
+# Every statistic is an integer; backend="gpu" (csrc/qc.hip) and backend="host" give the same tables.
+QC_STRIP = " \t\n\r\x0b\x0c\x1c\x1d\x1e\x1f"            # the counter's strip set (str.strip() of an ASCII line)
+QC_BASE_CLASSES = ("A", "C", "G", "T", "N", "Other")
+QC_STAT_NAMES = ("reads", "barcut", "qual_lines", "bases", "qual_bases", "qual_invalid", "empty_qual")
+QC_PERCENTILES = (10, 25, 50, 75, 90)
+QC_MAX_CYCLES = 1024
+
+
+class QCResult:
+    """What library_qc returns.  `.stats`: reads, barcut, qual_lines, bases, qual_bases, qual_invalid, empty_qual;
+    numpy uint64 arrays `.barcodes` (B + 1 rows of reads, bases, reads with a non-ACGT character; the last row is "no
+    barcode"), `.base_cycle` (C + 1 rows of A, C, G, T, N, other), `.qual_cycle` (C + 1 rows of Phred 0..93 and, in
+    column 94, invalid bytes), `.lengths` (C + 1) and `.meanq` (94); row C of a per-cycle table holds positions >= C."""
+
+    def __init__(self, stats, barcodes, base_cycle, qual_cycle, lengths, meanq, max_cycles):
+        self.stats, self.barcodes, self.base_cycle, self.qual_cycle = stats, barcodes, base_cycle, qual_cycle
+        self.lengths, self.meanq, self.max_cycles = lengths, meanq, max_cycles
+
+    def cycle_quantiles(self, p):
+        """Per row of qual_cycle: the smallest Phred value v with 100 * #(values <= v) >= p * n over the row's n valid
+        values, in integers; None for a row without one."""
+        out = []
+        for row in self.qual_cycle:
+            counts = [int(x) for x in row[:94]]
+            n = sum(counts)
+            if n == 0:
+                out.append(None)
+                continue
+            seen = 0
+            for v, c in enumerate(counts):
+                seen += c
+                if 100 * seen >= p * n:
+                    out.append(v)
+                    break
+            else:                                      # (p > 100: no value reaches it)
+                out.append(None)
+        return out
+
+    def cycle_means_x100(self):
+        """Per row of qual_cycle: 100 * sum of the valid values // their number; None for a row without one."""
+        out = []
+        for row in self.qual_cycle:
+            n = sum(int(x) for x in row[:94])
+            out.append(None if n == 0 else 100 * sum(v * int(x) for v, x in enumerate(row[:94])) // n)
+        return out
+
+
+def _qc_host(fqfile, barcodes, cutsite, C, maxreads):
+    """The QC rule line by line.  The file is read as the reference reads it with one record more than the bound, so
+    that the last record's quality line is seen: through line 4 R + 1, or to the file's end."""
+    import numpy as np
+    from ._binding import NonAsciiSequence
+    index = _census_host_index(barcodes, cutsite)
+    keylens = sorted({len(s) for s in index})
+    R = effective_maxreads(maxreads)
+    B = len(barcodes)
+    bar = [[0, 0, 0] for _ in range(B + 1)]
+    base = [[0] * 6 for _ in range(C + 1)]
+    qual = [[0] * 95 for _ in range(C + 1)]
+    lengths = [0] * (C + 1)
+    meanq = [0] * 94
+    st = dict.fromkeys(QC_STAT_NAMES, 0)
+    # (bytes.translate to class and bin numbers, then plain list cells: a numpy scalar add per byte is ten times slower)
+    to_class = bytes(dict(zip(b"ACGTN", range(5))).get(v, 5) for v in range(256))
+    to_bin = bytes(v - 33 if 33 <= v <= 126 else 94 for v in range(256))
+    opener = _gzip.open if fqfile[-2:].lower() == 'gz' else open
+    with opener(fqfile, 'rt', encoding='latin-1') as fh:
+        for k, line in enumerate(fh):
+            if k & 1 and (k >> 2) < R:
+                if k & 3 == 1:
+                    if any(ch >= '\x80' for ch in line):
+                        raise NonAsciiSequence("non-ASCII byte in a sequence line")
+                    line1 = line.strip(QC_STRIP).upper()
+                    n = len(line1)
+                    b = B
+                    for m in keylens:
+                        if n >= m and line1[:m] in index:
+                            b = index[line1[:m]]
+                            break
+                    codes = line1.encode('latin-1').translate(to_class)
+                    st["reads"] += 1
+                    st["bases"] += n
+                    st["barcut"] += b < B
+                    row = bar[b]
+                    row[0] += 1
+                    row[1] += n
+                    row[2] += codes.count(4) + codes.count(5) > 0
+                    lengths[min(n, C)] += 1
+                    for i, c in enumerate(codes[:C]):
+                        base[i][c] += 1
+                    if n > C:
+                        tail, row = codes[C:], base[C]
+                        for c in range(6):
+                            row[c] += tail.count(c)
+                else:
+                    bins = line.strip(QC_STRIP).encode('latin-1').translate(to_bin)
+                    invalid = bins.count(94)
+                    nvalid = len(bins) - invalid
+                    for i, v in enumerate(bins[:C]):
+                        qual[i][v] += 1
+                    if len(bins) > C:
+                        tail, row = bins[C:], qual[C]
+                        for v in set(tail):
+                            row[v] += tail.count(v)
+                    st["qual_lines"] += 1
+                    st["qual_bases"] += nvalid
+                    st["qual_invalid"] += invalid
+                    if nvalid == 0:
+                        st["empty_qual"] += 1
+                    else:
+                        meanq[(sum(bins) - 94 * invalid) // nvalid] += 1
+            if k >= 4 * R + 1:
+                break
+    u = lambda x: np.array(x, dtype=np.uint64)
+    bar, base, qual, lengths, meanq = u(bar), u(base), u(qual), u(lengths), u(meanq)
+    return QCResult(st, bar, base, qual, lengths, meanq, C)
+
+
+def library_qc(fqfile, barcodes, cutsite="TGCAG", max_cycles=160, maxreads=5e9, device=0, backend="gpu"):
+    """Per-barcode and per-cycle statistics of one library (plain or .gz by name) in one pass -> QCResult.
+
+    Lines are the counter's; record r is lines 4r .. 4r + 3 and the first `maxreads` records are looked at.  A sequence
+    line is stripped and upper-cased (a byte >= 0x80 raises NonAsciiSequence); its barcode row comes from
+    find_tags_fastq's barcode + cut site lookup, the last row taking the reads without one.  A quality line is stripped
+    and its bytes 33..126 count as Phred 0..93, any other byte as invalid.  Positions >= max_cycles (1..1024) go to the
+    tables' last row.  Every line is decided on its own: there is no per-barcode quality and no length comparison of a
+    record's two lines.  backend="gpu": csrc/qc.hip; backend="host": the same rule in Python."""
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    C = int(max_cycles)
+    if not 1 <= C <= QC_MAX_CYCLES:
+        raise ValueError("max_cycles must be 1..1024")
+    if backend == "host":
+        return _qc_host(fqfile, barcodes, cutsite, C, maxreads)
+    eng = default_engine(device)
+    eng.qc_begin(barcodes, cutsite, C)
+    try:
+        eng.qc_file(fqfile, maxreads)
+        stats = eng.qc_stats()
+        tables = eng.qc_fetch()
+    finally:
+        try:
+            eng.qc_end()
+        except Exception:          # noqa: BLE001 -- the error that brought us here is the one to report
+            pass
+    return QCResult({k: stats[k] for k in QC_STAT_NAMES}, *tables, C)
+
+
+def _qc_cycle_label(i, C):
+    return str(i + 1) if i < C else ">{}".format(C)
+
+
+def writeQCSamples(filename, libraries, results, barcodes, samples):
+    """One row per barcode of every library and a last row `(none)` for its reads without barcode + cut site: Library,
+    Barcode, Sample, Reads, Reads ppm of library (floor), Bases, Reads with non-ACGT.  `libraries`, `results`,
+    `barcodes` and `samples` are lists with one entry per library.  CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Library", "Barcode", "Sample", "Reads", "Reads ppm of library", "Bases", "Reads with non-ACGT"])
+        for lib, res, bars, sams in zip(libraries, results, barcodes, samples):
+            total = res.stats["reads"]
+            for k, row in enumerate(res.barcodes):
+                r, n, a = (int(x) for x in row)
+                last = k == len(bars)
+                out.writerow([lib, "(none)" if last else bars[k], "(none)" if last else sams[k], r,
+                              r * 1000000 // total if total else 0, n, a])
+
+
+def writeQCCycles(filename, libraries, results):
+    """One row per cycle of every library (the last, `>C`, for the positions beyond max_cycles): the six base counts,
+    the valid and invalid quality bytes, their mean (100 * sum // n, two decimals) and the 10th, 25th, 50th, 75th and
+    90th percentile; the quality cells of a cycle without a valid byte are empty."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Library", "Cycle"] + list(QC_BASE_CLASSES) + ["Quality values", "Invalid quality bytes", "Mean quality"] +
+                     ["Q{}".format(p) for p in QC_PERCENTILES])
+        for lib, res in zip(libraries, results):
+            means = res.cycle_means_x100()
+            quants = [res.cycle_quantiles(p) for p in QC_PERCENTILES]
+            for i in range(res.max_cycles + 1):
+                valid = sum(int(x) for x in res.qual_cycle[i][:94])
+                mean = "" if means[i] is None else "{}.{:02d}".format(means[i] // 100, means[i] % 100)
+                out.writerow([lib, _qc_cycle_label(i, res.max_cycles)] + [int(x) for x in res.base_cycle[i]] +
+                             [valid, int(res.qual_cycle[i][94]), mean] + ["" if q[i] is None else q[i] for q in quants])
+
+
+def writeQCLengths(filename, libraries, results):
+    """Library, Length, Reads: the reads of every length 0 .. max_cycles - 1 and, as `>=C`, of the longer ones."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Library", "Length", "Reads"])
+        for lib, res in zip(libraries, results):
+            for n, c in enumerate(res.lengths):
+                out.writerow([lib, n if n < res.max_cycles else ">={}".format(res.max_cycles), int(c)])
+
+
+def writeQCQualityMatrix(filename, libraries, results):
+    """The full cycle x Phred table: Library, Cycle, Q0 .. Q93, Invalid."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Library", "Cycle"] + ["Q{}".format(v) for v in range(94)] + ["Invalid"])
+        for lib, res in zip(libraries, results):
+            for i, row in enumerate(res.qual_cycle):
+                out.writerow([lib, _qc_cycle_label(i, res.max_cycles)] + [int(x) for x in row])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Tag Manager (reference tagdigger_fun.py:1389-1905 and the prompts of :936-1028, :1182-1200).
 #
 # Every function keeps the reference's signature, return values, printed lines, files and exceptions.  Those with a
