@@ -354,26 +354,21 @@ constexpr size_t CENSUS_LDS_INDEX = 40 * 1024;            // the barcode index's
 struct Census {
     td_handle *h = nullptr;
     uint32_t taglen = 0, bblob_bytes = 0, off_bmeta = 0, off_bdir = 0;
-    uint32_t *d_bblob = nullptr;
-    unsigned long long *d_table = nullptr, *d_cs = nullptr;
+    tdi::DevBuf<uint32_t> d_bblob;
+    tdi::DevBuf<unsigned long long> d_table, d_cs;
     uint64_t slots = 0, max_keys = 0;
     int combine = 1;
     bool used = false;                        // something has been added since td_census_begin
     int dead = 0;                             // the code every call answers with after a failure, until td_census_begin
     std::string dead_msg;
     size_t slot_words() const { return taglen > 32 ? 4 : 2; }
-    ~Census() {
-        if (d_bblob) (void)hipFree(d_bblob);
-        if (d_table) (void)hipFree(d_table);
-        if (d_cs) (void)hipFree(d_cs);
-    }
 };
 
 Census *census_of(td_handle *h) { return h ? (Census *)*td_handle_census(h) : nullptr; }
 
 int census_zero(Census *c, hipStream_t s) {
-    TD_HIPCHK(hipMemsetAsync(c->d_table, 0, c->slots * c->slot_words() * 8, s));
-    TD_HIPCHK(hipMemsetAsync(c->d_cs, 0, tdc::CS_NWORDS * 8, s));
+    TD_HIPCHK(hipMemsetAsync(c->d_table.p, 0, c->slots * c->slot_words() * 8, s));
+    TD_HIPCHK(hipMemsetAsync(c->d_cs.p, 0, tdc::CS_NWORDS * 8, s));
     TD_HIPCHK(hipStreamSynchronize(s));
     c->used = false;
     return TD_OK;
@@ -387,14 +382,14 @@ int census_launch(Census *c, const void *d_fastq, uint64_t nbytes, uint64_t firs
     if (max_reads == 0) max_reads = 1;
     c->used = true;
     const uint64_t *prefix = nullptr;
-    int rc = td_line_prefix(c->h, d_fastq, nbytes, (void *)stream, &prefix, c->d_cs + tdc::CS_TOTAL); if (rc) return rc;
+    int rc = td_line_prefix(c->h, d_fastq, nbytes, (void *)stream, &prefix, c->d_cs.p + tdc::CS_TOTAL); if (rc) return rc;
     tdc::CensusParams p{};
     p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
     // last read line that is looked at: ordinal r (1-based) sits on line 4 (r - 1) + 1
     p.limit_line = max_reads >= (1ull << 60) ? ~0ull - 8 : 4 * (max_reads - 1) + 1;
     p.prefix = prefix; p.ntiles = (uint32_t)((nbytes + tdc::TILE - 1) / tdc::TILE);
-    p.bblob = c->d_bblob; p.bblob_bytes = c->bblob_bytes; p.off_bmeta = c->off_bmeta; p.off_bdir = c->off_bdir;
-    p.taglen = c->taglen; p.table = c->d_table; p.slot_mask = c->slots - 1; p.max_keys = c->max_keys; p.cs = c->d_cs;
+    p.bblob = c->d_bblob.p; p.bblob_bytes = c->bblob_bytes; p.off_bmeta = c->off_bmeta; p.off_bdir = c->off_bdir;
+    p.taglen = c->taglen; p.table = c->d_table.p; p.slot_mask = c->slots - 1; p.max_keys = c->max_keys; p.cs = c->d_cs.p;
     p.cursor_in = cursor_in; p.cursor_out = cursor_out; p.combine = (uint32_t)c->combine;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(p.ntiles, (uint64_t)td_handle_num_cu(c->h) * 8);
     hipLaunchKernelGGL(tdc::k_census, dim3(grid), dim3(tdk::BLOCK), c->bblob_bytes, stream, p);
@@ -418,7 +413,7 @@ int census_check(Census *c, const unsigned long long *cs) {
 int census_sync_stats(Census *c, unsigned long long cs[tdc::CS_NWORDS]) {
     if (c->dead) return td_fail_internal(c->dead, c->dead_msg.c_str());
     TD_HIPCHK(hipDeviceSynchronize());
-    TD_HIPCHK(hipMemcpy(cs, c->d_cs, tdc::CS_NWORDS * 8, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(cs, c->d_cs.p, tdc::CS_NWORDS * 8, hipMemcpyDeviceToHost));
     return census_check(c, cs);
 }
 
@@ -463,12 +458,12 @@ int td_census_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, 
     c->slots = slots; c->max_keys = slots / 4 * 3;
     const char *env = getenv("TAGDIG_CENSUS_COMBINE");
     c->combine = env ? (atoi(env) != 0) : 1;
-    hipError_t e = hipMalloc((void **)&c->d_bblob, bytes);
-    if (e == hipSuccess) e = hipMemcpy(c->d_bblob, blob, bytes, hipMemcpyHostToDevice);
+    hipError_t e = c->d_bblob.alloc((bytes + 3) / 4);
+    if (e == hipSuccess) e = hipMemcpy(c->d_bblob.p, blob, bytes, hipMemcpyHostToDevice);
     free(blob);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_cs, tdc::CS_NWORDS * 8);
+    if (e == hipSuccess) e = c->d_cs.alloc(tdc::CS_NWORDS);
     if (e != hipSuccess) { delete c; (void)hipGetLastError(); return td_fail_internal(TD_E_HIP, hipGetErrorString(e)); }
-    e = hipMalloc((void **)&c->d_table, slots * c->slot_words() * 8);
+    e = c->d_table.alloc(slots * c->slot_words());
     if (e != hipSuccess) {
         delete c; (void)hipGetLastError();
         return td_fail_internal(TD_E_HIP, ("no device memory for a census table of " + std::to_string(slots) + " slots").c_str());
@@ -527,27 +522,26 @@ int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *
     if (min_count == 0) min_count = 1;
     const uint32_t two = c->taglen > 32 ? 1u : 0u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((c->slots + 255) / 256, (uint64_t)td_handle_num_cu(h) * 8);
-    unsigned long long *d_n = nullptr, *d_out = nullptr;
-    TD_HIPCHK(hipMalloc((void **)&d_n, 8));
-    struct Free { unsigned long long *&a, *&b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } guard{d_n, d_out};
+    tdi::DevBuf<unsigned long long> d_n, d_out;
+    TD_HIPCHK(d_n.alloc(1));
     unsigned long long n = cs[tdc::CS_DISTINCT];
     // how many there are: a pass that keeps nothing -- run when only the number is asked for, or when room for every
     // distinct window (the bound that needs no pass) would be more than 1 GiB
     const bool count_first = min_count > 1 && (capacity == 0 || n * 24 > (1ull << 30));
     if (count_first) {
-        TD_HIPCHK(hipMemset(d_n, 0, 8));
-        hipLaunchKernelGGL(tdc::k_census_compact, dim3(grid), dim3(256), 0, 0, c->d_table, c->slots, two, (unsigned long long)min_count,
-                           (unsigned long long *)nullptr, 0ull, d_n);
+        TD_HIPCHK(hipMemset(d_n.p, 0, 8));
+        hipLaunchKernelGGL(tdc::k_census_compact, dim3(grid), dim3(256), 0, 0, c->d_table.p, c->slots, two, (unsigned long long)min_count,
+                           (unsigned long long *)nullptr, 0ull, d_n.p);
         TD_HIPCHK(hipGetLastError());
-        TD_HIPCHK(hipMemcpy(&n, d_n, 8, hipMemcpyDeviceToHost));
+        TD_HIPCHK(hipMemcpy(&n, d_n.p, 8, hipMemcpyDeviceToHost));
     }
     if (n == 0 || capacity == 0) { *n_out = n; return TD_OK; }
-    TD_HIPCHK(hipMalloc((void **)&d_out, n * 24));
-    TD_HIPCHK(hipMemset(d_n, 0, 8));
-    hipLaunchKernelGGL(tdc::k_census_compact, dim3(grid), dim3(256), 0, 0, c->d_table, c->slots, two, (unsigned long long)min_count, d_out, n, d_n);
+    TD_HIPCHK(d_out.alloc(n * 3));
+    TD_HIPCHK(hipMemset(d_n.p, 0, 8));
+    hipLaunchKernelGGL(tdc::k_census_compact, dim3(grid), dim3(256), 0, 0, c->d_table.p, c->slots, two, (unsigned long long)min_count, d_out.p, n, d_n.p);
     TD_HIPCHK(hipGetLastError());
     unsigned long long n2 = 0;
-    TD_HIPCHK(hipMemcpy(&n2, d_n, 8, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(&n2, d_n.p, 8, hipMemcpyDeviceToHost));
     if (count_first || min_count <= 1 ? n2 != n : n2 > n)
         return td_fail_internal(TD_E_INTERNAL, "census compaction found another number of entries than the table holds");
     n = n2;
@@ -555,7 +549,7 @@ int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *
     if (n == 0) return TD_OK;
     struct Ent { uint64_t hi, lo, count; };
     std::vector<Ent> ents(n);
-    TD_HIPCHK(hipMemcpy(ents.data(), d_out, n * 24, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(ents.data(), d_out.p, n * 24, hipMemcpyDeviceToHost));
     for (Ent &e : ents) { e.hi = acgt_order(e.hi); e.lo = acgt_order(e.lo); }
     // count descending, then sequence ascending (A < C < G < T)
     std::sort(ents.begin(), ents.end(), [](const Ent &a, const Ent &b) {

@@ -274,15 +274,15 @@ extern "C" int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, 
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     struct Slot {
         tdi::PinBuf<uint8_t> pin; tdi::PinBuf<Md5Job> pin_jobs; tdi::DevBuf<uint8_t> dev; tdi::DevBuf<Md5Job> dev_jobs;
-        tdi::Events<1> up; tdi::Events<2> k; bool busy = false;         // up: no timing; k: around the kernel
+        tdi::Event up; tdi::Events<2> k; bool busy = false;         // up: no timing; k: around the kernel
     } slot[2];
     tdi::DevBuf<uint32_t> d_state;
     // two streams: the upload of round r + 1 runs beside the kernel of round r (an event orders a round's kernel
     // behind its upload; a slot is refilled only after its kernel is through)
-    hipStream_t st = nullptr, sc = nullptr;
-    struct StreamGuard { hipStream_t &s; ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } } guard{st}, guard_copy{sc};
-    TD_HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    TD_HIPCHK(hipStreamCreateWithFlags(&sc, hipStreamNonBlocking));
+    tdi::Stream kernel_stream, copy_stream;     // (declared behind the buffers: waited for and destroyed before those are freed)
+    TD_HIPCHK(kernel_stream.create());
+    TD_HIPCHK(copy_stream.create());
+    const hipStream_t st = kernel_stream.s, sc = copy_stream.s;
     TD_HIPCHK(d_state.alloc(4 * (size_t)n));
     TD_HIPCHK(init_states(d_state.p, n));
     for (auto &s : slot) {
@@ -290,7 +290,7 @@ extern "C" int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, 
         TD_HIPCHK(s.pin_jobs.alloc(n));
         TD_HIPCHK(s.dev.alloc(cap));
         TD_HIPCHK(s.dev_jobs.alloc(n));
-        TD_HIPCHK(hipEventCreateWithFlags(&s.up.e[0], hipEventDisableTiming));
+        TD_HIPCHK(s.up.create(hipEventDisableTiming));
         TD_HIPCHK(s.k.create());
     }
     auto retire = [&](Slot &s) -> hipError_t {          // wait until the slot's kernel is through; book its time
@@ -357,8 +357,8 @@ extern "C" int td_md5_files(td_handle *h, const char *const *paths, uint32_t n, 
         if (bad.load() != UINT32_MAX) return io_fail(bad.load(), "cannot read", bad_errno.load());
         TD_HIPCHK(hipMemcpyAsync(s.dev.p, s.pin.p, used, hipMemcpyHostToDevice, sc));
         TD_HIPCHK(hipMemcpyAsync(s.dev_jobs.p, s.pin_jobs.p, njobs * sizeof(Md5Job), hipMemcpyHostToDevice, sc));
-        TD_HIPCHK(hipEventRecord(s.up.e[0], sc));
-        TD_HIPCHK(hipStreamWaitEvent(st, s.up.e[0], 0));
+        TD_HIPCHK(hipEventRecord(s.up.e, sc));
+        TD_HIPCHK(hipStreamWaitEvent(st, s.up.e, 0));
         TD_HIPCHK(hipEventRecord(s.k.e[0], st));
         k_md5_update<true><<<waves(njobs), 64, 0, st>>>(s.dev.p, s.dev_jobs.p, njobs, d_state.p);
         TD_HIPCHK(hipGetLastError());

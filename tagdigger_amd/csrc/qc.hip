@@ -406,8 +406,8 @@ constexpr uint32_t QC_FLUSH_DEFAULT = 4096, QC_FLUSH_MAX = 1u << 20;
 struct Qc {
     td_handle *h = nullptr;
     uint32_t C = 0, nbar = 0, bblob_bytes = 0, off_bmeta = 0, off_bdir = 0;
-    uint32_t *d_bblob = nullptr;
-    unsigned long long *d_all = nullptr;      // QS_* | barcode rows | base_cycle | qual_cycle | length | meanq
+    tdi::DevBuf<uint32_t> d_bblob;
+    tdi::DevBuf<unsigned long long> d_all;    // QS_* | barcode rows | base_cycle | qual_cycle | length | meanq
     uint64_t file_records = 0;                // td_qc_file's bound (the readers are handed one record more)
     bool used = false;                        // something has been added since td_qc_begin
     int dead = 0;                             // the code every call answers with after a failure, until td_qc_begin
@@ -417,22 +417,18 @@ struct Qc {
     size_t n_qual() const { return ((size_t)C + 1) * tdq::NQ; }
     size_t n_len() const { return (size_t)C + 1; }
     size_t words() const { return tdq::QS_NWORDS + n_bar() + n_base() + n_qual() + n_len() + tdq::NMEAN; }
-    unsigned long long *d_qs() const { return d_all; }
-    unsigned long long *d_bar() const { return d_all + tdq::QS_NWORDS; }
+    unsigned long long *d_qs() const { return d_all.p; }
+    unsigned long long *d_bar() const { return d_all.p + tdq::QS_NWORDS; }
     unsigned long long *d_base() const { return d_bar() + n_bar(); }
     unsigned long long *d_qual() const { return d_base() + n_base(); }
     unsigned long long *d_len() const { return d_qual() + n_qual(); }
     unsigned long long *d_meanq() const { return d_len() + n_len(); }
-    ~Qc() {
-        if (d_bblob) (void)hipFree(d_bblob);
-        if (d_all) (void)hipFree(d_all);
-    }
 };
 
 Qc *qc_of(td_handle *h) { return h ? (Qc *)*td_handle_qc(h) : nullptr; }
 
 int qc_zero(Qc *q, hipStream_t s) {
-    TD_HIPCHK(hipMemsetAsync(q->d_all, 0, q->words() * 8, s));
+    TD_HIPCHK(hipMemsetAsync(q->d_all.p, 0, q->words() * 8, s));
     TD_HIPCHK(hipStreamSynchronize(s));
     q->used = false;
     return TD_OK;
@@ -451,7 +447,7 @@ int qc_launch(Qc *q, const void *d_fastq, uint64_t nbytes, uint64_t first_line, 
     p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
     p.max_records = std::min<uint64_t>(max_records, 1ull << 61);
     p.prefix = prefix; p.ntiles = (uint32_t)((nbytes + tdq::TILE - 1) / tdq::TILE);
-    p.bblob = q->d_bblob; p.bblob_bytes = q->bblob_bytes; p.off_bmeta = q->off_bmeta; p.off_bdir = q->off_bdir;
+    p.bblob = q->d_bblob.p; p.bblob_bytes = q->bblob_bytes; p.off_bmeta = q->off_bmeta; p.off_bdir = q->off_bdir;
     p.nbar = q->nbar; p.C = q->C;
     p.bar_lds = q->nbar + 1 <= tdq::BAR_LDS_ROWS ? 1u : 0u;
     // the window: as many cycles as leave room for a second workgroup on the CU, within QC_WIN_MIN .. QC_WIN
@@ -517,10 +513,10 @@ int td_qc_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint
         if (baroff[b] > 32) { free(blob); return td_fail_internal(TD_E_LIMIT, "barcode longer than 32 bases"); }
     Qc *q = new Qc();
     q->h = h; q->C = max_cycles; q->nbar = barnum; q->bblob_bytes = bytes; q->off_bmeta = off_bmeta; q->off_bdir = off_bdir;
-    hipError_t e = hipMalloc((void **)&q->d_bblob, bytes);
-    if (e == hipSuccess) e = hipMemcpy(q->d_bblob, blob, bytes, hipMemcpyHostToDevice);
+    hipError_t e = q->d_bblob.alloc((bytes + 3) / 4);
+    if (e == hipSuccess) e = hipMemcpy(q->d_bblob.p, blob, bytes, hipMemcpyHostToDevice);
     free(blob);
-    if (e == hipSuccess) e = hipMalloc((void **)&q->d_all, q->words() * 8);
+    if (e == hipSuccess) e = q->d_all.alloc(q->words());
     if (e != hipSuccess) { delete q; (void)hipGetLastError(); return td_fail_internal(TD_E_HIP, hipGetErrorString(e)); }
     rc = qc_zero(q, (hipStream_t)td_handle_work_stream(h));
     if (rc) { delete q; return rc; }

@@ -11,6 +11,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <chrono>
@@ -36,19 +37,17 @@
 #include "piece_sink.hpp"
 #include "td_internal.hpp"                      // the hidden hooks defined below, as the other translation units see them
 
+using tdi::DevBuf;
+using tdi::PinBuf;
+using tdi::Event;
+using tdi::Stream;
+
 namespace {
 
 thread_local std::string g_err;
 thread_local uint32_t g_bad = 0;
 
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
-
-#define HIPCHK(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail(TD_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));        \
-    } while (0)
 
 // base codes must match the device's (byte >> 1) & 3:  A 0, C 1, T 2, G 3
 inline int base_code(char c) {
@@ -128,19 +127,6 @@ struct Resolver {
     }
 };
 
-template <typename T> struct DevBuf {
-    T *p = nullptr; size_t n = 0;
-    int ensure(size_t want) {
-        if (want <= n && p) return TD_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        HIPCHK(hipMalloc(&p, std::max<size_t>(want, 1) * sizeof(T)));
-        n = want;
-        return TD_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 constexpr int W_CHOICES[] = {1, 2, 3, 4, 6, 10};
 constexpr uint32_t MAX_SHORT = 16;
 constexpr size_t LDS_BUDGET = 64 * 1024;     // per workgroup
@@ -148,17 +134,19 @@ constexpr size_t STATS_SLOTS = 32;           // TD_STAT_NSTATS public + diagnost
 
 }  // namespace
 
+// Everything the handle allocates is a member that frees itself.  Members go in reverse order of declaration: the streams
+// come first, so they outlive every buffer and event.
 struct td_handle {
+    Stream copy_stream, work_stream;
+    // (one copy engine moves 22-30 GB/s out of pinned memory that lies on the far socket, two or three together 50: large
+    // uploads are spread over copy_stream and these; TAGDIG_COPY_STREAMS = 1..3, default 3)
+    Stream side_copy[2]; Event side_done[2];
     int device = 0;
     const td_piece_sink *sink = nullptr;
     void *census = nullptr;                   // csrc/census.hip's state (td_census_begin .. td_census_end)
     void *qc = nullptr;                       // csrc/qc.hip's state (td_qc_begin .. td_qc_end)
     uint32_t qc_flush_tiles = 0;              // (tests: tiles between two merges of k_qc's LDS tables; 0 = the built-in 4096)
     int num_cu = 256;
-    hipStream_t copy_stream = nullptr, work_stream = nullptr;
-    // (one copy engine moves 22-30 GB/s out of pinned memory that lies on the far socket, two or three together 50: large
-    // uploads are spread over copy_stream and these; TAGDIG_COPY_STREAMS = 1..3, default 3)
-    hipStream_t side_copy[2] = {nullptr, nullptr}; hipEvent_t side_done[2] = {nullptr, nullptr};
     // index
     bool have_index = false;
     bool counted = false;                     // something has been counted since the results were last zeroed
@@ -172,13 +160,13 @@ struct td_handle {
     // results
     DevBuf<uint32_t> d_counts;
     DevBuf<unsigned long long> d_counts64;
-    uint32_t *bound_counts = nullptr;
+    uint32_t *bound_counts = nullptr;         // the caller's matrix (td_bind_counts): not ours to free
     bool used64 = false;
     DevBuf<unsigned long long> d_stats;       // TD_STAT_NSTATS
     // progress windows (option "progress"): per 50 000 reads, how many had a barcode / a tag (reference :268-271)
     int progress = 0;
     uint32_t zb_members = 1u << 30;           // (tests: BGZF members per GPU batch, below the built-in 49 152)
-    unsigned long long *pin_cursor = nullptr; // pinned: the line index after the newest counted BGZF batch
+    PinBuf<unsigned long long> pin_cursor;    // pinned, [2]: the line index after the newest counted BGZF batch
     int split_kernel = 2;                     // 2: k_split2 (tile in LDS), 1: k_split
     bool sp_sites_acgt = false;
     int last_fast_tile_kb = 0;                // tile size of the last free-running count launch (0: it took another path)
@@ -203,8 +191,8 @@ struct td_handle {
     bool have_splitter = false;
     std::vector<std::string> sp_barcodes;
     // td_split_file's two staging slots, kept between calls (pinned allocations cost tens of milliseconds)
-    struct SplitSlot { uint8_t *pin = nullptr, *dev = nullptr; int2 *res_dev = nullptr, *res_pin = nullptr; size_t n = 0;
-                       hipEvent_t done = nullptr; bool pending = false; } sp_slot[2];
+    struct SplitSlot { PinBuf<uint8_t> pin; DevBuf<uint8_t> dev; DevBuf<int2> res_dev; PinBuf<int2> res_pin; size_t n = 0;
+                       Event done; bool pending = false; } sp_slot[2];
     uint32_t sp_bblob_bytes = 0, sp_off_bmeta = 0, sp_off_bdir = 0, sp_cutlen = 0;
     unsigned long long sp_site[2] = {0, 0};
     uint32_t sp_site_len[2] = {0, 0};
@@ -217,21 +205,23 @@ struct td_handle {
     DevBuf<uint8_t> d_sp_pool;
     DevBuf<uint4> d_fixlist;
     DevBuf<uint32_t> d_rowmap;                // td_fold_rows: sample row of every barcode row
-    // BGZF members inflated on the GPU (count_bgzf_gpu): two batches in flight
-    struct ZSlot { uint8_t *d_in = nullptr, *d_out = nullptr; tdinf::Member *pin_mem = nullptr, *d_mem = nullptr;
-                   uint32_t *d_status = nullptr, *pin_status = nullptr; uint8_t *pin_tail = nullptr; hipEvent_t copied = nullptr; } zslot[2];
-    struct ZPiece { uint8_t *pin = nullptr; hipEvent_t sent = nullptr; bool busy = false; } zpiece[2];     // pinned staging of the compressed bytes
+    // BGZF members inflated on the GPU (count_bgzf_gpu): two batches in flight.  The batch buffers are sized from the file,
+    // kept between files and replaced together when a larger file comes (a new Bgzf: the old one frees them all)
+    struct ZSlot { DevBuf<uint8_t> d_in, d_out; PinBuf<tdinf::Member> pin_mem; DevBuf<tdinf::Member> d_mem;
+                   DevBuf<uint32_t> d_status; PinBuf<uint32_t> pin_status; PinBuf<uint8_t> pin_tail; Event copied; };
+    struct ZPiece { PinBuf<uint8_t> pin; Event sent; bool busy = false; };     // pinned staging of the compressed bytes
+    struct Bgzf { ZSlot slot[2]; ZPiece piece[2]; DevBuf<uint8_t> d_scratch;
+                  uint32_t cap_members = 0; size_t cap_in = 0; };              // (what the buffers were allocated for)
+    std::unique_ptr<Bgzf> bgzf{new Bgzf()};   // (never null)
     ZPiece ldpiece[2];                        // td_load_file_range's pinned staging
     // ordinary gzip: symbols decoded by the host, resolved on the GPU (count_gzip_dev): two batches in flight
     struct GSlot { DevBuf<uint8_t> d_sym, d_out, d_win; DevBuf<tdgz::Block> d_blk; DevBuf<uint32_t> d_crc;
-                   tdgz::Block *pin_blk = nullptr; uint32_t *pin_crc = nullptr; uint8_t *pin_tail = nullptr; size_t pin_cap = 0; hipEvent_t done = nullptr;
-                   hipEvent_t copied = nullptr; } gslot[2];
+                   PinBuf<tdgz::Block> pin_blk; PinBuf<uint32_t> pin_crc; PinBuf<uint8_t> pin_tail; size_t pin_cap = 0; Event done, copied; } gslot[2];
     DevBuf<uint32_t> d_gzflag;
     // ordinary gzip decoded on the GPU (count_gzip_gpu, gz_gpu.hpp): the whole file's buffers, kept between files
     struct GzGpu { DevBuf<uint8_t> d_in, d_in2, d_out, d_win, d_carry, d_segwin; DevBuf<uint16_t> d_maps; DevBuf<uint32_t> d_tok, d_crc; DevBuf<uint16_t> d_sym; DevBuf<tdgz2::Chunk> d_chunks;
-                   DevBuf<tdgz2::ChunkOut> d_res; DevBuf<uint64_t> d_found, d_symoff; DevBuf<tdgz::Block> d_blk;
-                   void release() { d_in.release(); d_in2.release(); d_out.release(); d_win.release(); d_carry.release(); d_tok.release(); d_crc.release(); d_sym.release();
-                                    d_chunks.release(); d_res.release(); d_found.release(); d_symoff.release(); d_blk.release(); d_segwin.release(); d_maps.release(); } } gzgpu;
+                   DevBuf<tdgz2::ChunkOut> d_res; DevBuf<uint64_t> d_found, d_symoff; DevBuf<tdgz::Block> d_blk; };
+    std::unique_ptr<GzGpu> gzgpu{new GzGpu()};    // (never null; option "gz_gpu_release": a new GzGpu, the old one frees them all)
     bool gz_attr_done = false;
     // one gzip file over several devices: this rank's share between td_gz_shard_open / _decode / _resolve
     struct GzShard { bool open = false, decoded = false; std::string path; uint64_t n = 0, base = 0, in_bits = 0, nwords = 0, start_rel = 0;
@@ -247,8 +237,7 @@ struct td_handle {
     uint32_t gz_gpu_seg_kb = 1u << 20, gz_gpu_margin_kb = 16384;      // ... a segment of compressed data (1 GiB), and how far its last chunk may run past it
     int gz_gpu_false_every = 0;               // (tests) every n-th found block start is moved by some bits: a false start
     int gpu_resolve = 1;                      // ordinary gzip of 8 MiB and more: markers -> bytes and CRC-32 on the GPU (0: all on the host)
-    uint8_t *d_zscratch = nullptr; uint32_t *d_crctab = nullptr;
-    uint32_t zcap_members = 0; size_t zcap_in = 0;   // what the batch buffers above were allocated for
+    DevBuf<uint32_t> d_crctab;                // slicing-by-4 CRC-32 tables (ensure_bgzf_buffers), kept for the handle's life
     int gpu_inflate = 1;                      // BGZF input: inflate on the GPU (0: member-parallel on the host)
     int gpu_inflate_crc = 1;                  // ... and check every member's CRC-32 there
     uint32_t max_need = 0;                    // bases from a read's start that the matcher may look at
@@ -267,35 +256,12 @@ struct td_handle {
     int stagger = 0;
     int prio = 0xE4;            // wave priority per phase of the fast path: A 0, B-C 1, D 2, end of A 3 (kernel_fast.hpp set_prio)
     // timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<Event, Event>> ev_pool;
     size_t ev_used = 0;
     const void *occ_fn = nullptr; size_t occ_lds = 0; int occ_val = 1;
 };
 
 namespace {
-
-// count_bgzf_gpu's batch buffers (sized from the file, kept on the handle between files)
-void release_bgzf_buffers(td_handle *h) {
-    for (auto &zp : h->zpiece) {
-        if (zp.pin) (void)hipHostFree(zp.pin);
-        if (zp.sent) (void)hipEventDestroy(zp.sent);
-        zp = td_handle::ZPiece();
-    }
-    for (auto &z : h->zslot) {
-        if (z.d_in) (void)hipFree(z.d_in);
-        if (z.d_out) (void)hipFree(z.d_out);
-        if (z.pin_mem) (void)hipHostFree(z.pin_mem);
-        if (z.d_mem) (void)hipFree(z.d_mem);
-        if (z.d_status) (void)hipFree(z.d_status);
-        if (z.pin_status) (void)hipHostFree(z.pin_status);
-        if (z.pin_tail) (void)hipHostFree(z.pin_tail);
-        if (z.copied) (void)hipEventDestroy(z.copied);
-        z = td_handle::ZSlot();
-    }
-    if (h->d_zscratch) (void)hipFree(h->d_zscratch);
-    h->d_zscratch = nullptr;
-    h->zcap_members = 0; h->zcap_in = 0;
-}
 
 using KFn = void (*)(const tdk::KParams);
 template <int CPT, bool TASSEL> KFn pick_w(int W) {
@@ -401,11 +367,11 @@ size_t lds_bytes(const td_handle *h, int tile_kb) {
 int zero_results(td_handle *h) {
     // (the handle's own matrix may be left over from a smaller index while a caller's matrix is bound: only what is
     // allocated is cleared; td_bind_counts(NULL) grows and clears it before it is used again)
-    if (h->d_counts.p) HIPCHK(hipMemsetAsync(h->d_counts.p, 0, std::min<size_t>((size_t)h->barnum * h->ntags, h->d_counts.n) * 4, h->work_stream));
-    if (h->d_counts64.p) HIPCHK(hipMemsetAsync(h->d_counts64.p, 0, (size_t)h->barnum * h->ntags * 8, h->work_stream));
-    HIPCHK(hipMemsetAsync(h->d_stats.p, 0, STATS_SLOTS * 8, h->work_stream));
-    if (h->d_win.p) HIPCHK(hipMemsetAsync(h->d_win.p, 0, h->d_win.n * 8, h->work_stream));
-    HIPCHK(hipStreamSynchronize(h->work_stream));
+    if (h->d_counts.p) TD_HIPCHK(hipMemsetAsync(h->d_counts.p, 0, std::min<size_t>((size_t)h->barnum * h->ntags, h->d_counts.n) * 4, h->work_stream.s));
+    if (h->d_counts64.p) TD_HIPCHK(hipMemsetAsync(h->d_counts64.p, 0, (size_t)h->barnum * h->ntags * 8, h->work_stream.s));
+    TD_HIPCHK(hipMemsetAsync(h->d_stats.p, 0, STATS_SLOTS * 8, h->work_stream.s));
+    if (h->d_win.p) TD_HIPCHK(hipMemsetAsync(h->d_win.p, 0, h->d_win.n * 8, h->work_stream.s));
+    TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
     std::fill(h->host_acc.begin(), h->host_acc.end(), 0);
     h->bytes_since_flush = 0;
     h->used64 = false;
@@ -418,9 +384,9 @@ int flush_counts(td_handle *h) {
     if (h->bound_counts || !h->d_counts.p) return TD_OK;
     size_t cells = (size_t)h->barnum * h->ntags;
     std::vector<uint32_t> tmp(cells);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(tmp.data(), h->d_counts.p, cells * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(h->d_counts.p, 0, cells * 4));
+    TD_HIPCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipMemcpy(tmp.data(), h->d_counts.p, cells * 4, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemset(h->d_counts.p, 0, cells * 4));
     if (h->host_acc.size() != cells) h->host_acc.assign(cells, 0);
     for (size_t i = 0; i < cells; i++) h->host_acc[i] += tmp[i];
     h->bytes_since_flush = 0;
@@ -471,12 +437,12 @@ int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
     }
     if (tassel) {
         if (!h->d_counts64.p) {
-            int rc = h->d_counts64.ensure((size_t)h->barnum * h->ntags); if (rc) return rc;
-            HIPCHK(hipMemsetAsync(h->d_counts64.p, 0, (size_t)h->barnum * h->ntags * 8, stream));
+            TD_HIPCHK(h->d_counts64.ensure((size_t)h->barnum * h->ntags));
+            TD_HIPCHK(hipMemsetAsync(h->d_counts64.p, 0, (size_t)h->barnum * h->ntags * 8, stream));
         }
         h->used64 = true;
     }
-    { int rc = h->d_state.ensure(ntiles); if (rc) return rc; }
+    TD_HIPCHK(h->d_state.ensure(ntiles));
 
     tdk::KParams p{};
     p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
@@ -504,52 +470,51 @@ int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
         if (need > h->d_win.n) {
             const size_t cap = (size_t)std::max<uint64_t>(need * 2, 1u << 16);
             DevBuf<unsigned long long> bigger;
-            int rc = bigger.ensure(cap); if (rc) return rc;
-            HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipMemset(bigger.p, 0, cap * 8));
-            if (h->d_win.p) HIPCHK(hipMemcpy(bigger.p, h->d_win.p, h->d_win.n * 8, hipMemcpyDeviceToDevice));
-            h->d_win.release();
-            h->d_win = bigger;
+            TD_HIPCHK(bigger.alloc(cap));
+            TD_HIPCHK(hipStreamSynchronize(stream));
+            TD_HIPCHK(hipMemset(bigger.p, 0, cap * 8));
+            if (h->d_win.p) TD_HIPCHK(hipMemcpy(bigger.p, h->d_win.p, h->d_win.n * 8, hipMemcpyDeviceToDevice));
+            h->d_win.swap(bigger);                          // (the old windows go with `bigger`)
         }
         p.win = h->d_win.p; p.win_cap = (uint32_t)std::min<size_t>(h->d_win.n, 0xFFFFFFFFu);
     }
     h->last_fast_tile_kb = use_fast ? tile_kb : 0;        // (td_count_and_split_device: are d_tileinfo's counts the splitter's tiles?)
     h->last_fast_ntiles = use_fast ? ntiles : 0;
     if (use_fast) {
-        int rc = h->d_tileinfo.ensure(ntiles); if (rc) return rc;
+        TD_HIPCHK(h->d_tileinfo.ensure(ntiles));
         const uint32_t fix_cap = 3u * ntiles + 8u;
-        rc = h->d_fixlist.ensure(fix_cap); if (rc) return rc;
-        rc = h->d_nfix.ensure(4); if (rc) return rc;
+        TD_HIPCHK(h->d_fixlist.ensure(fix_cap));
+        TD_HIPCHK(h->d_nfix.ensure(4));
         {   // the tiles whose window (tile + halo) crosses the end of the buffer: a zero-padded copy
             const uint64_t TILE = (uint64_t)tile_kb * 1024;
             const uint64_t inside = nbytes >= TILE + h->halo ? (nbytes - h->halo) / TILE : 0;
             const size_t tail_cap = 2 * (size_t)TILE + 2 * (size_t)h->halo + 256;
-            rc = h->d_tail.ensure(tail_cap); if (rc) return rc;
+            TD_HIPCHK(h->d_tail.ensure(tail_cap));
             const uint64_t start = inside * TILE;
             if (nbytes - start > tail_cap) return fail(TD_E_INTERNAL, "tail copy larger than its buffer");
-            HIPCHK(hipMemsetAsync(h->d_tail.p, 0, tail_cap, stream));
+            TD_HIPCHK(hipMemsetAsync(h->d_tail.p, 0, tail_cap, stream));
             if (nbytes > start)
-                HIPCHK(hipMemcpyAsync(h->d_tail.p, (const uint8_t *)d_fastq + start, nbytes - start, hipMemcpyDeviceToDevice, stream));
+                TD_HIPCHK(hipMemcpyAsync(h->d_tail.p, (const uint8_t *)d_fastq + start, nbytes - start, hipMemcpyDeviceToDevice, stream));
             p.tail_buf = h->d_tail.p; p.tail_tile = (uint32_t)inside;
         }
         tdk::FParams fp{};
         fp.k = p; fp.tile_info = h->d_tileinfo.p; fp.fixlist = h->d_fixlist.p; fp.nfix = h->d_nfix.p; fp.fix_cap = fix_cap;
         if (h->progress) {
-            rc = h->d_tilesums.ensure(ntiles); if (rc) return rc;
-            HIPCHK(hipMemsetAsync(h->d_tilesums.p, 0, (size_t)ntiles * 4, stream));
+            TD_HIPCHK(h->d_tilesums.ensure(ntiles));
+            TD_HIPCHK(hipMemsetAsync(h->d_tilesums.p, 0, (size_t)ntiles * 4, stream));
             fp.tile_sums = h->d_tilesums.p;
         }
-        HIPCHK(hipMemsetAsync(h->d_nfix.p, 0, 4, stream));
+        TD_HIPCHK(hipMemsetAsync(h->d_nfix.p, 0, 4, stream));
         FFn ffn = gen4 ? pick_fast4(h->W, h->nch2, h->progress != 0) : gen2 ? pick_fast2(tile_kb, h->W, h->nch2, h->progress != 0) : pick_fast(tile_kb, h->W, false), fixfn = pick_fix(tile_kb, h->W);
         const size_t flds = gen4 ? lds_bytes_fast4(h) : gen2 ? lds_bytes_fast2(h, tile_kb) : lds_bytes_fast(h, tile_kb), fixlds = lds_bytes_fast(h, tile_kb);
         const unsigned main_threads = gen4 ? (unsigned)tdk::F4_BLOCK : (unsigned)tdk::FBLOCK, fix_threads = tile_kb == 12 ? 128u : (unsigned)tdk::FBLOCK;
-        if (flds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)ffn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-        if (fixlds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)fixfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fixlds));
+        if (flds > 48 * 1024) TD_HIPCHK(hipFuncSetAttribute((const void *)ffn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
+        if (fixlds > 48 * 1024) TD_HIPCHK(hipFuncSetAttribute((const void *)fixfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fixlds));
         int bpc = h->blocks_per_cu;
         if (bpc <= 0) {
             if (h->occ_fn != (const void *)ffn || h->occ_lds != flds) {
                 int occ = 0;
-                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)ffn, (int)main_threads, flds));
+                TD_HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)ffn, (int)main_threads, flds));
                 h->occ_fn = (const void *)ffn; h->occ_lds = flds; h->occ_val = std::max(1, occ);
             }
             bpc = h->occ_val;
@@ -559,16 +524,16 @@ int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->timing) {
             if (h->ev_used == h->ev_pool.size()) {
-                hipEvent_t a, b;
-                HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-                h->ev_pool.emplace_back(a, b);
+                Event a, b;
+                TD_HIPCHK(a.create()); TD_HIPCHK(b.create());
+                h->ev_pool.emplace_back(std::move(a), std::move(b));
             }
-            e0 = h->ev_pool[h->ev_used].first; e1 = h->ev_pool[h->ev_used].second; h->ev_used++;
-            HIPCHK(hipEventRecord(e0, stream));
+            e0 = h->ev_pool[h->ev_used].first.e; e1 = h->ev_pool[h->ev_used].second.e; h->ev_used++;
+            TD_HIPCHK(hipEventRecord(e0, stream));
         }
         if (gen4 && !h->f4_nprod) {
             // (the tail copy holds the bytes of a buffer shorter than a tile)
-            int rc4 = h->d_f4np.ensure(4); if (rc4) return rc4;
+            TD_HIPCHK(h->d_f4np.ensure(4));
             hipLaunchKernelGGL(tdk::k_f4_estimate, dim3(1), dim3(256), 0, stream, (const uint8_t *)d_fastq, nbytes, h->d_f4np.p);
             fp.k.f4_nprod_dev = h->d_f4np.p;
         }
@@ -580,31 +545,31 @@ int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
             hipLaunchKernelGGL(tdk::k_resolve, dim3(rblocks), dim3(1024), 0, stream, fp, super);
         }
         hipLaunchKernelGGL(fixfn, dim3(std::min<uint32_t>(grid, (uint32_t)h->num_cu * 2)), dim3(fix_threads), fixlds, stream, fp);
-        HIPCHK(hipGetLastError());
-        if (h->timing) HIPCHK(hipEventRecord(e1, stream));
+        TD_HIPCHK(hipGetLastError());
+        if (h->timing) TD_HIPCHK(hipEventRecord(e1, stream));
         return TD_OK;
     }
 
-    HIPCHK(hipMemsetAsync(h->d_ticket.p, 0, 4, stream));
+    TD_HIPCHK(hipMemsetAsync(h->d_ticket.p, 0, 4, stream));
     if (h->prescan) {
-        int rc = h->d_tilecounts.ensure(ntiles); if (rc) return rc;
+        TD_HIPCHK(h->d_tilecounts.ensure(ntiles));
         uint32_t g = std::min<uint32_t>(ntiles, (uint32_t)h->num_cu * 8);
         if (tile_kb == 32) hipLaunchKernelGGL((tdk::k_count_lines<8>), dim3(g), dim3(tdk::BLOCK), 0, stream, p.buf, nbytes, ntiles, h->d_tilecounts.p);
         else hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, stream, p.buf, nbytes, ntiles, h->d_tilecounts.p);
         hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, stream, h->d_tilecounts.p, ntiles, h->d_state.p, (unsigned long long *)nullptr);
     } else {
-        HIPCHK(hipMemsetAsync(h->d_state.p, 0, (size_t)ntiles * 8, stream));
+        TD_HIPCHK(hipMemsetAsync(h->d_state.p, 0, (size_t)ntiles * 8, stream));
     }
 
     KFn fn = pick_kernel(tile_kb, h->W, tassel);
     const size_t lds = lds_bytes(h, tile_kb);
     if (lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TD_HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int bpc = h->blocks_per_cu;
     if (bpc <= 0) {
         if (h->occ_fn != (const void *)fn || h->occ_lds != lds) {
             int occ = 0;
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, tdk::BLOCK, lds));
+            TD_HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, tdk::BLOCK, lds));
             h->occ_fn = (const void *)fn; h->occ_lds = lds; h->occ_val = std::max(1, occ);
         }
         bpc = h->occ_val;
@@ -614,16 +579,16 @@ int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->timing) {
         if (h->ev_used == h->ev_pool.size()) {
-            hipEvent_t a, b;
-            HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-            h->ev_pool.emplace_back(a, b);
+            Event a, b;
+            TD_HIPCHK(a.create()); TD_HIPCHK(b.create());
+            h->ev_pool.emplace_back(std::move(a), std::move(b));
         }
-        e0 = h->ev_pool[h->ev_used].first; e1 = h->ev_pool[h->ev_used].second; h->ev_used++;
-        HIPCHK(hipEventRecord(e0, stream));
+        e0 = h->ev_pool[h->ev_used].first.e; e1 = h->ev_pool[h->ev_used].second.e; h->ev_used++;
+        TD_HIPCHK(hipEventRecord(e0, stream));
     }
     hipLaunchKernelGGL(fn, dim3(grid), dim3(tdk::BLOCK), lds, stream, p);
-    HIPCHK(hipGetLastError());
-    if (h->timing) HIPCHK(hipEventRecord(e1, stream));
+    TD_HIPCHK(hipGetLastError());
+    if (h->timing) TD_HIPCHK(hipEventRecord(e1, stream));
     return TD_OK;
 }
 
@@ -707,8 +672,8 @@ extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t 
 // every launch enqueued through this handle (they may be on its own streams) has finished
 extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h) {
     hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->work_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->work_stream.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream.s);
     return e == hipSuccess ? TD_OK : fail(TD_E_HIP, std::string("waiting for the handle's streams: ") + hipGetErrorString(e));
 }
 // for csrc/census.hip (hidden): its state's place on the handle, the work stream, the CU count; the barcode + cut-site
@@ -718,7 +683,7 @@ extern "C" __attribute__((visibility("hidden"))) void **td_handle_census(td_hand
 extern "C" __attribute__((visibility("hidden"))) void **td_handle_qc(td_handle *h) { return &h->qc; }
 extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_qc_flush_tiles(const td_handle *h) { return h->qc_flush_tiles; }
 extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_max_grid(const td_handle *h) { return h->max_grid; }
-extern "C" __attribute__((visibility("hidden"))) void *td_handle_work_stream(const td_handle *h) { return (void *)h->work_stream; }
+extern "C" __attribute__((visibility("hidden"))) void *td_handle_work_stream(const td_handle *h) { return (void *)h->work_stream.s; }
 extern "C" __attribute__((visibility("hidden"))) int td_handle_num_cu(const td_handle *h) { return h->num_cu; }
 extern "C" __attribute__((visibility("hidden"))) int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
                                                                     uint8_t **blob_out, uint32_t *bytes, uint32_t *off_bmeta, uint32_t *off_bdir) {
@@ -743,12 +708,12 @@ extern "C" __attribute__((visibility("hidden"))) int td_line_prefix(td_handle *h
                                                                     unsigned long long *d_total) {
     const uint64_t nt = (nbytes + 16383) / 16384;
     if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    int rc = h->d_tilecounts.ensure(nt); if (rc) return rc;
-    rc = h->d_state.ensure(nt); if (rc) return rc;
+    TD_HIPCHK(h->d_tilecounts.ensure(nt));
+    TD_HIPCHK(h->d_state.ensure(nt));
     const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
     hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, (hipStream_t)s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
     hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, (hipStream_t)s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, d_total);
-    HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     *prefix = h->d_state.p;
     return TD_OK;
 }
@@ -761,23 +726,23 @@ int td_create(td_handle **out, int device_id) {
     if (e != hipSuccess || n <= 0)
         return fail(TD_E_HIP, "no usable HIP device (libtagdig has no CPU fallback)");
     if (device_id < 0 || device_id >= n) return fail(TD_E_ARG, "device_id out of range");
-    HIPCHK(hipSetDevice(device_id));
-    td_handle *h = new td_handle();
+    TD_HIPCHK(hipSetDevice(device_id));
+    std::unique_ptr<td_handle> h(new td_handle());
     h->device = device_id;
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device_id));
+    TD_HIPCHK(hipGetDeviceProperties(&prop, device_id));
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    TD_HIPCHK(h->copy_stream.create());
     for (int k = 0; k < 2; k++) {
-        HIPCHK(hipStreamCreateWithFlags(&h->side_copy[k], hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&h->side_done[k], hipEventDisableTiming));
+        TD_HIPCHK(h->side_copy[k].create());
+        TD_HIPCHK(h->side_done[k].create(hipEventDisableTiming));
     }
-    HIPCHK(hipStreamCreateWithFlags(&h->work_stream, hipStreamNonBlocking));
-    int rc = h->d_stats.ensure(STATS_SLOTS); if (rc) { delete h; return rc; }
-    rc = h->d_ticket.ensure(4); if (rc) { delete h; return rc; }
-    rc = h->d_cursor.ensure(2); if (rc) { delete h; return rc; }
-    HIPCHK(hipMemset(h->d_stats.p, 0, STATS_SLOTS * 8));
-    *out = h;
+    TD_HIPCHK(h->work_stream.create());
+    TD_HIPCHK(h->d_stats.ensure(STATS_SLOTS));
+    TD_HIPCHK(h->d_ticket.ensure(4));
+    TD_HIPCHK(h->d_cursor.ensure(2));
+    TD_HIPCHK(hipMemset(h->d_stats.p, 0, STATS_SLOTS * 8));
+    *out = h.release();
     handle_born();
     return TD_OK;
 }
@@ -789,43 +754,13 @@ void td_destroy(td_handle *h) {
     (void)hipDeviceSynchronize();
     td_census_release(h);
     td_qc_release(h);
-    h->d_bblob.release(); h->d_slots.release(); h->d_shorts.release(); h->d_counts.release();
-    if (h->pin_cursor) (void)hipHostFree(h->pin_cursor);
-    h->d_win.release(); h->d_tilesums.release(); h->d_f4np.release(); h->d_sp_entries16.release(); h->d_sp_e8.release(); h->d_sp_pool2.release();
-    h->d_counts64.release(); h->d_stats.release(); h->d_state.release(); h->d_tilecounts.release();
-    h->d_ticket.release(); h->d_cursor.release(); h->d_seam_lines.release(); h->d_tileinfo.release(); h->d_nfix.release(); h->d_tail.release(); h->d_fixlist.release(); h->d_rowmap.release();
-    for (auto &ev : h->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    for (auto &sl : h->sp_slot) {
-        if (sl.pin) (void)hipHostFree(sl.pin);
-        if (sl.dev) (void)hipFree(sl.dev);
-        if (sl.res_dev) (void)hipFree(sl.res_dev);
-        if (sl.res_pin) (void)hipHostFree(sl.res_pin);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    release_bgzf_buffers(h);
-    for (auto &lp : h->ldpiece) { if (lp.pin) (void)hipHostFree(lp.pin); if (lp.sent) (void)hipEventDestroy(lp.sent); }
-    for (auto &g : h->gslot) {
-        g.d_sym.release(); g.d_out.release(); g.d_win.release(); g.d_blk.release(); g.d_crc.release();
-        if (g.pin_blk) (void)hipHostFree(g.pin_blk);
-        if (g.pin_crc) (void)hipHostFree(g.pin_crc);
-        if (g.pin_tail) (void)hipHostFree(g.pin_tail);
-        if (g.copied) (void)hipEventDestroy(g.copied);
-        if (g.done) (void)hipEventDestroy(g.done);
-    }
-    h->d_gzflag.release();
-    h->gzgpu.release();
-    if (h->d_crctab) (void)hipFree(h->d_crctab);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    for (auto &st : h->side_copy) if (st) (void)hipStreamDestroy(st);
-    for (auto &ev : h->side_done) if (ev) (void)hipEventDestroy(ev);
-    if (h->work_stream) (void)hipStreamDestroy(h->work_stream);
     delete h;
 }
 
 int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum,
                  const uint32_t *tagoff, const char *const *tags, uint32_t ntags) {
     if (!h) return fail(TD_E_ARG, "handle is NULL");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     h->have_index = false;
     std::vector<std::string> bs(n_barcut), ts(ntags);
     for (uint32_t i = 0; i < n_barcut; i++) bs[i] = barcut[i];
@@ -926,14 +861,14 @@ int td_set_index(td_handle *h, const char *const *barcut, uint32_t n_barcut, uin
     if (lds_bytes(h, h->tile_kb) > LDS_BUDGET) h->tile_kb = 16;
     if (h->tile_kb2 && lds_bytes_fast2(h, h->tile_kb2) > LDS_BUDGET) h->tile_kb2 = 0;     // (back to the automatic choice)
 
-    rc = h->d_bblob.ensure(h->bblob_bytes / 4); if (rc) return rc;
-    HIPCHK(hipMemcpy(h->d_bblob.p, blob.data(), h->bblob_bytes, hipMemcpyHostToDevice));
-    rc = h->d_slots.ensure(nslots * slot_u4); if (rc) return rc;
-    HIPCHK(hipMemcpy(h->d_slots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-    rc = h->d_shorts.ensure(std::max<size_t>(1, shorts.size() / 4)); if (rc) return rc;
-    if (!shorts.empty()) HIPCHK(hipMemcpy(h->d_shorts.p, shorts.data(), shorts.size() * 4, hipMemcpyHostToDevice));
-    h->d_counts64.release();
-    if (!h->bound_counts) { rc = h->d_counts.ensure((size_t)barnum * ntags); if (rc) return rc; }
+    TD_HIPCHK(h->d_bblob.ensure(h->bblob_bytes / 4));
+    TD_HIPCHK(hipMemcpy(h->d_bblob.p, blob.data(), h->bblob_bytes, hipMemcpyHostToDevice));
+    TD_HIPCHK(h->d_slots.ensure(nslots * slot_u4));
+    TD_HIPCHK(hipMemcpy(h->d_slots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+    TD_HIPCHK(h->d_shorts.ensure(std::max<size_t>(1, shorts.size() / 4)));
+    if (!shorts.empty()) TD_HIPCHK(hipMemcpy(h->d_shorts.p, shorts.data(), shorts.size() * 4, hipMemcpyHostToDevice));
+    h->d_counts64.reset();
+    if (!h->bound_counts) TD_HIPCHK(h->d_counts.ensure((size_t)barnum * ntags));
     h->host_acc.assign((size_t)barnum * ntags, 0);
     h->have_index = true;
     return zero_results(h);
@@ -949,43 +884,43 @@ int td_index_info(td_handle *h, uint64_t out[TD_INDEX_NINFO]) {
 int td_bind_counts(td_handle *h, void *d_counts) {
     if (!h) return fail(TD_E_ARG, "handle is NULL");
     h->bound_counts = (uint32_t *)d_counts;
-    if (!d_counts && h->have_index) { int rc = h->d_counts.ensure((size_t)h->barnum * h->ntags); if (rc) return rc; return zero_results(h); }
+    if (!d_counts && h->have_index) { TD_HIPCHK(h->d_counts.ensure((size_t)h->barnum * h->ntags)); return zero_results(h); }
     return TD_OK;
 }
 
 int td_reset(td_handle *h) {
     if (!h) return fail(TD_E_ARG, "handle is NULL");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipDeviceSynchronize());
     return zero_results(h);
 }
 
 int td_count_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads,
                     int weights, void *stream) {
     if (!h) return fail(TD_E_ARG, "handle is NULL");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     return launch_count(h, d_fastq, nbytes, first_line, max_reads, weights, (hipStream_t)stream);
 }
 
 int td_count_lines_device(td_handle *h, const void *d_fastq, uint64_t nbytes, void *stream, uint64_t *out) {
     if (!h || !out) return fail(TD_E_ARG, "NULL argument");
     if (((uintptr_t)d_fastq & 15) != 0) return fail(TD_E_ARG, "device FASTQ pointer must be 16-byte aligned");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     *out = 0;
     if (nbytes == 0) return TD_OK;
     const uint64_t tile = 16 * 1024;
     const uint64_t nt = (nbytes + tile - 1) / tile;
     if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    int rc = h->d_tilecounts.ensure(nt); if (rc) return rc;
-    rc = h->d_state.ensure(nt); if (rc) return rc;
+    TD_HIPCHK(h->d_tilecounts.ensure(nt));
+    TD_HIPCHK(h->d_state.ensure(nt));
     hipStream_t s = (hipStream_t)stream;
     uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
     hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
     hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, h->d_cursor.p);
-    HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     unsigned long long v = 0;
-    HIPCHK(hipMemcpyAsync(&v, h->d_cursor.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    TD_HIPCHK(hipMemcpyAsync(&v, h->d_cursor.p, 8, hipMemcpyDeviceToHost, s));
+    TD_HIPCHK(hipStreamSynchronize(s));
     *out = v;
     return TD_OK;
 }
@@ -1006,11 +941,11 @@ int upload(td_handle *h, void *dst, const void *src, size_t n) {
     for (int k = 1; k < lanes; k++) {
         const size_t off = std::min(n, (size_t)k * part), len = std::min(n, off + part) - off;
         if (!len) continue;
-        HIPCHK(hipMemcpyAsync((uint8_t *)dst + off, (const uint8_t *)src + off, len, hipMemcpyHostToDevice, h->side_copy[k - 1]));
-        HIPCHK(hipEventRecord(h->side_done[k - 1], h->side_copy[k - 1]));
+        TD_HIPCHK(hipMemcpyAsync((uint8_t *)dst + off, (const uint8_t *)src + off, len, hipMemcpyHostToDevice, h->side_copy[k - 1].s));
+        TD_HIPCHK(hipEventRecord(h->side_done[k - 1].e, h->side_copy[k - 1].s));
     }
-    HIPCHK(hipMemcpyAsync(dst, src, std::min(n, part), hipMemcpyHostToDevice, h->copy_stream));
-    for (int k = 1; k < lanes; k++) HIPCHK(hipStreamWaitEvent(h->copy_stream, h->side_done[k - 1], 0));
+    TD_HIPCHK(hipMemcpyAsync(dst, src, std::min(n, part), hipMemcpyHostToDevice, h->copy_stream.s));
+    for (int k = 1; k < lanes; k++) TD_HIPCHK(hipStreamWaitEvent(h->copy_stream.s, h->side_done[k - 1].e, 0));
     return TD_OK;
 }
 
@@ -1018,58 +953,49 @@ struct Stager {
     td_handle *h = nullptr;
     static constexpr int NB = 3;
     size_t cap = 0;
-    uint8_t *pin[NB] = {nullptr, nullptr, nullptr};
-    uint8_t *dev[NB] = {nullptr, nullptr, nullptr};
-    hipEvent_t copied[NB] = {nullptr, nullptr, nullptr};  // H2D of buffer i landed
-    hipEvent_t done[NB] = {nullptr, nullptr, nullptr};    // kernel on buffer i finished
+    PinBuf<uint8_t> pin[NB];
+    DevBuf<uint8_t> dev[NB];
+    Event copied[NB];                         // H2D of buffer i landed
+    Event done[NB];                           // kernel on buffer i finished
     bool busy[NB] = {false, false, false};
     int cur = 0;
     uint64_t first_line = 0;
     uint64_t bytes_submitted = 0;             // every line holds >= 1 byte: bounds the line index from above
     unsigned pieces = 0;
-    unsigned long long *lines_after = nullptr;   // pinned: line terminators counted up to and including buffer i's piece
+    PinBuf<unsigned long long> lines_after;      // pinned: line terminators counted up to and including buffer i's piece
     uint64_t lines_seen = 0;                     // ... of the newest piece known to have drained (a lower bound of the cursor)
     int init(td_handle *hh, size_t capacity, uint64_t first) {
         h = hh; cap = capacity; first_line = first;
-        HIPCHK(hipHostMalloc((void **)&lines_after, NB * sizeof(unsigned long long), hipHostMallocDefault));
+        TD_HIPCHK(lines_after.alloc(NB));
         for (int i = 0; i < NB; i++) {
-            HIPCHK(hipHostMalloc((void **)&pin[i], cap, hipHostMallocDefault));
-            HIPCHK(hipMalloc((void **)&dev[i], cap));
-            HIPCHK(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
+            TD_HIPCHK(pin[i].alloc(cap));
+            TD_HIPCHK(dev[i].alloc(cap));
+            TD_HIPCHK(copied[i].create(hipEventDisableTiming));
+            TD_HIPCHK(done[i].create(hipEventDisableTiming));
         }
-        HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream));
+        TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream.s));
         return TD_OK;
-    }
-    ~Stager() {
-        if (lines_after) (void)hipHostFree(lines_after);
-        for (int i = 0; i < NB; i++) {
-            if (pin[i]) (void)hipHostFree(pin[i]);
-            if (dev[i]) (void)hipFree(dev[i]);
-            if (copied[i]) (void)hipEventDestroy(copied[i]);
-            if (done[i]) (void)hipEventDestroy(done[i]);
-        }
     }
     // buffer to fill next (waits until its previous use has drained)
     int acquire(uint8_t **p) {
-        if (busy[cur]) { HIPCHK(hipEventSynchronize(done[cur])); busy[cur] = false; lines_seen = lines_after[cur]; }
-        *p = pin[cur];
+        if (busy[cur]) { TD_HIPCHK(hipEventSynchronize(done[cur].e)); busy[cur] = false; lines_seen = lines_after.p[cur]; }
+        *p = pin[cur].p;
         return TD_OK;
     }
     // copy on the copy stream, count on the work stream; the line index travels
     // from piece to piece through d_cursor[pieces & 1] on the device
     int submit(size_t n, uint64_t max_reads, int weights) {
         if (n == 0) return TD_OK;
-        { const int rc = upload(h, dev[cur], pin[cur], n); if (rc) return rc; }
-        HIPCHK(hipEventRecord(copied[cur], h->copy_stream));
-        HIPCHK(hipStreamWaitEvent(h->work_stream, copied[cur], 0));
-        int rc = launch_count(h, dev[cur], n, first_line, max_reads, weights, h->work_stream,
+        { const int rc = upload(h, dev[cur].p, pin[cur].p, n); if (rc) return rc; }
+        TD_HIPCHK(hipEventRecord(copied[cur].e, h->copy_stream.s));
+        TD_HIPCHK(hipStreamWaitEvent(h->work_stream.s, copied[cur].e, 0));
+        int rc = launch_count(h, dev[cur].p, n, first_line, max_reads, weights, h->work_stream.s,
                               h->d_cursor.p + (pieces & 1), h->d_cursor.p + ((pieces + 1) & 1),
                               first_line + bytes_submitted);
         if (rc) return rc;
         bytes_submitted += n;
-        HIPCHK(hipMemcpyAsync(lines_after + cur, h->d_cursor.p + ((pieces + 1) & 1), 8, hipMemcpyDeviceToHost, h->work_stream));
-        HIPCHK(hipEventRecord(done[cur], h->work_stream));
+        TD_HIPCHK(hipMemcpyAsync(lines_after.p + cur, h->d_cursor.p + ((pieces + 1) & 1), 8, hipMemcpyDeviceToHost, h->work_stream.s));
+        TD_HIPCHK(hipEventRecord(done[cur].e, h->work_stream.s));
         busy[cur] = true;
         pieces++;
         cur = (cur + 1) % NB;
@@ -1077,9 +1003,9 @@ struct Stager {
     }
     int finish(uint64_t *lines) {
         unsigned long long v = 0;
-        HIPCHK(hipMemcpyAsync(&v, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream));
-        HIPCHK(hipStreamSynchronize(h->work_stream));
-        HIPCHK(hipStreamSynchronize(h->copy_stream));
+        TD_HIPCHK(hipMemcpyAsync(&v, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream.s));
+        TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
+        TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
         if (lines) *lines = v;
         return TD_OK;
     }
@@ -1123,16 +1049,16 @@ int cut_before_header_device(td_handle *h, const uint8_t *d_buf, size_t total, c
     if (*c == 0) return TD_OK;
     const uint64_t nbytes = total - ntail + *c, nt = (nbytes + 16383) / 16384;
     if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    int rc = h->d_tilecounts.ensure(nt); if (rc) return rc;
-    rc = h->d_state.ensure(nt); if (rc) return rc;
-    rc = h->d_seam_lines.ensure(1); if (rc) return rc;
+    TD_HIPCHK(h->d_tilecounts.ensure(nt));
+    TD_HIPCHK(h->d_state.ensure(nt));
+    TD_HIPCHK(h->d_seam_lines.ensure(1));
     const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
     hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, st, d_buf, nbytes, (uint32_t)nt, h->d_tilecounts.p);
     hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, st, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, h->d_seam_lines.p);
-    HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     unsigned long long lines = 0;
-    HIPCHK(hipMemcpyAsync(&lines, h->d_seam_lines.p, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    TD_HIPCHK(hipMemcpyAsync(&lines, h->d_seam_lines.p, 8, hipMemcpyDeviceToHost, st));
+    TD_HIPCHK(hipStreamSynchronize(st));
     const size_t c2 = cut_before_header(tail, *c, *line_at + lines);
     if (c2 != *c) {
         if (c2 == 0 && ntail < total) return fail(TD_E_LIMIT, "a header line exceeds the staging buffer");
@@ -1232,41 +1158,34 @@ constexpr size_t ZB_TAIL = (size_t)1 << 20;                  // bytes of a batch
 // file comes), the CRC tables, the kernel's LDS attribute.  *ok = false: no room on the device.
 int ensure_bgzf_buffers(td_handle *h, uint32_t need_members, size_t need_in, bool *ok_out) {
     *ok_out = true;
-    if (need_members > h->zcap_members || need_in > h->zcap_in) {
-        need_members = std::max(need_members, h->zcap_members);
-        need_in = std::max(need_in, h->zcap_in);
-        release_bgzf_buffers(h);
+    if (need_members > h->bgzf->cap_members || need_in > h->bgzf->cap_in) {
+        need_members = std::max(need_members, h->bgzf->cap_members);
+        need_in = std::max(need_in, h->bgzf->cap_in);
+        h->bgzf.reset(new td_handle::Bgzf());                    // (the old buffers go first)
+        td_handle::Bgzf &z = *h->bgzf;
         const size_t out_cap = (size_t)need_members * 65536 + ZB_CARRY + 4096;
-        bool ok = true;
-        auto dev = [&](void **p, size_t n) { if (ok && hipMalloc(p, n) != hipSuccess) { ok = false; (void)hipGetLastError(); } };
-        auto pin = [&](void **p, size_t n) { if (ok && hipHostMalloc(p, n, hipHostMallocDefault) != hipSuccess) { ok = false; (void)hipGetLastError(); } };
-        for (auto &zp : h->zpiece) {
-            pin((void **)&zp.pin, std::min(ZB_PIECE, need_in + 64) + 64);
-            if (ok && hipEventCreateWithFlags(&zp.sent, hipEventDisableTiming) != hipSuccess) ok = false;
-        }
-        for (auto &z : h->zslot) {
-            dev((void **)&z.d_in, need_in + 1024);
-            dev((void **)&z.d_out, out_cap);
-            pin((void **)&z.pin_mem, (size_t)need_members * sizeof(tdinf::Member));
-            dev((void **)&z.d_mem, (size_t)need_members * sizeof(tdinf::Member));
-            dev((void **)&z.d_status, (size_t)need_members * 4);
-            pin((void **)&z.pin_status, (size_t)need_members * 4);
-            pin((void **)&z.pin_tail, ZB_TAIL);
-            if (ok && hipEventCreateWithFlags(&z.copied, hipEventDisableTiming) != hipSuccess) ok = false;
-        }
-        dev((void **)&h->d_zscratch, (size_t)need_members * tdinf::SCRATCH_BYTES);
-        if (!ok) { release_bgzf_buffers(h); *ok_out = false; return TD_OK; }
-        h->zcap_members = need_members; h->zcap_in = need_in;
+        const auto ok = [](hipError_t e) { return e == hipSuccess; };
+        const bool room = [&]() {                                // (in this order; nothing more is asked for after the first refusal)
+            for (auto &zp : z.piece)
+                if (!ok(zp.pin.alloc(std::min(ZB_PIECE, need_in + 64) + 64)) || !ok(zp.sent.create(hipEventDisableTiming))) return false;
+            for (auto &sl : z.slot)
+                if (!ok(sl.d_in.alloc(need_in + 1024)) || !ok(sl.d_out.alloc(out_cap)) || !ok(sl.pin_mem.alloc(need_members)) ||
+                    !ok(sl.d_mem.alloc(need_members)) || !ok(sl.d_status.alloc(need_members)) || !ok(sl.pin_status.alloc(need_members)) ||
+                    !ok(sl.pin_tail.alloc(ZB_TAIL)) || !ok(sl.copied.create(hipEventDisableTiming))) return false;
+            return ok(z.d_scratch.alloc((size_t)need_members * tdinf::SCRATCH_BYTES));
+        }();
+        if (!room) { (void)hipGetLastError(); h->bgzf.reset(new td_handle::Bgzf()); *ok_out = false; return TD_OK; }
+        z.cap_members = need_members; z.cap_in = need_in;
     }
-    if (!h->d_crctab) {
+    if (!h->d_crctab.p) {
         uint32_t T[1024];                                        // slicing-by-4: T[256 k + b] = CRC of byte b followed by k zero bytes
         for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1; T[i] = c; }
         for (uint32_t k = 1; k < 4; k++)
             for (uint32_t i = 0; i < 256; i++) T[256 * k + i] = T[T[256 * (k - 1) + i] & 0xFFu] ^ (T[256 * (k - 1) + i] >> 8);
-        HIPCHK(hipMalloc((void **)&h->d_crctab, sizeof(T)));
-        HIPCHK(hipMemcpy(h->d_crctab, T, sizeof(T), hipMemcpyHostToDevice));
+        TD_HIPCHK(h->d_crctab.alloc(1024));
+        TD_HIPCHK(hipMemcpy(h->d_crctab.p, T, sizeof(T), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipFuncSetAttribute((const void *)tdinf::k_bgzf_inflate, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * tdinf::TABLE_U16 * 2 + 4096));
+    TD_HIPCHK(hipFuncSetAttribute((const void *)tdinf::k_bgzf_inflate, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * tdinf::TABLE_U16 * 2 + 4096));
     return TD_OK;
 }
 
@@ -1301,14 +1220,14 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         if (rc_b) return rc_b;
         if (!ok) { *not_bgzf = true; return TD_OK; }          // no room on the device: the host inflater takes the file
     }
-    const uint32_t batch_members = std::min<uint32_t>(h->zcap_members, h->zb_members);
-    const size_t batch_in = h->zcap_in, piece_cap = std::min(ZB_PIECE, h->zcap_in + 64);
-    HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream));
+    const uint32_t batch_members = std::min<uint32_t>(h->bgzf->cap_members, h->zb_members);
+    const size_t batch_in = h->bgzf->cap_in, piece_cap = std::min(ZB_PIECE, h->bgzf->cap_in + 64);
+    TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream.s));
     struct Batch { uint32_t n = 0; size_t out_total = 0; bool last = false; };
     size_t pos = 0;
     // members of the next batch: descriptors and compressed bytes into the slot's pinned buffers, then on their way to the device
     auto prepare = [&](int slot, Batch &b) -> int {
-        td_handle::ZSlot &z = h->zslot[slot];
+        td_handle::ZSlot &z = h->bgzf->slot[slot];
         b = Batch();
         const size_t first = pos;
         while (pos < src.bsize && b.n < batch_members) {
@@ -1322,7 +1241,7 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
             const uint32_t crc = tail[0] | (tail[1] << 8) | (tail[2] << 16) | ((uint32_t)tail[3] << 24);
             const uint32_t isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
             if (isize > 65536) return fail(TD_E_IO, "BGZF member larger than 64 KiB");
-            z.pin_mem[b.n] = tdinf::Member{pos + hs - first, b.out_total, bs - hs - 8, isize, crc, 0};
+            z.pin_mem.p[b.n] = tdinf::Member{pos + hs - first, b.out_total, bs - hs - 8, isize, crc, 0};
             b.out_total += isize; b.n++;
             pos += bs;
         }
@@ -1331,25 +1250,25 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         // the compressed bytes, through the two pinned pieces in turn (+ 64 zero bytes: the decoder reads a little ahead)
         int k = 0;
         for (size_t off = 0; off < nin + 64; off += piece_cap, k ^= 1) {
-            td_handle::ZPiece &zp = h->zpiece[k];
-            if (zp.busy) { HIPCHK(hipEventSynchronize(zp.sent)); zp.busy = false; }
+            td_handle::ZPiece &zp = h->bgzf->piece[k];
+            if (zp.busy) { TD_HIPCHK(hipEventSynchronize(zp.sent.e)); zp.busy = false; }
             const size_t want = std::min(piece_cap, nin + 64 - off), have = off < nin ? std::min(want, nin - off) : 0;
-            if (have) stage_parallel(have, [&](size_t o2, size_t len) { memcpy(zp.pin + o2, src.map + first + off + o2, len); return true; });
-            if (want > have) memset(zp.pin + have, 0, want - have);
-            { const int urc = upload(h, z.d_in + off, zp.pin, want); if (urc) return urc; }
-            HIPCHK(hipEventRecord(zp.sent, h->copy_stream));
+            if (have) stage_parallel(have, [&](size_t o2, size_t len) { memcpy(zp.pin.p + o2, src.map + first + off + o2, len); return true; });
+            if (want > have) memset(zp.pin.p + have, 0, want - have);
+            { const int urc = upload(h, z.d_in.p + off, zp.pin.p, want); if (urc) return urc; }
+            TD_HIPCHK(hipEventRecord(zp.sent.e, h->copy_stream.s));
             zp.busy = true;
         }
-        if (b.n) HIPCHK(hipMemcpyAsync(z.d_mem, z.pin_mem, (size_t)b.n * sizeof(tdinf::Member), hipMemcpyHostToDevice, h->copy_stream));
-        HIPCHK(hipEventRecord(z.copied, h->copy_stream));
+        if (b.n) TD_HIPCHK(hipMemcpyAsync(z.d_mem.p, z.pin_mem.p, (size_t)b.n * sizeof(tdinf::Member), hipMemcpyHostToDevice, h->copy_stream.s));
+        TD_HIPCHK(hipEventRecord(z.copied.e, h->copy_stream.s));
         return TD_OK;
     };
     Batch cur, nxt;
     int slot = 0;
     // (reference :272: the loop ends at maxreads -- no further batch is inflated once a counted batch's line index shows
     // that the bound has been passed; the kernels ignore reads past it either way)
-    if (!h->pin_cursor) HIPCHK(hipHostMalloc((void **)&h->pin_cursor, 16, hipHostMallocDefault));
-    h->pin_cursor[0] = 0;
+    if (!h->pin_cursor.p) TD_HIPCHK(h->pin_cursor.alloc(2));
+    h->pin_cursor.p[0] = 0;
     const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
     int rc = prepare(0, cur); if (rc) return rc;
     size_t carry = 0;                                       // bytes of an unfinished line at the front of this slot's output
@@ -1357,27 +1276,27 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
     uint64_t bytes_submitted = 0;
     unsigned pieces = 0;
     for (;;) {
-        td_handle::ZSlot &z = h->zslot[slot];
-        HIPCHK(hipStreamWaitEvent(h->work_stream, z.copied, 0));
+        td_handle::ZSlot &z = h->bgzf->slot[slot];
+        TD_HIPCHK(hipStreamWaitEvent(h->work_stream.s, z.copied.e, 0));
         if (cur.n) {
-            hipLaunchKernelGGL(tdinf::k_bgzf_inflate, dim3((cur.n + 63) / 64), dim3(64), 64 * tdinf::TABLE_U16 * 2 + 4096, h->work_stream,
-                               z.d_in, z.d_out + carry, z.d_mem, cur.n, h->d_zscratch, z.d_status, h->d_crctab, (uint32_t)h->gpu_inflate_crc);
-            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(tdinf::k_bgzf_inflate, dim3((cur.n + 63) / 64), dim3(64), 64 * tdinf::TABLE_U16 * 2 + 4096, h->work_stream.s,
+                               z.d_in.p, z.d_out.p + carry, z.d_mem.p, cur.n, h->bgzf->d_scratch.p, z.d_status.p, h->d_crctab.p, (uint32_t)h->gpu_inflate_crc);
+            TD_HIPCHK(hipGetLastError());
         }
         const size_t total = carry + cur.out_total;
         const size_t ntail = std::min(total, ZB_TAIL);
-        if (cur.n) HIPCHK(hipMemcpyAsync(z.pin_status, z.d_status, (size_t)cur.n * 4, hipMemcpyDeviceToHost, h->work_stream));
-        if (ntail && !cur.last) HIPCHK(hipMemcpyAsync(z.pin_tail, z.d_out + total - ntail, ntail, hipMemcpyDeviceToHost, h->work_stream));
+        if (cur.n) TD_HIPCHK(hipMemcpyAsync(z.pin_status.p, z.d_status.p, (size_t)cur.n * 4, hipMemcpyDeviceToHost, h->work_stream.s));
+        if (ntail && !cur.last) TD_HIPCHK(hipMemcpyAsync(z.pin_tail.p, z.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, h->work_stream.s));
         // the next batch is read and sent while this one inflates
         if (!cur.last) { rc = prepare(slot ^ 1, nxt); if (rc) return rc; }
-        HIPCHK(hipStreamSynchronize(h->work_stream));
-        if (h->pin_cursor[0] >= stop_line) break;               // (the batches counted so far already hold read number max_reads)
+        TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
+        if (h->pin_cursor.p[0] >= stop_line) break;               // (the batches counted so far already hold read number max_reads)
         for (uint32_t i = 0; i < cur.n; i++)
-            if (z.pin_status[i]) return fail(TD_E_IO, z.pin_status[i] == 100 ? "BGZF member fails its CRC-32" : "inflate error in a BGZF member");
+            if (z.pin_status.p[i]) return fail(TD_E_IO, z.pin_status.p[i] == 100 ? "BGZF member fails its CRC-32" : "inflate error in a BGZF member");
         size_t cut = total;
         if (!cur.last && total) {
-            size_t c = cut_at_line_end(z.pin_tail, ntail);
-            if (weights) { rc = cut_before_header_device(h, z.d_out, total, z.pin_tail, ntail, h->work_stream, &line_at, &c); if (rc) return rc; }
+            size_t c = cut_at_line_end(z.pin_tail.p, ntail);
+            if (weights) { rc = cut_before_header_device(h, z.d_out.p, total, z.pin_tail.p, ntail, h->work_stream.s, &line_at, &c); if (rc) return rc; }
             if (c == 0) {                                       // (no line end in sight: everything waits for the next batch)
                 if (total > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
                 cut = 0;
@@ -1387,19 +1306,19 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
             }
         }
         if (cut) {
-            rc = launch_count(h, z.d_out, cut, 0, max_reads, weights, h->work_stream, h->d_cursor.p + (pieces & 1),
+            rc = launch_count(h, z.d_out.p, cut, 0, max_reads, weights, h->work_stream.s, h->d_cursor.p + (pieces & 1),
                               h->d_cursor.p + ((pieces + 1) & 1), bytes_submitted);
             if (rc) return rc;
             bytes_submitted += cut; pieces++;
-            HIPCHK(hipMemcpyAsync(h->pin_cursor, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream));
+            TD_HIPCHK(hipMemcpyAsync(h->pin_cursor.p, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream.s));
         }
         if (cur.last) break;
         carry = total - cut;
-        if (carry) HIPCHK(hipMemcpyAsync(h->zslot[slot ^ 1].d_out, z.d_out + cut, carry, hipMemcpyDeviceToDevice, h->work_stream));
+        if (carry) TD_HIPCHK(hipMemcpyAsync(h->bgzf->slot[slot ^ 1].d_out.p, z.d_out.p + cut, carry, hipMemcpyDeviceToDevice, h->work_stream.s));
         cur = nxt; slot ^= 1;
     }
-    HIPCHK(hipStreamSynchronize(h->work_stream));
-    HIPCHK(hipStreamSynchronize(h->copy_stream));
+    TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
+    TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
     return TD_OK;
 }
 }  // namespace
@@ -1465,16 +1384,17 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
     *not_applicable = false;
     tdhost::GzSource src;
     if (!src.open_dev(path, &g_pinned_alloc)) { *not_applicable = true; return TD_OK; }
-    int rc = h->d_gzflag.ensure(4); if (rc) return rc;
-    HIPCHK(hipMemsetAsync(h->d_gzflag.p, 0, 16, h->work_stream));
-    if (!h->d_crctab) { bool ok = true; rc = ensure_bgzf_buffers(h, 0, 0, &ok); if (rc) return rc; }      // (the CRC tables)
-    HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream));
-    if (!h->pin_cursor) HIPCHK(hipHostMalloc((void **)&h->pin_cursor, 16, hipHostMallocDefault));
-    h->pin_cursor[0] = 0;
+    TD_HIPCHK(h->d_gzflag.ensure(4));
+    TD_HIPCHK(hipMemsetAsync(h->d_gzflag.p, 0, 16, h->work_stream.s));
+    int rc = TD_OK;
+    if (!h->d_crctab.p) { bool ok = true; rc = ensure_bgzf_buffers(h, 0, 0, &ok); if (rc) return rc; }      // (the CRC tables)
+    TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream.s));
+    if (!h->pin_cursor.p) TD_HIPCHK(h->pin_cursor.alloc(2));
+    h->pin_cursor.p[0] = 0;
     // (events the host waits on sleeping: a spinning wait would take a core from the decoder's threads)
     for (auto &g : h->gslot) {
-        if (!g.copied) HIPCHK(hipEventCreateWithFlags(&g.copied, hipEventDisableTiming | hipEventBlockingSync));
-        if (!g.done) HIPCHK(hipEventCreateWithFlags(&g.done, hipEventDisableTiming | hipEventBlockingSync));
+        if (!g.copied.e) TD_HIPCHK(g.copied.create(hipEventDisableTiming | hipEventBlockingSync));
+        if (!g.done.e) TD_HIPCHK(g.done.create(hipEventDisableTiming | hipEventBlockingSync));
     }
     const int copy_streams = copy_lanes();
     struct Batch {
@@ -1505,19 +1425,17 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
         for (const PI::DevPiece &pc : db->pieces) { nblk += (pc.len + tdgz::BLOCK_SYMS - 1) / tdgz::BLOCK_SYMS; sym_bytes += (pc.len * (pc.narrow ? 1 : 2) + 15) & ~(size_t)15; }
         std::vector<const uint8_t *> wins;
         if (nblk > g.pin_cap) {
-            if (g.pin_blk) (void)hipHostFree(g.pin_blk);
-            if (g.pin_crc) (void)hipHostFree(g.pin_crc);
-            g.pin_blk = nullptr; g.pin_crc = nullptr;
+            g.pin_blk.reset(); g.pin_crc.reset(); g.pin_cap = 0;
             const size_t cap = nblk * 2 + 1024;
-            HIPCHK(hipHostMalloc((void **)&g.pin_blk, cap * sizeof(tdgz::Block), hipHostMallocDefault));
-            HIPCHK(hipHostMalloc((void **)&g.pin_crc, cap * 4, hipHostMallocDefault));
+            TD_HIPCHK(g.pin_blk.alloc(cap));
+            TD_HIPCHK(g.pin_crc.alloc(cap));
             g.pin_cap = cap;
         }
-        if (!g.pin_tail) HIPCHK(hipHostMalloc((void **)&g.pin_tail, ZB_TAIL + 16, hipHostMallocDefault));     // (+ the marker flag)
-        int rc2 = g.d_sym.ensure(sym_bytes + 64); if (rc2) return rc2;
-        rc2 = g.d_out.ensure(ZB_CARRY + db->total + 4096 + (db->total >> 3)); if (rc2) return rc2;
-        rc2 = g.d_blk.ensure(nblk + 1); if (rc2) return rc2;
-        rc2 = g.d_crc.ensure(nblk + 1); if (rc2) return rc2;
+        if (!g.pin_tail.p) TD_HIPCHK(g.pin_tail.alloc(ZB_TAIL + 16));     // (+ the marker flag)
+        TD_HIPCHK(g.d_sym.ensure(sym_bytes + 64));
+        TD_HIPCHK(g.d_out.ensure(ZB_CARRY + db->total + 4096 + (db->total >> 3)));
+        TD_HIPCHK(g.d_blk.ensure(nblk + 1));
+        TD_HIPCHK(g.d_crc.ensure(nblk + 1));
         size_t at = 0, kb = 0;
         unsigned npiece = 0;
         for (const PI::DevPiece &pc : db->pieces) {
@@ -1526,28 +1444,28 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
             if (wi == wins.size()) wins.push_back(pc.window);
             const size_t esz = pc.narrow ? 1 : 2;
             const int lane = (int)(npiece++ % (unsigned)copy_streams);           // (the chunks of a batch over the copy engines)
-            HIPCHK(hipMemcpyAsync(g.d_sym.p + at, pc.src, pc.len * esz, hipMemcpyHostToDevice, lane ? h->side_copy[lane - 1] : h->copy_stream));
+            TD_HIPCHK(hipMemcpyAsync(g.d_sym.p + at, pc.src, pc.len * esz, hipMemcpyHostToDevice, lane ? h->side_copy[lane - 1].s : h->copy_stream.s));
             for (size_t o = 0; o < pc.len; o += tdgz::BLOCK_SYMS, kb++)
-                g.pin_blk[kb] = tdgz::Block{at + o * esz, pc.dest_off + o, (uint32_t)std::min<size_t>(tdgz::BLOCK_SYMS, pc.len - o), wi,
+                g.pin_blk.p[kb] = tdgz::Block{at + o * esz, pc.dest_off + o, (uint32_t)std::min<size_t>(tdgz::BLOCK_SYMS, pc.len - o), wi,
                                             pc.min_idx, pc.narrow ? 1u : 0u};
             at += (pc.len * esz + 15) & ~(size_t)15;
         }
-        rc2 = g.d_win.ensure(std::max<size_t>(1, wins.size()) * tdgz::WINDOW); if (rc2) return rc2;
+        TD_HIPCHK(g.d_win.ensure(std::max<size_t>(1, wins.size()) * tdgz::WINDOW));
         for (size_t w = 0; w < wins.size(); w++)
-            HIPCHK(hipMemcpyAsync(g.d_win.p + w * tdgz::WINDOW, wins[w], tdgz::WINDOW, hipMemcpyHostToDevice, h->copy_stream));
-        HIPCHK(hipMemcpyAsync(g.d_blk.p, g.pin_blk, nblk * sizeof(tdgz::Block), hipMemcpyHostToDevice, h->copy_stream));
+            TD_HIPCHK(hipMemcpyAsync(g.d_win.p + w * tdgz::WINDOW, wins[w], tdgz::WINDOW, hipMemcpyHostToDevice, h->copy_stream.s));
+        TD_HIPCHK(hipMemcpyAsync(g.d_blk.p, g.pin_blk.p, nblk * sizeof(tdgz::Block), hipMemcpyHostToDevice, h->copy_stream.s));
         for (int k = 0; k + 1 < copy_streams; k++) {
-            HIPCHK(hipEventRecord(h->side_done[k], h->side_copy[k]));
-            HIPCHK(hipStreamWaitEvent(h->copy_stream, h->side_done[k], 0));
+            TD_HIPCHK(hipEventRecord(h->side_done[k].e, h->side_copy[k].s));
+            TD_HIPCHK(hipStreamWaitEvent(h->copy_stream.s, h->side_done[k].e, 0));
         }
-        HIPCHK(hipEventRecord(g.copied, h->copy_stream));
+        TD_HIPCHK(hipEventRecord(g.copied.e, h->copy_stream.s));
         b.valid = true; b.last = db->last; b.member_done = db->member_done; b.want_crc = db->want_crc;
         b.nblk = (uint32_t)nblk; b.total = db->total;
         b.crc_len.resize(nblk);
-        for (size_t k = 0; k < nblk; k++) b.crc_len[k].second = g.pin_blk[k].len;
+        for (size_t k = 0; k < nblk; k++) b.crc_len[k].second = g.pin_blk.p[k].len;
         // the decoder may have its buffers back once the copies have left them
         const double tu = PI::now();
-        HIPCHK(hipEventSynchronize(g.copied));
+        TD_HIPCHK(hipEventSynchronize(g.copied.e));
         t_upload += PI::now() - tu; up_bytes += at;
         src.pi.dev_release();
         return TD_OK;
@@ -1560,33 +1478,33 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
     unsigned pieces = 0;
     while (cur.valid) {
         td_handle::GSlot &g = h->gslot[slot];
-        HIPCHK(hipStreamWaitEvent(h->work_stream, g.copied, 0));
+        TD_HIPCHK(hipStreamWaitEvent(h->work_stream.s, g.copied.e, 0));
         if (cur.nblk) {
             // (the batch's bytes go behind what the batch before left of its last line: d_out + carry)
-            hipLaunchKernelGGL(tdgz::k_gz_resolve, dim3(cur.nblk), dim3(256), 0, h->work_stream, g.d_sym.p, g.d_win.p, g.d_out.p + carry, g.d_blk.p, cur.nblk, h->d_gzflag.p);
-            hipLaunchKernelGGL(tdgz::k_gz_crc, dim3((cur.nblk + 63) / 64), dim3(64), 0, h->work_stream, g.d_out.p + carry, g.d_blk.p, cur.nblk, h->d_crctab, g.d_crc.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(g.pin_crc, g.d_crc.p, (size_t)cur.nblk * 4, hipMemcpyDeviceToHost, h->work_stream));
+            hipLaunchKernelGGL(tdgz::k_gz_resolve, dim3(cur.nblk), dim3(256), 0, h->work_stream.s, g.d_sym.p, g.d_win.p, g.d_out.p + carry, g.d_blk.p, cur.nblk, h->d_gzflag.p);
+            hipLaunchKernelGGL(tdgz::k_gz_crc, dim3((cur.nblk + 63) / 64), dim3(64), 0, h->work_stream.s, g.d_out.p + carry, g.d_blk.p, cur.nblk, h->d_crctab.p, g.d_crc.p);
+            TD_HIPCHK(hipGetLastError());
+            TD_HIPCHK(hipMemcpyAsync(g.pin_crc.p, g.d_crc.p, (size_t)cur.nblk * 4, hipMemcpyDeviceToHost, h->work_stream.s));
         }
         const size_t total = carry + cur.total;
         const size_t ntail = std::min(total, ZB_TAIL);
-        if (ntail && !cur.last) HIPCHK(hipMemcpyAsync(g.pin_tail, g.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, h->work_stream));
-        uint32_t *flag = (uint32_t *)(g.pin_tail + ZB_TAIL);
-        HIPCHK(hipMemcpyAsync(flag, h->d_gzflag.p, 4, hipMemcpyDeviceToHost, h->work_stream));
-        HIPCHK(hipEventRecord(g.done, h->work_stream));
+        if (ntail && !cur.last) TD_HIPCHK(hipMemcpyAsync(g.pin_tail.p, g.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, h->work_stream.s));
+        uint32_t *flag = (uint32_t *)(g.pin_tail.p + ZB_TAIL);
+        TD_HIPCHK(hipMemcpyAsync(flag, h->d_gzflag.p, 4, hipMemcpyDeviceToHost, h->work_stream.s));
+        TD_HIPCHK(hipEventRecord(g.done.e, h->work_stream.s));
         // the next batch is taken from the decoder and sent while this one is resolved
         if (!cur.last) { rc = prepare(slot ^ 1, nxt); if (rc) return rc; }
         const double ts = PI::now();
-        HIPCHK(hipEventSynchronize(g.done));
+        TD_HIPCHK(hipEventSynchronize(g.done.e));
         t_sync += PI::now() - ts; nbatch++;
         if (*flag) return fail(TD_E_IO, "gzip: distance reaches before the start of the output");
-        for (uint32_t k = 0; k < cur.nblk; k++) cur.crc_len[k].first = g.pin_crc[k];
+        for (uint32_t k = 0; k < cur.nblk; k++) cur.crc_len[k].first = g.pin_crc.p[k];
         if (!src.pi.dev_check(cur.crc_len, cur.member_done, cur.want_crc)) return fail(TD_E_IO, std::string("gzip: ") + src.pi.error());
-        if (h->pin_cursor[0] >= stop_line) break;               // (the batches counted so far already hold read number max_reads)
+        if (h->pin_cursor.p[0] >= stop_line) break;               // (the batches counted so far already hold read number max_reads)
         size_t cut = total;
         if (!cur.last && total) {
-            size_t c = cut_at_line_end(g.pin_tail, ntail);
-            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, g.pin_tail, ntail, h->work_stream, &line_at, &c); if (rc) return rc; }
+            size_t c = cut_at_line_end(g.pin_tail.p, ntail);
+            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, g.pin_tail.p, ntail, h->work_stream.s, &line_at, &c); if (rc) return rc; }
             if (c == 0) {
                 // no line end in sight -- a member that stops inside a line, followed by an empty one or one of a few bytes
                 // (a batch closes at every member end): everything waits for the next batch
@@ -1598,20 +1516,20 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
             }
         }
         if (cut) {
-            rc = launch_count(h, g.d_out.p, cut, 0, max_reads, weights, h->work_stream, h->d_cursor.p + (pieces & 1),
+            rc = launch_count(h, g.d_out.p, cut, 0, max_reads, weights, h->work_stream.s, h->d_cursor.p + (pieces & 1),
                               h->d_cursor.p + ((pieces + 1) & 1), bytes_submitted);
             if (rc) return rc;
             bytes_submitted += cut; pieces++;
-            HIPCHK(hipMemcpyAsync(h->pin_cursor, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream));
+            TD_HIPCHK(hipMemcpyAsync(h->pin_cursor.p, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream.s));
         }
         if (cur.last) break;
         const size_t carry_next = total - cut;
-        if (carry_next) HIPCHK(hipMemcpyAsync(h->gslot[slot ^ 1].d_out.p, g.d_out.p + cut, carry_next, hipMemcpyDeviceToDevice, h->work_stream));
+        if (carry_next) TD_HIPCHK(hipMemcpyAsync(h->gslot[slot ^ 1].d_out.p, g.d_out.p + cut, carry_next, hipMemcpyDeviceToDevice, h->work_stream.s));
         carry = carry_next;
         cur = nxt; slot ^= 1;
     }
-    HIPCHK(hipStreamSynchronize(h->work_stream));
-    HIPCHK(hipStreamSynchronize(h->copy_stream));
+    TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
+    TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
     if (getenv("TAGDIG_INFLATE_STATS"))
         fprintf(stderr, "count_gzip_dev: %lu batches, %.1f MB sent to the GPU; waiting for the decoder %.3f s, for the copies %.3f s, for the kernels %.3f s\n",
                 (unsigned long)nbatch, up_bytes / 1e6, t_next, t_upload, t_sync);
@@ -1692,7 +1610,7 @@ struct GzGpuStream {
         const uint64_t seg = std::min<uint64_t>(n, SEG + MARGIN);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); why = "no device"; return false; }
-        const td_handle::GzGpu &g = h->gzgpu;
+        const td_handle::GzGpu &g = *h->gzgpu;
         const uint64_t have = free_b + g.d_in.n + g.d_tok.n * 4 + g.d_sym.n * 2 + g.d_out.n + g.d_win.n;
         if (seg * 34 + ((uint64_t)1 << 30) > have) { why = "no room on the device"; return false; }
         return true;
@@ -1705,8 +1623,8 @@ struct GzGpuStream {
         using PI = tdhost::ParInflate;
         *gave_up = false; *nbytes = 0; *last = false;
         auto giveup = [&](const char *w) { why = w; *gave_up = true; if (verbose) fprintf(stderr, "gz_gpu_inflate: %s (segment %lu)\n", w, (unsigned long)segments); return TD_OK; };
-        td_handle::GzGpu &g = h->gzgpu;
-        hipStream_t st = h->work_stream;
+        td_handle::GzGpu &g = *h->gzgpu;
+        hipStream_t st = h->work_stream.s;
         // (an allocation that fails -- another process on the card -- is a reason to leave the file to the host decoder, not an error)
         auto no_room = [&]() { (void)hipGetLastError(); return giveup("no room on the device"); };
         const double t0 = PI::now();
@@ -1716,8 +1634,9 @@ struct GzGpuStream {
         const uint64_t nb = up_end - base;
         const bool to_file_end = seg_end == n;
         const size_t buf_bytes = std::min<uint64_t>(n, SEG + 2 * MARGIN) + 8192 + 4096;
-        int rc = g.d_in.ensure(buf_bytes); if (rc) return no_room();
-        HIPCHK(hipStreamSynchronize(st));                                   // (the segment before may still read its bytes)
+        int rc = TD_OK;
+        if (g.d_in.ensure(buf_bytes) != hipSuccess) return no_room();
+        TD_HIPCHK(hipStreamSynchronize(st));                                   // (the segment before may still read its bytes)
         const uint8_t *din = nullptr;
         size_t in_cap = 0;
         if (pf_active) {
@@ -1731,8 +1650,8 @@ struct GzGpuStream {
         }
         if (!din) {
             in_cap = ((nb + 4096 + 15) & ~(size_t)15);
-            HIPCHK(hipMemsetAsync(g.d_in.p + (nb & ~(size_t)15), 0, in_cap - (nb & ~(size_t)15), h->copy_stream));
-            HIPCHK(hipStreamSynchronize(h->copy_stream));
+            TD_HIPCHK(hipMemsetAsync(g.d_in.p + (nb & ~(size_t)15), 0, in_cap - (nb & ~(size_t)15), h->copy_stream.s));
+            TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
             rc = td_load_file_range(h, path, base, nb, g.d_in.p); if (rc) return rc;
             din = g.d_in.p; cur_alt = false;
         }
@@ -1742,15 +1661,15 @@ struct GzGpuStream {
         // 1. block starts
         const uint64_t terr = (uint64_t)h->gz_gpu_terr_kb << 10;
         const uint32_t nterr = (uint32_t)((seg_end - base + terr - 1) / terr);
-        rc = g.d_found.ensure(nterr + 4); if (rc) return no_room();
-        HIPCHK(hipMemsetAsync(g.d_found.p + nterr, 0, 32, st));
+        if (g.d_found.ensure(nterr + 4) != hipSuccess) return no_room();
+        TD_HIPCHK(hipMemsetAsync(g.d_found.p + nterr, 0, 32, st));
         if (nterr > 1)
             hipLaunchKernelGGL(tdgz2::k_gz_find, dim3((nterr - 1 + tdgz2::WAVES - 1) / tdgz2::WAVES), dim3(64 * tdgz2::WAVES), 0, st,
                                din, in_bits, nwords, first_bit, terr * 8, nterr, g.d_found.p, (uint32_t)h->gz_gpu_verify, 1u);
-        HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipGetLastError());
         std::vector<uint64_t> found(nterr);
-        if (nterr > 1) HIPCHK(hipMemcpyAsync(found.data() + 1, g.d_found.p + 1, (size_t)(nterr - 1) * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        if (nterr > 1) TD_HIPCHK(hipMemcpyAsync(found.data() + 1, g.d_found.p + 1, (size_t)(nterr - 1) * 8, hipMemcpyDeviceToHost, st));
+        TD_HIPCHK(hipStreamSynchronize(st));
         found[0] = tdgz2::NONE;
         if (h->gz_gpu_false_every > 0)
             for (uint32_t t = 1; t < nterr; t++)
@@ -1772,18 +1691,18 @@ struct GzGpuStream {
                 chunks[i].tok_off = at; chunks[i].tok_cap = (uint32_t)cap;
                 at += (cap + 63) & ~(uint64_t)63;
             }
-            rc = g.d_tok.ensure(at + 64); if (rc) return no_room();
+            if (g.d_tok.ensure(at + 64) != hipSuccess) return no_room();
         }
-        rc = g.d_chunks.ensure(2 * (size_t)nchunks); if (rc) return no_room();               // (behind the chunks: the ones decoded a second time)
-        rc = g.d_res.ensure(2 * (size_t)nchunks); if (rc) return no_room();
-        HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(g.d_res.p, 0, (size_t)nchunks * sizeof(tdgz2::ChunkOut), st));
+        if (g.d_chunks.ensure(2 * (size_t)nchunks) != hipSuccess) return no_room();               // (behind the chunks: the ones decoded a second time)
+        if (g.d_res.ensure(2 * (size_t)nchunks) != hipSuccess) return no_room();
+        TD_HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
+        TD_HIPCHK(hipMemsetAsync(g.d_res.p, 0, (size_t)nchunks * sizeof(tdgz2::ChunkOut), st));
         hipLaunchKernelGGL(tdgz2::k_gz_tokens, dim3((nchunks + tdgz2::WAVES - 1) / tdgz2::WAVES), dim3(64 * tdgz2::WAVES), 0, st,
                            din, in_bits, nwords, g.d_chunks.p, nchunks, g.d_tok.p, g.d_res.p);
-        HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipGetLastError());
         std::vector<tdgz2::ChunkOut> res(nchunks);
-        HIPCHK(hipMemcpyAsync(res.data(), g.d_res.p, (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        TD_HIPCHK(hipMemcpyAsync(res.data(), g.d_res.p, (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyDeviceToHost, st));
+        TD_HIPCHK(hipStreamSynchronize(st));
         const double t3 = PI::now();
         // 3. the chain: every chunk begins where its predecessor ended.  A chunk that ran past its successor's start met a false
         // one there: the successor is dropped, and what lies between this chunk's end and the next start is decoded in a second
@@ -1841,12 +1760,12 @@ struct GzGpuStream {
             std::vector<tdgz2::Chunk> rc_in(nr);
             std::vector<tdgz2::ChunkOut> rc_out(nr);
             for (uint32_t q = 0; q < nr; q++) rc_in[q] = chunks[redo[q]];
-            HIPCHK(hipMemcpyAsync(g.d_chunks.p + nchunks, rc_in.data(), (size_t)nr * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
+            TD_HIPCHK(hipMemcpyAsync(g.d_chunks.p + nchunks, rc_in.data(), (size_t)nr * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(tdgz2::k_gz_tokens, dim3((nr + tdgz2::WAVES - 1) / tdgz2::WAVES), dim3(64 * tdgz2::WAVES), 0, st, din, in_bits, nwords,
                                g.d_chunks.p + nchunks, nr, g.d_tok.p, g.d_res.p + nchunks);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(rc_out.data(), g.d_res.p + nchunks, (size_t)nr * sizeof(tdgz2::ChunkOut), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
+            TD_HIPCHK(hipGetLastError());
+            TD_HIPCHK(hipMemcpyAsync(rc_out.data(), g.d_res.p + nchunks, (size_t)nr * sizeof(tdgz2::ChunkOut), hipMemcpyDeviceToHost, st));
+            TD_HIPCHK(hipStreamSynchronize(st));
             for (uint32_t q = 0; q < nr; q++) res[redo[q]] = rc_out[q];
             if (verbose) fprintf(stderr, "gz_gpu_inflate: %u false block starts; the stretches behind them decoded again\n", nr);
         }
@@ -1856,8 +1775,8 @@ struct GzGpuStream {
             for (uint32_t i = 0; i < nchunks; i++) if (!dead[i]) { chunks[w] = chunks[i]; res[w] = res[i]; w++; }
             chunks.resize(w); res.resize(w);
             nchunks = w;
-            HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(g.d_res.p, res.data(), (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyHostToDevice, st));
+            TD_HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
+            TD_HIPCHK(hipMemcpyAsync(g.d_res.p, res.data(), (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyHostToDevice, st));
         }
         std::vector<uint64_t> sym_off(nchunks + 1);
         uint64_t total = 0;
@@ -1888,27 +1807,27 @@ struct GzGpuStream {
         const uint32_t nblk = (uint32_t)nblk64;
         {
             size_t free_b = 0, total_b = 0;
-            HIPCHK(hipMemGetInfo(&free_b, &total_b));
+            TD_HIPCHK(hipMemGetInfo(&free_b, &total_b));
             const uint64_t need = 2 * total + total + ZB_CARRY + (uint64_t)nchunks * tdgz2::WINDOW + (uint64_t)nblk * 40 + ((uint64_t)64 << 20);
             if (need > free_b + g.d_sym.n * 2 + g.d_out.n + g.d_win.n) return giveup("no room on the device for the text");
         }
-        rc = g.d_sym.ensure(total + 64); if (rc) return no_room();
+        if (g.d_sym.ensure(total + 64) != hipSuccess) return no_room();
         if (g.d_out.n < ZB_CARRY + total + 4096 + (total >> 3)) {
             // (the carried bytes lie at the front of the old buffer)
             DevBuf<uint8_t> bigger;
-            rc = bigger.ensure(ZB_CARRY + total + 4096 + (total >> 3) + (total >> 2)); if (rc) return no_room();
-            if (carry) HIPCHK(hipMemcpyAsync(bigger.p, g.d_out.p, carry, hipMemcpyDeviceToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));
-            g.d_out.release();
-            g.d_out = bigger; bigger.p = nullptr; bigger.n = 0;
+            if (bigger.alloc(ZB_CARRY + total + 4096 + (total >> 3) + (total >> 2)) != hipSuccess) return no_room();
+            if (carry) TD_HIPCHK(hipMemcpyAsync(bigger.p, g.d_out.p, carry, hipMemcpyDeviceToDevice, st));
+            TD_HIPCHK(hipStreamSynchronize(st));
+            g.d_out.swap(bigger);
+            bigger.reset();                                                 // (the old text: freed here, before the allocations below)
         }
-        rc = g.d_win.ensure((size_t)nchunks * tdgz2::WINDOW); if (rc) return no_room();
-        rc = g.d_carry.ensure(tdgz2::WINDOW); if (rc) return no_room();
-        rc = g.d_symoff.ensure(nchunks + 1); if (rc) return no_room();
-        rc = g.d_blk.ensure(nblk + 1); if (rc) return no_room();
-        rc = g.d_crc.ensure(nblk + 1); if (rc) return no_room();
-        rc = h->d_gzflag.ensure(4); if (rc) return no_room();
-        if (!h->d_crctab) { bool ok = true; rc = ensure_bgzf_buffers(h, 0, 0, &ok); if (rc) return rc; }      // (the CRC tables)
+        if (g.d_win.ensure((size_t)nchunks * tdgz2::WINDOW) != hipSuccess) return no_room();
+        if (g.d_carry.ensure(tdgz2::WINDOW) != hipSuccess) return no_room();
+        if (g.d_symoff.ensure(nchunks + 1) != hipSuccess) return no_room();
+        if (g.d_blk.ensure(nblk + 1) != hipSuccess) return no_room();
+        if (g.d_crc.ensure(nblk + 1) != hipSuccess) return no_room();
+        if (h->d_gzflag.ensure(4) != hipSuccess) return no_room();
+        if (!h->d_crctab.p) { bool ok = true; rc = ensure_bgzf_buffers(h, 0, 0, &ok); if (rc) return rc; }      // (the CRC tables)
         std::vector<tdgz::Block> blocks(nblk);
         {
             size_t kb = 0;
@@ -1918,14 +1837,14 @@ struct GzGpuStream {
                     blocks[kb++] = tdgz::Block{(sym_off[i] + o) * 2, sym_off[i] + o, (uint32_t)std::min<uint64_t>(tdgz::BLOCK_SYMS, res[i].out_len - o), i, min_idx, 0u};
             }
         }
-        HIPCHK(hipMemcpyAsync(g.d_symoff.p, sym_off.data(), (size_t)(nchunks + 1) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(g.d_blk.p, blocks.data(), (size_t)nblk * sizeof(tdgz::Block), hipMemcpyHostToDevice, st));
-        if (member_fresh) HIPCHK(hipMemsetAsync(g.d_carry.p, 0, tdgz2::WINDOW, st));           // (a member begins with nothing behind it)
-        HIPCHK(hipMemsetAsync(h->d_gzflag.p, 0, 16, st));
+        TD_HIPCHK(hipMemcpyAsync(g.d_symoff.p, sym_off.data(), (size_t)(nchunks + 1) * 8, hipMemcpyHostToDevice, st));
+        TD_HIPCHK(hipMemcpyAsync(g.d_blk.p, blocks.data(), (size_t)nblk * sizeof(tdgz::Block), hipMemcpyHostToDevice, st));
+        if (member_fresh) TD_HIPCHK(hipMemsetAsync(g.d_carry.p, 0, tdgz2::WINDOW, st));           // (a member begins with nothing behind it)
+        TD_HIPCHK(hipMemsetAsync(h->d_gzflag.p, 0, 16, st));
         if (!to_file_end) {
             // the bytes behind this segment on their way while its symbols, windows, bytes and CRC-32 are made and its text is
             // counted: the next segment begins somewhere in the first MARGIN of them.  (Started here, behind this segment's
-            // allocations: hipMalloc and hipFree wait for the copies in flight.)
+            // allocations: allocating and freeing device memory wait for the copies in flight.)
             rc = g.d_in2.ensure(buf_bytes); if (rc) return no_room();
             pf_buf = cur_alt ? g.d_in.p : g.d_in2.p;
             pf_base = seg_end & ~(uint64_t)4095;
@@ -1935,24 +1854,24 @@ struct GzGpuStream {
             pf_active = true;
             pf_thread = std::thread([this]() {
                 if (hipSetDevice(h->device) != hipSuccess) { pf_rc = TD_E_INTERNAL; return; }
-                if (hipMemsetAsync(pf_buf + (pf_nb & ~(uint64_t)15), 0, pf_cap - (pf_nb & ~(uint64_t)15), h->copy_stream) != hipSuccess ||
-                    hipStreamSynchronize(h->copy_stream) != hipSuccess) { pf_rc = TD_E_INTERNAL; return; }
+                if (hipMemsetAsync(pf_buf + (pf_nb & ~(uint64_t)15), 0, pf_cap - (pf_nb & ~(uint64_t)15), h->copy_stream.s) != hipSuccess ||
+                    hipStreamSynchronize(h->copy_stream.s) != hipSuccess) { pf_rc = TD_E_INTERNAL; return; }
                 pf_rc = td_load_file_range(h, path, pf_base, pf_nb, pf_buf);
             });
         }
-        hipEvent_t ev[5] = {};
-        auto mark = [&](int k) { if (verbose) { if (!ev[k]) (void)hipEventCreate(&ev[k]); (void)hipEventRecord(ev[k], st); } };
+        Event ev[5];
+        auto mark = [&](int k) { if (verbose) { if (!ev[k].e) (void)ev[k].create(); (void)hipEventRecord(ev[k].e, st); } };
         mark(0);
         hipLaunchKernelGGL(tdgz2::k_gz_lz, dim3((nchunks + tdgz2::WAVES - 1) / tdgz2::WAVES), dim3(64 * tdgz2::WAVES), 0, st,
                            g.d_tok.p, g.d_chunks.p, g.d_res.p, g.d_symoff.p, nchunks, g.d_sym.p);
         mark(1);
         {   // the windows: segments of chunks (gz_gpu.hpp, 5.)
             const uint32_t seg_len = 32, nseg = (nchunks + seg_len - 1) / seg_len;
-            rc = g.d_maps.ensure((size_t)nseg * tdgz2::WINDOW); if (rc) return no_room();
-            rc = g.d_segwin.ensure((size_t)nseg * tdgz2::WINDOW); if (rc) return no_room();
+            if (g.d_maps.ensure((size_t)nseg * tdgz2::WINDOW) != hipSuccess) return no_room();
+            if (g.d_segwin.ensure((size_t)nseg * tdgz2::WINDOW) != hipSuccess) return no_room();
             if (!h->gz_attr_done) {                                          // (per device: a handle has one)
-                HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)tdgz2::WINDOW));
-                HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (int)tdgz2::WINDOW));
+                TD_HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)tdgz2::WINDOW));
+                TD_HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (int)tdgz2::WINDOW));
                 h->gz_attr_done = true;
             }
             hipLaunchKernelGGL(tdgz2::k_gz_windows<uint16_t>, dim3(nseg), dim3(1024), 4 * tdgz2::WINDOW, st, g.d_sym.p, g.d_symoff.p, g.d_res.p, nchunks, seg_len,
@@ -1967,24 +1886,23 @@ struct GzGpuStream {
         if (nblk) {
             hipLaunchKernelGGL(tdgz::k_gz_resolve, dim3(nblk), dim3(256), 0, st, (const uint8_t *)g.d_sym.p, g.d_win.p, g.d_out.p + carry, g.d_blk.p, nblk, h->d_gzflag.p);
             mark(3);
-            hipLaunchKernelGGL(tdgz::k_gz_crc, dim3((nblk + 63) / 64), dim3(64), 0, st, g.d_out.p + carry, g.d_blk.p, nblk, h->d_crctab, g.d_crc.p);
+            hipLaunchKernelGGL(tdgz::k_gz_crc, dim3((nblk + 63) / 64), dim3(64), 0, st, g.d_out.p + carry, g.d_blk.p, nblk, h->d_crctab.p, g.d_crc.p);
             mark(4);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(crcs.data(), g.d_crc.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, st));
+            TD_HIPCHK(hipGetLastError());
+            TD_HIPCHK(hipMemcpyAsync(crcs.data(), g.d_crc.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, st));
         }
-        HIPCHK(hipMemcpyAsync(&flag, h->d_gzflag.p, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        TD_HIPCHK(hipMemcpyAsync(&flag, h->d_gzflag.p, 4, hipMemcpyDeviceToHost, st));
+        TD_HIPCHK(hipStreamSynchronize(st));
         const double t4 = PI::now();
         if (verbose && nblk) {
             float a = 0, b = 0, c = 0, d = 0;
-            (void)hipEventElapsedTime(&a, ev[0], ev[1]); (void)hipEventElapsedTime(&b, ev[1], ev[2]); (void)hipEventElapsedTime(&c, ev[2], ev[3]); (void)hipEventElapsedTime(&d, ev[3], ev[4]);
+            (void)hipEventElapsedTime(&a, ev[0].e, ev[1].e); (void)hipEventElapsedTime(&b, ev[1].e, ev[2].e); (void)hipEventElapsedTime(&c, ev[2].e, ev[3].e); (void)hipEventElapsedTime(&d, ev[3].e, ev[4].e);
             uint64_t ntok = 0, nslow = 0; for (const auto &o : res) { ntok += o.ntok; nslow += o.nslow; }
             fprintf(stderr, "gz_gpu_inflate: %.1f %% of the tokens by the scalar code (a code longer than the table's index)\n", 100.0 * (double)nslow / (double)std::max<uint64_t>(1, ntok));
             fprintf(stderr, "gz_gpu_inflate: segment %lu: %.1f MB -> %.1f MB, %u chunks, %.1f M tokens: upload %.1f ms, block search %.1f ms, Huffman decoding %.1f ms, "
                     "k_gz_lz %.1f ms, windows %.1f ms, k_gz_resolve %.1f ms, k_gz_crc %.1f ms\n", (unsigned long)segments, (double)(seg_end - base) / 1e6, total / 1e6,
                     nchunks, ntok / 1e6, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, a, b, c, d);
         }
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         t_up += t1 - t0; t_find += t2 - t1; t_tok += t3 - t2; t_rest += t4 - t3;
         if (flag) return fail(TD_E_IO, "gzip: distance reaches before the start of the output");
         for (uint32_t k = 0; k < nblk; k++) crc_run = FI::crc32_join(crc_run, crcs[k], blocks[k].len);
@@ -2015,12 +1933,11 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         if (zs.verbose) fprintf(stderr, "gz_gpu_inflate: %s -- the host decoder takes the file\n", zs.why);
         return TD_OK;
     }
-    hipStream_t st = h->work_stream;
-    HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, st));
-    if (!h->pin_cursor) HIPCHK(hipHostMalloc((void **)&h->pin_cursor, 16, hipHostMallocDefault));
-    h->pin_cursor[0] = 0;
-    uint8_t *pin_tail = nullptr;
-    struct Free { uint8_t *&p; ~Free() { if (p) (void)hipHostFree(p); } } free_tail{pin_tail};
+    hipStream_t st = h->work_stream.s;
+    TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, st));
+    if (!h->pin_cursor.p) TD_HIPCHK(h->pin_cursor.alloc(2));
+    h->pin_cursor.p[0] = 0;
+    PinBuf<uint8_t> pin_tail;
     const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
     size_t carry = 0;
     uint64_t line_at = 0;                                                  // weights: index of the line the next piece starts with
@@ -2037,16 +1954,16 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
             return fail(TD_E_IO, std::string("gzip (device decoder): ") + zs.why);
         }
         *not_applicable = false;                                           // (from here on the file's verdict is this decoder's)
-        td_handle::GzGpu &g = h->gzgpu;
+        td_handle::GzGpu &g = *h->gzgpu;
         const size_t total = carry + nb;
         size_t cut = total;
         if (!last && total) {
-            if (!pin_tail) HIPCHK(hipHostMalloc((void **)&pin_tail, ZB_TAIL, hipHostMallocDefault));
+            if (!pin_tail.p) TD_HIPCHK(pin_tail.alloc(ZB_TAIL));
             const size_t ntail = std::min(total, ZB_TAIL);
-            HIPCHK(hipMemcpyAsync(pin_tail, g.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            size_t c = cut_at_line_end(pin_tail, ntail);
-            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, pin_tail, ntail, st, &line_at, &c); if (rc) return rc; }
+            TD_HIPCHK(hipMemcpyAsync(pin_tail.p, g.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, st));
+            TD_HIPCHK(hipStreamSynchronize(st));
+            size_t c = cut_at_line_end(pin_tail.p, ntail);
+            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, pin_tail.p, ntail, st, &line_at, &c); if (rc) return rc; }
             if (c == 0) {
                 if (total > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
                 cut = 0;
@@ -2059,24 +1976,23 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
             rc = launch_count(h, g.d_out.p, cut, 0, max_reads, weights, st, h->d_cursor.p + (pieces & 1), h->d_cursor.p + ((pieces + 1) & 1), bytes_submitted);
             if (rc) return rc;
             bytes_submitted += cut; pieces++;
-            HIPCHK(hipMemcpyAsync(h->pin_cursor, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, st));
+            TD_HIPCHK(hipMemcpyAsync(h->pin_cursor.p, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, st));
         }
         const size_t carry_next = total - cut;
         if (!last && carry_next) {
             // (to the front of the same buffer, behind the count: the pieces do not overlap when the text is longer than twice the carry)
-            if (cut >= carry_next) HIPCHK(hipMemcpyAsync(g.d_out.p, g.d_out.p + cut, carry_next, hipMemcpyDeviceToDevice, st));
+            if (cut >= carry_next) TD_HIPCHK(hipMemcpyAsync(g.d_out.p, g.d_out.p + cut, carry_next, hipMemcpyDeviceToDevice, st));
             else {
-                DevBuf<uint8_t> tmp; rc = tmp.ensure(carry_next); if (rc) return rc;
-                HIPCHK(hipMemcpyAsync(tmp.p, g.d_out.p + cut, carry_next, hipMemcpyDeviceToDevice, st));
-                HIPCHK(hipMemcpyAsync(g.d_out.p, tmp.p, carry_next, hipMemcpyDeviceToDevice, st));
-                HIPCHK(hipStreamSynchronize(st));
-                tmp.release();
+                DevBuf<uint8_t> tmp; TD_HIPCHK(tmp.alloc(carry_next));
+                TD_HIPCHK(hipMemcpyAsync(tmp.p, g.d_out.p + cut, carry_next, hipMemcpyDeviceToDevice, st));
+                TD_HIPCHK(hipMemcpyAsync(g.d_out.p, tmp.p, carry_next, hipMemcpyDeviceToDevice, st));
+                TD_HIPCHK(hipStreamSynchronize(st));
             }
         }
-        HIPCHK(hipStreamSynchronize(st));
+        TD_HIPCHK(hipStreamSynchronize(st));
         carry = carry_next;
         if (last) break;
-        if (h->pin_cursor[0] >= stop_line) break;                          // (the segments counted so far already hold read number max_reads)
+        if (h->pin_cursor.p[0] >= stop_line) break;                          // (the segments counted so far already hold read number max_reads)
     }
     if (!h->sink) h->last_gz_route = 1;       // (td_last_gz_route speaks of the files td_count_file counted only)
     if (zs.verbose)
@@ -2104,8 +2020,8 @@ int count_gz_by_reference_rules(td_handle *h, const char *path, uint64_t max_rea
         return fail(rc, refusal + " (the reference's loop ends before it meets this; the results were accumulating, so the file is not counted again)");
     int rc2 = h->sink ? h->sink->restart(h->sink->ctx) : zero_results(h); if (rc2) return rc2;
     if (h->bound_counts && !h->sink) {
-        HIPCHK(hipMemsetAsync(h->bound_counts, 0, (size_t)h->barnum * h->ntags * 4, h->work_stream));
-        HIPCHK(hipStreamSynchronize(h->work_stream));
+        TD_HIPCHK(hipMemsetAsync(h->bound_counts, 0, (size_t)h->barnum * h->ntags * 4, h->work_stream.s));
+        TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
     }
     tdhost::PyGzipReader pr(mf.p, mf.n);
     bool through = false;
@@ -2126,7 +2042,7 @@ extern "C" {
 
 int td_gunzip_file_gpu(td_handle *h, const char *path, void *dst, uint64_t capacity, uint64_t *n_out, int *on_gpu) {
     if (!h || !path || !n_out || !on_gpu || (!dst && capacity)) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     *n_out = 0; *on_gpu = 0;
     GzGpuStream zs(h, path);
     if (!zs.open()) return TD_OK;
@@ -2137,7 +2053,7 @@ int td_gunzip_file_gpu(td_handle *h, const char *path, void *dst, uint64_t capac
         if (rc) return rc;
         if (gave_up) return TD_OK;                                         // (whatever was copied so far is not reported)
         if (at + nb > capacity) return fail(TD_E_LIMIT, "destination too small");
-        if (nb) HIPCHK(hipMemcpy((uint8_t *)dst + at, h->gzgpu.d_out.p, nb, hipMemcpyDeviceToHost));
+        if (nb) TD_HIPCHK(hipMemcpy((uint8_t *)dst + at, h->gzgpu->d_out.p, nb, hipMemcpyDeviceToHost));
         at += nb;
         if (last) break;
     }
@@ -2154,7 +2070,7 @@ int td_last_gz_route(td_handle *h) { return h ? h->last_gz_route : 0; }
 int td_gz_shard_open(td_handle *h, const char *path, uint64_t byte_lo, uint64_t byte_hi, int first, uint64_t *start_bit, uint64_t *file_bytes) {
     using FI = tdhost::FastInflate;
     if (!h || !path || !start_bit || !file_bytes) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     td_handle::GzShard &sh = h->gzshard;
     sh = td_handle::GzShard();
     MappedFile mf(path);
@@ -2173,28 +2089,28 @@ int td_gz_shard_open(td_handle *h, const char *path, uint64_t byte_lo, uint64_t 
     const uint64_t MARGIN = (uint64_t)h->gz_gpu_margin_kb << 10, SEG = (uint64_t)h->gz_gpu_seg_kb << 10;
     const uint64_t base = byte_lo & ~(uint64_t)4095, up_end = std::min<uint64_t>(n, byte_hi + MARGIN), nb = up_end - base;
     if (nb > SEG + 2 * MARGIN) return fail(TD_E_LIMIT, "gzip shard larger than a segment");
-    td_handle::GzGpu &g = h->gzgpu;
-    int rc = g.d_in.ensure(nb + 8192 + 4096); if (rc) return rc;
+    td_handle::GzGpu &g = *h->gzgpu;
+    TD_HIPCHK(g.d_in.ensure(nb + 8192 + 4096));
     const size_t in_cap = ((nb + 4096 + 15) & ~(size_t)15);
-    HIPCHK(hipStreamSynchronize(h->work_stream));
-    HIPCHK(hipMemsetAsync(g.d_in.p + (nb & ~(size_t)15), 0, in_cap - (nb & ~(size_t)15), h->copy_stream));
-    HIPCHK(hipStreamSynchronize(h->copy_stream));
-    rc = td_load_file_range(h, path, base, nb, g.d_in.p); if (rc) return rc;
+    TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
+    TD_HIPCHK(hipMemsetAsync(g.d_in.p + (nb & ~(size_t)15), 0, in_cap - (nb & ~(size_t)15), h->copy_stream.s));
+    TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
+    int rc = td_load_file_range(h, path, base, nb, g.d_in.p); if (rc) return rc;
     const uint64_t in_bits = nb * 8, nwords = in_cap / 4;
     const uint64_t terr = (uint64_t)h->gz_gpu_terr_kb << 10;
     const uint32_t nterr = (uint32_t)((byte_hi - base + terr - 1) / terr);
     // block starts at or behind byte_lo (the first rank: behind its known start)
     const uint64_t lo_rel = first ? first_abs - base * 8 : std::max<uint64_t>((byte_lo - base) * 8, 1) - 1;
-    rc = g.d_found.ensure(nterr + 4); if (rc) return rc;
-    hipStream_t st = h->work_stream;
-    HIPCHK(hipMemsetAsync(g.d_found.p, 0xFF, (size_t)nterr * 8, st));
-    HIPCHK(hipMemsetAsync(g.d_found.p + nterr, 0, 32, st));
+    TD_HIPCHK(g.d_found.ensure(nterr + 4));
+    hipStream_t st = h->work_stream.s;
+    TD_HIPCHK(hipMemsetAsync(g.d_found.p, 0xFF, (size_t)nterr * 8, st));
+    TD_HIPCHK(hipMemsetAsync(g.d_found.p + nterr, 0, 32, st));
     hipLaunchKernelGGL(tdgz2::k_gz_find, dim3((nterr + tdgz2::WAVES - 1) / tdgz2::WAVES), dim3(64 * tdgz2::WAVES), 0, st,
                        g.d_in.p, in_bits, nwords, lo_rel, terr * 8, nterr, g.d_found.p, (uint32_t)h->gz_gpu_verify, 0u);
-    HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     sh.found.assign(nterr, tdgz2::NONE);
-    HIPCHK(hipMemcpyAsync(sh.found.data(), g.d_found.p, (size_t)nterr * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    TD_HIPCHK(hipMemcpyAsync(sh.found.data(), g.d_found.p, (size_t)nterr * 8, hipMemcpyDeviceToHost, st));
+    TD_HIPCHK(hipStreamSynchronize(st));
     // (a start at or past byte_hi is the next rank's)
     const uint64_t hi_rel = (byte_hi - base) * 8;
     for (auto &f : sh.found) if (f != tdgz2::NONE && f >= hi_rel) f = tdgz2::NONE;
@@ -2210,11 +2126,11 @@ int td_gz_shard_open(td_handle *h, const char *path, uint64_t byte_lo, uint64_t 
 // stop_bit: where the next rank with a start begins (~0: this rank's stretch runs to the member's end).  *final: it ended the member.
 int td_gz_shard_decode(td_handle *h, uint64_t stop_bit, uint64_t *end_bit, uint64_t *out_len, int *final, uint16_t *map_out) {
     if (!h || !end_bit || !out_len || !final || !map_out) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     td_handle::GzShard &sh = h->gzshard;
-    td_handle::GzGpu &g = h->gzgpu;
+    td_handle::GzGpu &g = *h->gzgpu;
     if (!sh.open || sh.start_rel == tdgz2::NONE) return fail(TD_E_STATE, "td_gz_shard_open found no block start for this rank");
-    hipStream_t st = h->work_stream;
+    hipStream_t st = h->work_stream.s;
     const uint64_t stop_rel = stop_bit == ~0ull ? ~0ull : stop_bit - sh.base * 8;
     if (stop_rel != ~0ull && stop_rel > sh.in_bits) return fail(TD_E_LIMIT, "gzip shard: the next rank's start lies beyond this rank's bytes");
     std::vector<tdgz2::Chunk> chunks;
@@ -2231,18 +2147,18 @@ int td_gz_shard_decode(td_handle *h, uint64_t stop_bit, uint64_t *end_bit, uint6
             chunks[i].tok_off = at; chunks[i].tok_cap = (uint32_t)cap;
             at += (cap + 63) & ~(uint64_t)63;
         }
-        int rc = g.d_tok.ensure(at + 64); if (rc) return rc;
+        TD_HIPCHK(g.d_tok.ensure(at + 64));
     }
-    int rc = g.d_chunks.ensure(2 * (size_t)nchunks); if (rc) return rc;
-    rc = g.d_res.ensure(2 * (size_t)nchunks); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(g.d_res.p, 0, (size_t)nchunks * sizeof(tdgz2::ChunkOut), st));
+    TD_HIPCHK(g.d_chunks.ensure(2 * (size_t)nchunks));
+    TD_HIPCHK(g.d_res.ensure(2 * (size_t)nchunks));
+    TD_HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
+    TD_HIPCHK(hipMemsetAsync(g.d_res.p, 0, (size_t)nchunks * sizeof(tdgz2::ChunkOut), st));
     hipLaunchKernelGGL(tdgz2::k_gz_tokens, dim3((nchunks + tdgz2::WAVES - 1) / tdgz2::WAVES), dim3(64 * tdgz2::WAVES), 0, st,
                        g.d_in.p, sh.in_bits, sh.nwords, g.d_chunks.p, nchunks, g.d_tok.p, g.d_res.p);
-    HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     std::vector<tdgz2::ChunkOut> res(nchunks);
-    HIPCHK(hipMemcpyAsync(res.data(), g.d_res.p, (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    TD_HIPCHK(hipMemcpyAsync(res.data(), g.d_res.p, (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyDeviceToHost, st));
+    TD_HIPCHK(hipStreamSynchronize(st));
     // the chain inside the rank (a false start is dropped where the chunk in front of it ends on a later start; anything else
     // sends the file to the one-rank path)
     std::vector<uint8_t> dead(nchunks, 0);
@@ -2261,32 +2177,32 @@ int td_gz_shard_decode(td_handle *h, uint64_t stop_bit, uint64_t *end_bit, uint6
         uint32_t w = 0;
         for (uint32_t i = 0; i < nchunks; i++) if (!dead[i]) { chunks[w] = chunks[i]; res[w] = res[i]; w++; }
         chunks.resize(w); res.resize(w); nchunks = w;
-        HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(g.d_res.p, res.data(), (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyHostToDevice, st));
+        TD_HIPCHK(hipMemcpyAsync(g.d_chunks.p, chunks.data(), (size_t)nchunks * sizeof(tdgz2::Chunk), hipMemcpyHostToDevice, st));
+        TD_HIPCHK(hipMemcpyAsync(g.d_res.p, res.data(), (size_t)nchunks * sizeof(tdgz2::ChunkOut), hipMemcpyHostToDevice, st));
     }
     sh.sym_off.assign(nchunks + 1, 0);
     uint64_t total = 0;
     for (uint32_t i = 0; i < nchunks; i++) { sh.sym_off[i] = total; total += res[i].out_len; }
     sh.sym_off[nchunks] = total;
-    rc = g.d_sym.ensure(total + 64); if (rc) return rc;
-    rc = g.d_symoff.ensure(nchunks + 1); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g.d_symoff.p, sh.sym_off.data(), (size_t)(nchunks + 1) * 8, hipMemcpyHostToDevice, st));
+    TD_HIPCHK(g.d_sym.ensure(total + 64));
+    TD_HIPCHK(g.d_symoff.ensure(nchunks + 1));
+    TD_HIPCHK(hipMemcpyAsync(g.d_symoff.p, sh.sym_off.data(), (size_t)(nchunks + 1) * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(tdgz2::k_gz_lz, dim3((nchunks + tdgz2::WAVES - 1) / tdgz2::WAVES), dim3(64 * tdgz2::WAVES), 0, st,
                        g.d_tok.p, g.d_chunks.p, g.d_res.p, g.d_symoff.p, nchunks, g.d_sym.p);
     const uint32_t seg_len = 32, nseg = (nchunks + seg_len - 1) / seg_len;
-    rc = g.d_maps.ensure((size_t)(nseg + 1) * tdgz2::WINDOW); if (rc) return rc;
+    TD_HIPCHK(g.d_maps.ensure((size_t)(nseg + 1) * tdgz2::WINDOW));
     if (!h->gz_attr_done) {
-        HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)tdgz2::WINDOW));
-        HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (int)tdgz2::WINDOW));
+        TD_HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)tdgz2::WINDOW));
+        TD_HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_windows<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (int)tdgz2::WINDOW));
         h->gz_attr_done = true;
     }
-    HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_compose_maps, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)tdgz2::WINDOW));
+    TD_HIPCHK(hipFuncSetAttribute((const void *)tdgz2::k_gz_compose_maps, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)tdgz2::WINDOW));
     hipLaunchKernelGGL(tdgz2::k_gz_windows<uint16_t>, dim3(nseg), dim3(1024), 4 * tdgz2::WINDOW, st, g.d_sym.p, g.d_symoff.p, g.d_res.p, nchunks, seg_len,
                        (const uint16_t *)nullptr, g.d_maps.p, (uint8_t *)nullptr);
     hipLaunchKernelGGL(tdgz2::k_gz_compose_maps, dim3(1), dim3(1024), 4 * tdgz2::WINDOW, st, g.d_maps.p, nseg, g.d_maps.p + (size_t)nseg * tdgz2::WINDOW);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(map_out, g.d_maps.p + (size_t)nseg * tdgz2::WINDOW, (size_t)tdgz2::WINDOW * 2, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipMemcpyAsync(map_out, g.d_maps.p + (size_t)nseg * tdgz2::WINDOW, (size_t)tdgz2::WINDOW * 2, hipMemcpyDeviceToHost, st));
+    TD_HIPCHK(hipStreamSynchronize(st));
     sh.chunks = chunks; sh.res = res; sh.total = total; sh.nseg = nseg; sh.decoded = true;
     *end_bit = sh.base * 8 + res[nchunks - 1].end_bit;
     *out_len = total;
@@ -2300,25 +2216,26 @@ int td_gz_shard_decode(td_handle *h, uint64_t stop_bit, uint64_t *end_bit, uint6
 int td_gz_shard_resolve(td_handle *h, const uint8_t *window_in, uint64_t member_out_before, void **d_text, uint32_t *crc32) {
     using FI = tdhost::FastInflate;
     if (!h || !window_in || !d_text || !crc32) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     td_handle::GzShard &sh = h->gzshard;
-    td_handle::GzGpu &g = h->gzgpu;
+    td_handle::GzGpu &g = *h->gzgpu;
     if (!sh.decoded) return fail(TD_E_STATE, "td_gz_shard_decode has not run");
-    hipStream_t st = h->work_stream;
+    hipStream_t st = h->work_stream.s;
     const uint32_t nchunks = (uint32_t)sh.chunks.size(), seg_len = 32;
     const uint64_t total = sh.total;
     uint64_t nblk64 = 0;
     for (uint32_t i = 0; i < nchunks; i++) nblk64 += (sh.res[i].out_len + tdgz::BLOCK_SYMS - 1) / tdgz::BLOCK_SYMS;
     if (nblk64 >= 0x7FFFFFFFull) return fail(TD_E_LIMIT, "gzip shard too large");
     const uint32_t nblk = (uint32_t)nblk64;
-    int rc = g.d_out.ensure(total + 4096 + (total >> 3) + ((size_t)1 << 20)); if (rc) return rc;
-    rc = g.d_win.ensure((size_t)nchunks * tdgz2::WINDOW); if (rc) return rc;
-    rc = g.d_carry.ensure(tdgz2::WINDOW); if (rc) return rc;
-    rc = g.d_segwin.ensure((size_t)sh.nseg * tdgz2::WINDOW); if (rc) return rc;
-    rc = g.d_blk.ensure(nblk + 1); if (rc) return rc;
-    rc = g.d_crc.ensure(nblk + 1); if (rc) return rc;
-    rc = h->d_gzflag.ensure(4); if (rc) return rc;
-    if (!h->d_crctab) { bool ok = true; rc = ensure_bgzf_buffers(h, 0, 0, &ok); if (rc) return rc; }
+    TD_HIPCHK(g.d_out.ensure(total + 4096 + (total >> 3) + ((size_t)1 << 20)));
+    TD_HIPCHK(g.d_win.ensure((size_t)nchunks * tdgz2::WINDOW));
+    TD_HIPCHK(g.d_carry.ensure(tdgz2::WINDOW));
+    TD_HIPCHK(g.d_segwin.ensure((size_t)sh.nseg * tdgz2::WINDOW));
+    TD_HIPCHK(g.d_blk.ensure(nblk + 1));
+    TD_HIPCHK(g.d_crc.ensure(nblk + 1));
+    TD_HIPCHK(h->d_gzflag.ensure(4));
+    int rc = TD_OK;
+    if (!h->d_crctab.p) { bool ok = true; rc = ensure_bgzf_buffers(h, 0, 0, &ok); if (rc) return rc; }
     std::vector<tdgz::Block> blocks(nblk);
     {
         size_t kb = 0;
@@ -2328,9 +2245,9 @@ int td_gz_shard_resolve(td_handle *h, const uint8_t *window_in, uint64_t member_
                 blocks[kb++] = tdgz::Block{(sh.sym_off[i] + o) * 2, sh.sym_off[i] + o, (uint32_t)std::min<uint64_t>(tdgz::BLOCK_SYMS, sh.res[i].out_len - o), i, min_idx, 0u};
         }
     }
-    HIPCHK(hipMemcpyAsync(g.d_carry.p, window_in, tdgz2::WINDOW, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(g.d_blk.p, blocks.data(), (size_t)nblk * sizeof(tdgz::Block), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(h->d_gzflag.p, 0, 16, st));
+    TD_HIPCHK(hipMemcpyAsync(g.d_carry.p, window_in, tdgz2::WINDOW, hipMemcpyHostToDevice, st));
+    TD_HIPCHK(hipMemcpyAsync(g.d_blk.p, blocks.data(), (size_t)nblk * sizeof(tdgz::Block), hipMemcpyHostToDevice, st));
+    TD_HIPCHK(hipMemsetAsync(h->d_gzflag.p, 0, 16, st));
     hipLaunchKernelGGL(tdgz2::k_gz_seg_windows, dim3(1), dim3(1024), 0, st, g.d_maps.p, sh.nseg, g.d_segwin.p, g.d_carry.p);
     hipLaunchKernelGGL(tdgz2::k_gz_windows<uint8_t>, dim3(sh.nseg), dim3(1024), 2 * tdgz2::WINDOW, st, g.d_sym.p, g.d_symoff.p, g.d_res.p, nchunks, seg_len,
                        (const uint8_t *)g.d_segwin.p, (uint8_t *)nullptr, g.d_win.p);
@@ -2338,17 +2255,17 @@ int td_gz_shard_resolve(td_handle *h, const uint8_t *window_in, uint64_t member_
     uint32_t flag = 0;
     if (nblk) {
         hipLaunchKernelGGL(tdgz::k_gz_resolve, dim3(nblk), dim3(256), 0, st, (const uint8_t *)g.d_sym.p, g.d_win.p, g.d_out.p, g.d_blk.p, nblk, h->d_gzflag.p);
-        hipLaunchKernelGGL(tdgz::k_gz_crc, dim3((nblk + 63) / 64), dim3(64), 0, st, g.d_out.p, g.d_blk.p, nblk, h->d_crctab, g.d_crc.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(crcs.data(), g.d_crc.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(tdgz::k_gz_crc, dim3((nblk + 63) / 64), dim3(64), 0, st, g.d_out.p, g.d_blk.p, nblk, h->d_crctab.p, g.d_crc.p);
+        TD_HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipMemcpyAsync(crcs.data(), g.d_crc.p, (size_t)nblk * 4, hipMemcpyDeviceToHost, st));
     }
-    HIPCHK(hipMemcpyAsync(&flag, h->d_gzflag.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    TD_HIPCHK(hipMemcpyAsync(&flag, h->d_gzflag.p, 4, hipMemcpyDeviceToHost, st));
+    TD_HIPCHK(hipStreamSynchronize(st));
     if (flag) return fail(TD_E_IO, "gzip: distance reaches before the start of the output");
     uint32_t crc = 0;
     for (uint32_t k = 0; k < nblk; k++) crc = FI::crc32_join(crc, crcs[k], blocks[k].len);
     *crc32 = crc;
-    *d_text = g.d_out.p;
+    *d_text = g.d_out.p;                      // (a view: the buffer stays the handle's)
     return TD_OK;
 }
 
@@ -2367,7 +2284,7 @@ int td_count_host(td_handle *h, const void *fastq, uint64_t nbytes, uint64_t fir
                   int weights, uint64_t *lines_out) {
     if (!h) return fail(TD_E_ARG, "handle is NULL");
     if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     const uint8_t *src = (const uint8_t *)fastq;
     uint64_t pos = 0;
     auto reader = [&](uint8_t *dst, size_t want) -> long {
@@ -2469,12 +2386,12 @@ static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, i
 int td_count_file(td_handle *h, const char *path, uint64_t max_reads, int weights) {
     if (!h || !path) return fail(TD_E_ARG, "NULL argument");
     if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     return count_file_impl(h, path, max_reads, weights);
 }
 // for csrc/census.hip (hidden): the file through td_count_file's readers, its pieces handed to `sink`
 __attribute__((visibility("hidden"))) int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink) {
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     h->sink = sink;
     const int rc = count_file_impl(h, path, max_reads, 0);
     h->sink = nullptr;
@@ -2555,36 +2472,36 @@ static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, i
 // more than two staging pieces of the shard
 int td_load_file_range(td_handle *h, const char *path, uint64_t offset, uint64_t length, void *d_dst) {
     if (!h || !path || (!d_dst && length)) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     if (length == 0) return TD_OK;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(TD_E_IO, std::string("cannot open ") + path);
     struct FdEnd { int fd; ~FdEnd() { close(fd); } } fd_end{fd};
     constexpr size_t PIECE = (size_t)32 << 20;
     for (auto &lp : h->ldpiece) {
-        if (lp.pin) continue;
-        HIPCHK(hipHostMalloc((void **)&lp.pin, PIECE, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&lp.sent, hipEventDisableTiming));
+        if (lp.pin.p) continue;
+        TD_HIPCHK(lp.pin.alloc(PIECE));
+        TD_HIPCHK(lp.sent.create(hipEventDisableTiming));
     }
     int k = 0;
     for (uint64_t pos = 0; pos < length; pos += PIECE, k ^= 1) {
         td_handle::ZPiece &lp = h->ldpiece[k];
-        if (lp.busy) { HIPCHK(hipEventSynchronize(lp.sent)); lp.busy = false; }
+        if (lp.busy) { TD_HIPCHK(hipEventSynchronize(lp.sent.e)); lp.busy = false; }
         const size_t n = (size_t)std::min<uint64_t>(PIECE, length - pos);
         const bool ok = stage_parallel(n, [&](size_t off, size_t len) {
             while (len) {
-                const ssize_t got = pread(fd, lp.pin + off, len, (off_t)(offset + pos + off));
+                const ssize_t got = pread(fd, lp.pin.p + off, len, (off_t)(offset + pos + off));
                 if (got <= 0) return false;
                 off += (size_t)got; len -= (size_t)got;
             }
             return true;
         });
         if (!ok) return fail(TD_E_IO, "read error (or the file is shorter than offset + length)");
-        { const int urc = upload(h, (uint8_t *)d_dst + pos, lp.pin, n); if (urc) return urc; }
-        HIPCHK(hipEventRecord(lp.sent, h->copy_stream));
+        { const int urc = upload(h, (uint8_t *)d_dst + pos, lp.pin.p, n); if (urc) return urc; }
+        TD_HIPCHK(hipEventRecord(lp.sent.e, h->copy_stream.s));
         lp.busy = true;
     }
-    HIPCHK(hipStreamSynchronize(h->copy_stream));
+    TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
     for (auto &lp : h->ldpiece) lp.busy = false;
     return TD_OK;
 }
@@ -2612,7 +2529,7 @@ int td_bgzf_index(const char *path, uint64_t *member_off, uint32_t *member_isize
 int td_bgzf_inflate_range(td_handle *h, const char *path, uint64_t off_begin, uint64_t off_end, void *d_dst, uint64_t capacity,
                           uint64_t *nbytes_out) {
     if (!h || !path || !nbytes_out || (!d_dst && capacity)) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     *nbytes_out = 0;
     tdhost::GzSource src;
     if (!src.map_only(path)) return fail(TD_E_IO, std::string("cannot open ") + path);
@@ -2637,13 +2554,13 @@ int td_bgzf_inflate_range(td_handle *h, const char *path, uint64_t off_begin, ui
     int rc = ensure_bgzf_buffers(h, need_members, need_in, &ok);
     if (rc) return rc;
     if (!ok) return fail(TD_E_HIP, "no room on the device for the BGZF batch buffers");
-    const uint32_t batch_members = std::min<uint32_t>(h->zcap_members, h->zb_members);
-    const size_t batch_in = h->zcap_in, piece_cap = std::min(ZB_PIECE, h->zcap_in + 64);
+    const uint32_t batch_members = std::min<uint32_t>(h->bgzf->cap_members, h->zb_members);
+    const size_t batch_in = h->bgzf->cap_in, piece_cap = std::min(ZB_PIECE, h->bgzf->cap_in + 64);
     size_t pos = off_begin;
     uint64_t out_pos = 0;
     struct Batch { uint32_t n = 0; size_t out_total = 0; };
     auto prepare = [&](int slot, Batch &b) -> int {
-        td_handle::ZSlot &z = h->zslot[slot];
+        td_handle::ZSlot &z = h->bgzf->slot[slot];
         b = Batch();
         const size_t first = pos;
         while (pos < off_end && b.n < batch_members) {
@@ -2655,57 +2572,57 @@ int td_bgzf_inflate_range(td_handle *h, const char *path, uint64_t off_begin, ui
             const uint32_t crc = tail[0] | (tail[1] << 8) | (tail[2] << 16) | ((uint32_t)tail[3] << 24);
             const uint32_t isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
             if (isize > 65536) return fail(TD_E_IO, "BGZF member larger than 64 KiB");
-            z.pin_mem[b.n] = tdinf::Member{pos + hs - first, b.out_total, bs - hs - 8, isize, crc, 0};
+            z.pin_mem.p[b.n] = tdinf::Member{pos + hs - first, b.out_total, bs - hs - 8, isize, crc, 0};
             b.out_total += isize; b.n++;
             pos += bs;
         }
         const size_t nin = pos - first;
         int k = 0;
         for (size_t off = 0; off < nin + 64; off += piece_cap, k ^= 1) {
-            td_handle::ZPiece &zp = h->zpiece[k];
-            if (zp.busy) { HIPCHK(hipEventSynchronize(zp.sent)); zp.busy = false; }
+            td_handle::ZPiece &zp = h->bgzf->piece[k];
+            if (zp.busy) { TD_HIPCHK(hipEventSynchronize(zp.sent.e)); zp.busy = false; }
             const size_t want = std::min(piece_cap, nin + 64 - off), have = off < nin ? std::min(want, nin - off) : 0;
-            if (have) stage_parallel(have, [&](size_t o2, size_t len) { memcpy(zp.pin + o2, src.map + first + off + o2, len); return true; });
-            if (want > have) memset(zp.pin + have, 0, want - have);
-            { const int urc = upload(h, z.d_in + off, zp.pin, want); if (urc) return urc; }
-            HIPCHK(hipEventRecord(zp.sent, h->copy_stream));
+            if (have) stage_parallel(have, [&](size_t o2, size_t len) { memcpy(zp.pin.p + o2, src.map + first + off + o2, len); return true; });
+            if (want > have) memset(zp.pin.p + have, 0, want - have);
+            { const int urc = upload(h, z.d_in.p + off, zp.pin.p, want); if (urc) return urc; }
+            TD_HIPCHK(hipEventRecord(zp.sent.e, h->copy_stream.s));
             zp.busy = true;
         }
-        if (b.n) HIPCHK(hipMemcpyAsync(z.d_mem, z.pin_mem, (size_t)b.n * sizeof(tdinf::Member), hipMemcpyHostToDevice, h->copy_stream));
-        HIPCHK(hipEventRecord(z.copied, h->copy_stream));
+        if (b.n) TD_HIPCHK(hipMemcpyAsync(z.d_mem.p, z.pin_mem.p, (size_t)b.n * sizeof(tdinf::Member), hipMemcpyHostToDevice, h->copy_stream.s));
+        TD_HIPCHK(hipEventRecord(z.copied.e, h->copy_stream.s));
         return TD_OK;
     };
     Batch cur, nxt;
     int slot = 0;
     rc = prepare(0, cur); if (rc) return rc;
     while (cur.n) {
-        td_handle::ZSlot &z = h->zslot[slot];
+        td_handle::ZSlot &z = h->bgzf->slot[slot];
         if (out_pos + cur.out_total > capacity) return fail(TD_E_LIMIT, "destination too small for the inflated members");
-        HIPCHK(hipStreamWaitEvent(h->work_stream, z.copied, 0));
-        hipLaunchKernelGGL(tdinf::k_bgzf_inflate, dim3((cur.n + 63) / 64), dim3(64), 64 * tdinf::TABLE_U16 * 2 + 4096, h->work_stream,
-                           z.d_in, (uint8_t *)d_dst + out_pos, z.d_mem, cur.n, h->d_zscratch, z.d_status, h->d_crctab, (uint32_t)h->gpu_inflate_crc);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(z.pin_status, z.d_status, (size_t)cur.n * 4, hipMemcpyDeviceToHost, h->work_stream));
+        TD_HIPCHK(hipStreamWaitEvent(h->work_stream.s, z.copied.e, 0));
+        hipLaunchKernelGGL(tdinf::k_bgzf_inflate, dim3((cur.n + 63) / 64), dim3(64), 64 * tdinf::TABLE_U16 * 2 + 4096, h->work_stream.s,
+                           z.d_in.p, (uint8_t *)d_dst + out_pos, z.d_mem.p, cur.n, h->bgzf->d_scratch.p, z.d_status.p, h->d_crctab.p, (uint32_t)h->gpu_inflate_crc);
+        TD_HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipMemcpyAsync(z.pin_status.p, z.d_status.p, (size_t)cur.n * 4, hipMemcpyDeviceToHost, h->work_stream.s));
         // the next batch is read and sent while this one inflates
         rc = prepare(slot ^ 1, nxt); if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(h->work_stream));
+        TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
         for (uint32_t i = 0; i < cur.n; i++)
-            if (z.pin_status[i]) return fail(TD_E_IO, z.pin_status[i] == 100 ? "BGZF member fails its CRC-32" : "inflate error in a BGZF member");
+            if (z.pin_status.p[i]) return fail(TD_E_IO, z.pin_status.p[i] == 100 ? "BGZF member fails its CRC-32" : "inflate error in a BGZF member");
         out_pos += cur.out_total;
         cur = nxt; slot ^= 1;
     }
-    HIPCHK(hipStreamSynchronize(h->copy_stream));
-    for (auto &zp : h->zpiece) zp.busy = false;
+    TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
+    for (auto &zp : h->bgzf->piece) zp.busy = false;
     *nbytes_out = out_pos;
     return TD_OK;
 }
 
 int td_get_stats(td_handle *h, uint64_t stats[TD_STAT_NSTATS]) {
     if (!h || !stats) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipDeviceSynchronize());
     unsigned long long st[TD_STAT_NSTATS];
-    HIPCHK(hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
     for (int i = 0; i < TD_STAT_NSTATS; i++) stats[i] = st[i];
     return check_device_errors(h, st);
 }
@@ -2722,7 +2639,7 @@ int td_get_progress(td_handle *h, uint64_t *out, uint64_t cap, uint64_t *nwindow
     // shards hold reads of high ordinals only (windows the handle never touched read as zero)
     const uint64_t take = std::min<uint64_t>(cap, h->d_win.n);
     std::vector<unsigned long long> w(take);
-    if (take) HIPCHK(hipMemcpy(w.data(), h->d_win.p, take * 8, hipMemcpyDeviceToHost));
+    if (take) TD_HIPCHK(hipMemcpy(w.data(), h->d_win.p, take * 8, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < cap; i++) {
         const unsigned long long v = i < take ? w[i] : 0ull;
         out[2 * i] = v & 0xFFFFFFFFull; out[2 * i + 1] = v >> 32;
@@ -2747,11 +2664,11 @@ int td_get_counts(td_handle *h, uint64_t *out) {
     const size_t cells = (size_t)h->barnum * h->ntags;
     std::vector<uint32_t> tmp(cells);
     const uint32_t *src = h->bound_counts ? h->bound_counts : h->d_counts.p;
-    HIPCHK(hipMemcpy(tmp.data(), src, cells * 4, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(tmp.data(), src, cells * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < cells; i++) out[i] = (uint64_t)tmp[i] + (h->host_acc.size() == cells ? h->host_acc[i] : 0);
     if (h->used64 && h->d_counts64.p) {
         std::vector<unsigned long long> t64(cells);
-        HIPCHK(hipMemcpy(t64.data(), h->d_counts64.p, cells * 8, hipMemcpyDeviceToHost));
+        TD_HIPCHK(hipMemcpy(t64.data(), h->d_counts64.p, cells * 8, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < cells; i++) out[i] += t64[i];
     }
     return TD_OK;
@@ -2759,12 +2676,12 @@ int td_get_counts(td_handle *h, uint64_t *out) {
 
 int td_debug_counters(td_handle *h, uint64_t out[24]) {
     if (!h || !out) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, h->d_stats.p + 8, 24 * 8, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipMemcpy(out, h->d_stats.p + 8, 24 * 8, hipMemcpyDeviceToHost));
     if (h->d_nfix.p) {          // [12]: length of the fast path's fix-up queue in the last launch
         uint32_t nf = 0;
-        HIPCHK(hipMemcpy(&nf, h->d_nfix.p, 4, hipMemcpyDeviceToHost));
+        TD_HIPCHK(hipMemcpy(&nf, h->d_nfix.p, 4, hipMemcpyDeviceToHost));
         out[11] = nf;
     }
     return TD_OK;
@@ -2801,7 +2718,7 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
     else if (n == "md5_piece") { if (value < 0 || value % 64) return fail(TD_E_ARG, "md5_piece: a multiple of 64, or 0"); h->md5_piece = (uint64_t)value; }
     else if (n == "tagnet_max_compares") { if (value < 0) return fail(TD_E_ARG, "tagnet_max_compares: 0 or more"); h->tagnet_max_compares = (uint64_t)value; }
     else if (n == "gz_gpu_terr_kb") { if (value < 16 || value > 4096) return fail(TD_E_ARG, "gz_gpu_terr_kb: 16..4096"); h->gz_gpu_terr_kb = (uint32_t)value; }
-    else if (n == "gz_gpu_release") { h->gzgpu.release(); }
+    else if (n == "gz_gpu_release") { h->gzgpu.reset(new td_handle::GzGpu()); }
     else if (n == "gz_gpu_verify") h->gz_gpu_verify = value ? 1 : 0;
     else if (n == "gz_gpu_seg_kb") { if (value < 64 || value > (4 << 20)) return fail(TD_E_ARG, "gz_gpu_seg_kb: 64..4194304"); h->gz_gpu_seg_kb = (uint32_t)value; }
     else if (n == "gz_gpu_margin_kb") { if (value < 64 || value > (1 << 20)) return fail(TD_E_ARG, "gz_gpu_margin_kb: 64..1048576"); h->gz_gpu_margin_kb = (uint32_t)value; }
@@ -2830,12 +2747,12 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
 
 int td_kernel_time_ms(td_handle *h, double *ms, uint32_t *launches) {
     if (!h || !ms) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     double tot = 0;
     for (size_t i = 0; i < h->ev_used; i++) {
-        HIPCHK(hipEventSynchronize(h->ev_pool[i].second));
+        TD_HIPCHK(hipEventSynchronize(h->ev_pool[i].second.e));
         float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, h->ev_pool[i].first, h->ev_pool[i].second));
+        TD_HIPCHK(hipEventElapsedTime(&t, h->ev_pool[i].first.e, h->ev_pool[i].second.e));
         tot += t;
     }
     *ms = h->ev_used ? tot / (double)h->ev_used : 0.0;
@@ -2846,12 +2763,12 @@ int td_kernel_time_ms(td_handle *h, double *ms, uint32_t *launches) {
 
 int td_kernel_times_ms(td_handle *h, double *out, uint32_t capacity, uint32_t *launches) {
     if (!h || !out || !launches) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     uint32_t n = 0;
     for (size_t i = 0; i < h->ev_used && n < capacity; i++, n++) {
-        HIPCHK(hipEventSynchronize(h->ev_pool[i].second));
+        TD_HIPCHK(hipEventSynchronize(h->ev_pool[i].second.e));
         float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, h->ev_pool[i].first, h->ev_pool[i].second));
+        TD_HIPCHK(hipEventElapsedTime(&t, h->ev_pool[i].first.e, h->ev_pool[i].second.e));
         out[n] = t;
     }
     *launches = n;
@@ -2861,32 +2778,32 @@ int td_kernel_times_ms(td_handle *h, double *out, uint32_t capacity, uint32_t *l
 
 int td_dev_alloc(td_handle *h, uint64_t nbytes, void **out) {
     if (!h || !out) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMalloc(out, std::max<uint64_t>(nbytes, 16)));
+    TD_HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipMalloc(out, std::max<uint64_t>(nbytes, 16)));            // (the caller's from here: td_dev_free)
     return TD_OK;
 }
 int td_dev_free(td_handle *h, void *p) {
     if (!h) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    if (p) HIPCHK(hipFree(p));
+    TD_HIPCHK(hipSetDevice(h->device));
+    if (p) TD_HIPCHK(hipFree(p));
     return TD_OK;
 }
 int td_memcpy_h2d(td_handle *h, void *dst, const void *src, uint64_t n) {
     if (!h) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    if (n) HIPCHK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipSetDevice(h->device));
+    if (n) TD_HIPCHK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
     return TD_OK;
 }
 int td_memcpy_d2h(td_handle *h, void *dst, const void *src, uint64_t n) {
     if (!h) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    if (n) HIPCHK(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipSetDevice(h->device));
+    if (n) TD_HIPCHK(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
     return TD_OK;
 }
 int td_device_sync(td_handle *h) {
     if (!h) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipDeviceSynchronize());
     return TD_OK;
 }
 
@@ -2946,7 +2863,7 @@ extern "C" {
 int td_fold_rows(td_handle *h, const uint32_t *row_of_barcode, uint32_t n_dst_rows, void *d_dst, void *stream) {
     if (!h || !row_of_barcode || !d_dst) return fail(TD_E_ARG, "NULL argument");
     if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     if (h->used64) return fail(TD_E_STATE, "td_fold_rows folds the uint32 matrix; tassel_tagcount weights are 64-bit");
     bool flushed = false;                      // (a library of more than ~17 GB: part of its counts sits in the host accumulator)
     for (uint64_t v : h->host_acc) if (v) { flushed = true; break; }
@@ -2954,33 +2871,33 @@ int td_fold_rows(td_handle *h, const uint32_t *row_of_barcode, uint32_t n_dst_ro
         if (row_of_barcode[b] >= n_dst_rows) return fail(TD_E_ARG, "row_of_barcode entry beyond n_dst_rows");
     hipStream_t s = (hipStream_t)stream;
     // every launch enqueued through this handle first (they may be on its own streams), and what they flagged
-    HIPCHK(hipStreamSynchronize(h->work_stream));
-    HIPCHK(hipStreamSynchronize(h->copy_stream));
-    int rc = h->d_rowmap.ensure(h->barnum); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h->d_rowmap.p, row_of_barcode, (size_t)h->barnum * 4, hipMemcpyHostToDevice, s));
+    TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
+    TD_HIPCHK(hipStreamSynchronize(h->copy_stream.s));
+    TD_HIPCHK(h->d_rowmap.ensure(h->barnum));
+    TD_HIPCHK(hipMemcpyAsync(h->d_rowmap.p, row_of_barcode, (size_t)h->barnum * 4, hipMemcpyHostToDevice, s));
     const uint32_t *src = h->bound_counts ? h->bound_counts : h->d_counts.p;
     const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((h->ntags + 255) / 256, 64));
     hipLaunchKernelGGL(k_fold_rows, dim3(gx, h->barnum), dim3(256), 0, s, src, h->barnum, h->ntags, h->d_rowmap.p, (uint32_t *)d_dst);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipStreamSynchronize(s));
     if (flushed) {
         // the flushed part goes the same way: its low 32 bits (the destination's cells are uint32) through the same kernel
         const size_t cells = (size_t)h->barnum * h->ntags;
         std::vector<uint32_t> low(cells);
         for (size_t i = 0; i < cells; i++) low[i] = (uint32_t)h->host_acc[i];
         DevBuf<uint32_t> d_low;
-        rc = d_low.ensure(cells); if (rc) return rc;
+        TD_HIPCHK(d_low.alloc(cells));
         hipError_t e = hipMemcpy(d_low.p, low.data(), cells * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_fold_rows, dim3(gx, h->barnum), dim3(256), 0, s, d_low.p, h->barnum, h->ntags, h->d_rowmap.p, (uint32_t *)d_dst);
             e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(s);
         }
-        d_low.release();
+        d_low.reset();
         if (e != hipSuccess) return fail(TD_E_HIP, std::string("td_fold_rows (flushed part): ") + hipGetErrorString(e));
     }
     unsigned long long st[TD_STAT_NSTATS];
-    HIPCHK(hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
     return check_device_errors(h, st);
 }
 
@@ -3010,17 +2927,16 @@ __global__ void k_synth_expected(td_synth_params P, uint64_t first_read, uint64_
 extern "C" {
 
 // the generator's optional draw tables (td_synth_spec.h "skew"): host thresholds -> device copies, pointers swapped in P
-static int synth_upload_cdfs(td_synth_params &P, uint64_t *&d_tag_cdf, uint64_t *&d_bar_cdf) {
-    d_tag_cdf = d_bar_cdf = nullptr;
+static int synth_upload_cdfs(td_synth_params &P, DevBuf<uint64_t> &d_tag_cdf, DevBuf<uint64_t> &d_bar_cdf) {
     if (P.tag_cdf) {
-        HIPCHK(hipMalloc((void **)&d_tag_cdf, (size_t)P.ntags * 8));
-        HIPCHK(hipMemcpy(d_tag_cdf, P.tag_cdf, (size_t)P.ntags * 8, hipMemcpyHostToDevice));
-        P.tag_cdf = d_tag_cdf;
+        TD_HIPCHK(d_tag_cdf.alloc(P.ntags));
+        TD_HIPCHK(hipMemcpy(d_tag_cdf.p, P.tag_cdf, (size_t)P.ntags * 8, hipMemcpyHostToDevice));
+        P.tag_cdf = d_tag_cdf.p;
     }
     if (P.bar_cdf) {
-        HIPCHK(hipMalloc((void **)&d_bar_cdf, (size_t)P.nbar * 8));
-        HIPCHK(hipMemcpy(d_bar_cdf, P.bar_cdf, (size_t)P.nbar * 8, hipMemcpyHostToDevice));
-        P.bar_cdf = d_bar_cdf;
+        TD_HIPCHK(d_bar_cdf.alloc(P.nbar));
+        TD_HIPCHK(hipMemcpy(d_bar_cdf.p, P.bar_cdf, (size_t)P.nbar * 8, hipMemcpyHostToDevice));
+        P.bar_cdf = d_bar_cdf.p;
     }
     return TD_OK;
 }
@@ -3029,53 +2945,47 @@ int td_synth_fill_device(td_handle *h, const void *params, uint64_t first_read, 
                          const char *bar_tab, const uint8_t *bar_len, const char *cut_tab,
                          const char *tag_tab, const uint16_t *tag_len, void *d_out, void *stream) {
     if (!h || !params || !d_out) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     td_synth_params P = *(const td_synth_params *)params;
     if (P.adapter_len > TD_SYNTH_ADAPTER_MAX) return fail(TD_E_ARG, "adapter_len beyond TD_SYNTH_ADAPTER_MAX");
     hipStream_t s = (hipStream_t)stream;
-    char *d_bar = nullptr, *d_cut = nullptr, *d_tag = nullptr; uint8_t *d_bl = nullptr; uint16_t *d_tl = nullptr;
-    uint64_t *d_tc = nullptr, *d_bc = nullptr;
+    DevBuf<char> d_bar, d_cut, d_tag; DevBuf<uint8_t> d_bl; DevBuf<uint16_t> d_tl;
+    DevBuf<uint64_t> d_tc, d_bc;
     { int rc = synth_upload_cdfs(P, d_tc, d_bc); if (rc) return rc; }
-    HIPCHK(hipMalloc((void **)&d_bar, (size_t)P.nbar * TD_SYNTH_BAR_STRIDE));
-    HIPCHK(hipMalloc((void **)&d_bl, P.nbar));
-    HIPCHK(hipMalloc((void **)&d_cut, (size_t)P.ncut * TD_SYNTH_CUT_STRIDE));
-    HIPCHK(hipMalloc((void **)&d_tag, (size_t)P.ntags * P.tag_stride));
-    HIPCHK(hipMalloc((void **)&d_tl, (size_t)P.ntags * 2));
-    HIPCHK(hipMemcpy(d_bar, bar_tab, (size_t)P.nbar * TD_SYNTH_BAR_STRIDE, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_bl, bar_len, P.nbar, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_cut, cut_tab, (size_t)P.ncut * TD_SYNTH_CUT_STRIDE, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_tag, tag_tab, (size_t)P.ntags * P.tag_stride, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_tl, tag_len, (size_t)P.ntags * 2, hipMemcpyHostToDevice));
+    TD_HIPCHK(d_bar.alloc((size_t)P.nbar * TD_SYNTH_BAR_STRIDE));
+    TD_HIPCHK(d_bl.alloc(P.nbar));
+    TD_HIPCHK(d_cut.alloc((size_t)P.ncut * TD_SYNTH_CUT_STRIDE));
+    TD_HIPCHK(d_tag.alloc((size_t)P.ntags * P.tag_stride));
+    TD_HIPCHK(d_tl.alloc(P.ntags));
+    TD_HIPCHK(hipMemcpy(d_bar.p, bar_tab, (size_t)P.nbar * TD_SYNTH_BAR_STRIDE, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(d_bl.p, bar_len, P.nbar, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(d_cut.p, cut_tab, (size_t)P.ncut * TD_SYNTH_CUT_STRIDE, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(d_tag.p, tag_tab, (size_t)P.ntags * P.tag_stride, hipMemcpyHostToDevice));
+    TD_HIPCHK(hipMemcpy(d_tl.p, tag_len, (size_t)P.ntags * 2, hipMemcpyHostToDevice));
     const uint32_t grid = (uint32_t)std::min<uint64_t>((nreads + 255) / 256, (uint64_t)h->num_cu * 32);
-    if (nreads) hipLaunchKernelGGL(k_synth, dim3(grid), dim3(256), 0, s, P, first_read, nreads, d_bar, d_bl, d_cut, d_tag, d_tl, (uint8_t *)d_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    (void)hipFree(d_bar); (void)hipFree(d_bl); (void)hipFree(d_cut); (void)hipFree(d_tag); (void)hipFree(d_tl);
-    if (d_tc) (void)hipFree(d_tc);
-    if (d_bc) (void)hipFree(d_bc);
+    if (nreads) hipLaunchKernelGGL(k_synth, dim3(grid), dim3(256), 0, s, P, first_read, nreads, d_bar.p, d_bl.p, d_cut.p, d_tag.p, d_tl.p, (uint8_t *)d_out);
+    TD_HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipStreamSynchronize(s));
     return TD_OK;
 }
 
 int td_synth_expected_device(td_handle *h, const void *params, uint64_t first_read, uint64_t nreads,
                              uint32_t *d_counts, uint64_t *hits_out, void *stream) {
     if (!h || !params || !d_counts) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     td_synth_params P = *(const td_synth_params *)params;
     hipStream_t s = (hipStream_t)stream;
-    uint64_t *d_tc = nullptr, *d_bc = nullptr;
+    DevBuf<uint64_t> d_tc, d_bc;
     { int rc = synth_upload_cdfs(P, d_tc, d_bc); if (rc) return rc; }
-    unsigned long long *d_hits = nullptr;
-    HIPCHK(hipMalloc((void **)&d_hits, 8));
-    HIPCHK(hipMemsetAsync(d_hits, 0, 8, s));
+    DevBuf<unsigned long long> d_hits;
+    TD_HIPCHK(d_hits.alloc(1));
+    TD_HIPCHK(hipMemsetAsync(d_hits.p, 0, 8, s));
     const uint32_t grid = (uint32_t)std::min<uint64_t>((nreads + 255) / 256, (uint64_t)h->num_cu * 32);
-    if (nreads) hipLaunchKernelGGL(k_synth_expected, dim3(grid), dim3(256), 0, s, P, first_read, nreads, d_counts, d_hits);
-    HIPCHK(hipGetLastError());
+    if (nreads) hipLaunchKernelGGL(k_synth_expected, dim3(grid), dim3(256), 0, s, P, first_read, nreads, d_counts, d_hits.p);
+    TD_HIPCHK(hipGetLastError());
     unsigned long long v = 0;
-    HIPCHK(hipMemcpyAsync(&v, d_hits, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    (void)hipFree(d_hits);
-    if (d_tc) (void)hipFree(d_tc);
-    if (d_bc) (void)hipFree(d_bc);
+    TD_HIPCHK(hipMemcpyAsync(&v, d_hits.p, 8, hipMemcpyDeviceToHost, s));
+    TD_HIPCHK(hipStreamSynchronize(s));
     if (hits_out) *hits_out = v;
     return TD_OK;
 }
@@ -3102,8 +3012,8 @@ int launch_split_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, hipS
     const uint64_t tile = use_split2(h) ? 24 * 1024 : 16 * 1024;
     const uint64_t nt = (nbytes + tile - 1) / tile;
     if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    int rc = h->d_tilecounts.ensure(nt); if (rc) return rc;
-    rc = h->d_state.ensure(nt); if (rc) return rc;
+    TD_HIPCHK(h->d_tilecounts.ensure(nt));
+    TD_HIPCHK(h->d_state.ensure(nt));
     const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
     // `counted`: the count pass just enqueued on this stream ran over the same bytes in tiles of this size and left
     // every tile's terminator count in d_tileinfo
@@ -3112,7 +3022,7 @@ int launch_split_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, hipS
     else if (use_split2(h)) hipLaunchKernelGGL((tdk::k_count_lines<6>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
     else hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
     hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, h->d_cursor.p);
-    HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     return TD_OK;
 }
 
@@ -3134,12 +3044,12 @@ int launch_split(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
     sp.out = d_out; sp.stats = h->d_stats.p; sp.dbg = (uint32_t)h->debug_ablate;
     if (two) {
         hipLaunchKernelGGL((tdk::k_split2<6>), dim3(g), dim3(tdk::FBLOCK), lds_bytes_split2(h), s, sp);
-        HIPCHK(hipGetLastError());
+        TD_HIPCHK(hipGetLastError());
         return TD_OK;
     }
     const size_t lds = (size_t)4 * tdk::BLOCK * 2 + 64 + h->sp_bblob_bytes;
     hipLaunchKernelGGL((tdk::k_split<4>), dim3(g), dim3(tdk::BLOCK), lds, s, sp);
-    HIPCHK(hipGetLastError());
+    TD_HIPCHK(hipGetLastError());
     return TD_OK;
 }
 
@@ -3377,7 +3287,7 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
                     const char *fullsite0, const char *fullsite1, const uint32_t *ent_begin,
                     const char *const *ent_seq, const int32_t *ent_slice, uint32_t nent) {
     if (!h || !barcodes || !cutsite || !fullsite0 || !fullsite1 || !ent_begin) return fail(TD_E_ARG, "NULL argument");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     h->have_splitter = false;
     if (nbar == 0) return fail(TD_E_EMPTY, "empty barcode list");
     const std::string cs(cutsite);
@@ -3455,10 +3365,10 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
             }
         }
     }
-    rc = h->d_sp_bblob.ensure(blob.size() / 4); if (rc) return rc;
-    HIPCHK(hipMemcpy(h->d_sp_bblob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    rc = h->d_sp_ent_begin.ensure(nbar + 1); if (rc) return rc;
-    HIPCHK(hipMemcpy(h->d_sp_ent_begin.p, ent_begin, (size_t)(nbar + 1) * 4, hipMemcpyHostToDevice));
+    TD_HIPCHK(h->d_sp_bblob.ensure(blob.size() / 4));
+    TD_HIPCHK(hipMemcpy(h->d_sp_bblob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    TD_HIPCHK(h->d_sp_ent_begin.ensure(nbar + 1));
+    TD_HIPCHK(hipMemcpy(h->d_sp_ent_begin.p, ent_begin, (size_t)(nbar + 1) * 4, hipMemcpyHostToDevice));
     {   // k_split2's view of the same entries: per barcode 16 groups by the codes of the LAST TWO characters (a one-character
         // entry sits in all four groups of its character), every group padded to the same capacity (empty entries: len 0),
         // so a read finds its group by address alone -- the loads can be issued before the group is needed -- and looks
@@ -3483,8 +3393,8 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
         std::vector<tdk::SplitEntry> e16((size_t)nbar * 16 * cap, tdk::SplitEntry{0u, 0u, 999, 0u});
         for (size_t g = 0; g < grp.size(); g++) std::copy(grp[g].begin(), grp[g].end(), e16.begin() + g * cap);
         h->sp_gcap = (uint32_t)cap;
-        rc = h->d_sp_entries16.ensure(std::max<size_t>(1, e16.size())); if (rc) return rc;
-        HIPCHK(hipMemcpy(h->d_sp_entries16.p, e16.data(), e16.size() * sizeof(tdk::SplitEntry), hipMemcpyHostToDevice));
+        TD_HIPCHK(h->d_sp_entries16.ensure(std::max<size_t>(1, e16.size())));
+        TD_HIPCHK(hipMemcpy(h->d_sp_entries16.p, e16.data(), e16.size() * sizeof(tdk::SplitEntry), hipMemcpyHostToDevice));
     }
     {   // k_split2's view (round 3): per barcode 64 groups by the codes of the LAST THREE characters (an entry shorter than
         // that sits in every group of its characters), eight compact entries of 8 bytes per group -- ONE 64-byte fetch per
@@ -3531,20 +3441,20 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
         }
         if (h->sp_compact) {
             pool2.resize(pool2.size() + 128, 0);                     // (the compare reads eight bytes at a time)
-            rc = h->d_sp_e8.ensure(e8.size()); if (rc) return rc;
-            HIPCHK(hipMemcpy(h->d_sp_e8.p, e8.data(), e8.size() * sizeof(uint2), hipMemcpyHostToDevice));
-            rc = h->d_sp_pool2.ensure(pool2.size()); if (rc) return rc;
-            HIPCHK(hipMemcpy(h->d_sp_pool2.p, pool2.data(), pool2.size(), hipMemcpyHostToDevice));
+            TD_HIPCHK(h->d_sp_e8.ensure(e8.size()));
+            TD_HIPCHK(hipMemcpy(h->d_sp_e8.p, e8.data(), e8.size() * sizeof(uint2), hipMemcpyHostToDevice));
+            TD_HIPCHK(h->d_sp_pool2.ensure(pool2.size()));
+            TD_HIPCHK(hipMemcpy(h->d_sp_pool2.p, pool2.data(), pool2.size(), hipMemcpyHostToDevice));
         }
     }
-    rc = h->d_sp_ent_group.ensure((size_t)nbar * 4); if (rc) return rc;
-    HIPCHK(hipMemcpy(h->d_sp_ent_group.p, groups.data(), groups.size() * 4, hipMemcpyHostToDevice));
-    rc = h->d_sp_entries.ensure(std::max<size_t>(1, nent)); if (rc) return rc;
-    if (nent) HIPCHK(hipMemcpy(h->d_sp_entries.p, ents.data(), (size_t)nent * sizeof(tdk::SplitEntry), hipMemcpyHostToDevice));
+    TD_HIPCHK(h->d_sp_ent_group.ensure((size_t)nbar * 4));
+    TD_HIPCHK(hipMemcpy(h->d_sp_ent_group.p, groups.data(), groups.size() * 4, hipMemcpyHostToDevice));
+    TD_HIPCHK(h->d_sp_entries.ensure(std::max<size_t>(1, nent)));
+    if (nent) TD_HIPCHK(hipMemcpy(h->d_sp_entries.p, ents.data(), (size_t)nent * sizeof(tdk::SplitEntry), hipMemcpyHostToDevice));
     pool.insert(pool.end(), 8, 0);                        // (k_split2 compares eight bytes at a time: may read past the last string)
-    rc = h->d_sp_pool.ensure(std::max<size_t>(1, pool.size())); if (rc) return rc;
-    if (!pool.empty()) HIPCHK(hipMemcpy(h->d_sp_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice));
-    rc = h->d_cursor.ensure(2); if (rc) return rc;
+    TD_HIPCHK(h->d_sp_pool.ensure(std::max<size_t>(1, pool.size())));
+    if (!pool.empty()) TD_HIPCHK(hipMemcpy(h->d_sp_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice));
+    TD_HIPCHK(h->d_cursor.ensure(2));
     h->have_splitter = true;
     return TD_OK;
 }
@@ -3563,20 +3473,20 @@ static int split_device_impl(td_handle *h, const void *d_fastq, uint64_t nbytes,
     if (!h || !d_out) return fail(TD_E_ARG, "NULL argument");
     if (!h->have_splitter) return fail(TD_E_STATE, "td_set_splitter has not been called");
     if (((uintptr_t)d_fastq & 15) != 0) return fail(TD_E_ARG, "device FASTQ pointer must be 16-byte aligned");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     if (n_terminators) *n_terminators = 0;
     if (nbytes == 0) return TD_OK;
     hipStream_t s = (hipStream_t)stream;
     int rc = launch_split_prefix(h, d_fastq, nbytes, s, counted); if (rc) return rc;
     unsigned long long v = 0;
-    HIPCHK(hipMemcpyAsync(&v, h->d_cursor.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    TD_HIPCHK(hipMemcpyAsync(&v, h->d_cursor.p, 8, hipMemcpyDeviceToHost, s));
+    TD_HIPCHK(hipStreamSynchronize(s));
     if (n_terminators) *n_terminators = v;
     if (out_capacity < max_seq_lines(v + 1)) return fail(TD_E_ARG, "output must hold (terminators + 1) / 4 + 2 results");
     rc = launch_split(h, d_fastq, nbytes, first_line, (int2 *)d_out, s); if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s));
+    TD_HIPCHK(hipStreamSynchronize(s));
     unsigned long long st[TD_STAT_NSTATS];
-    HIPCHK(hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    TD_HIPCHK(hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
     return check_device_errors(h, st);
 }
 
@@ -3587,7 +3497,7 @@ int td_count_and_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes
     // in the Infinity Cache for buffers that fit it); one synchronisation at the end
     if (!h || !d_out) return fail(TD_E_ARG, "NULL argument");
     if (!h->have_splitter) return fail(TD_E_STATE, "td_set_splitter has not been called");
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     int rc = launch_count(h, d_fastq, nbytes, first_line, max_reads, 0, (hipStream_t)stream);
     if (rc) return rc;
     return split_device_impl(h, d_fastq, nbytes, first_line, d_out, out_capacity, stream, n_terminators, true);
@@ -3614,10 +3524,11 @@ int td_split_file(td_handle *h, const char *in_path, const char *const *out_path
 }
 static int split_file_impl(td_handle *h, const char *in_path, const char *const *out_paths, uint64_t max_reads, uint64_t stats[3],
                            bool by_reference_rules, bool *gz_refused) {
-    HIPCHK(hipSetDevice(h->device));
+    TD_HIPCHK(hipSetDevice(h->device));
     const size_t len = strlen(in_path);
     const bool gz = len >= 2 && (in_path[len - 2] == 'g' || in_path[len - 2] == 'G') && (in_path[len - 1] == 'z' || in_path[len - 1] == 'Z');
     tdhost::GzSource zsrc; FILE *pf = nullptr;
+    struct FileEnd { FILE *&f; ~FileEnd() { if (f) fclose(f); } } pf_end{pf};
     std::unique_ptr<MappedFile> rules_map;
     std::unique_ptr<tdhost::PyGzipReader> rules;
     bool rules_through = false;
@@ -3689,28 +3600,21 @@ static int split_file_impl(td_handle *h, const char *in_path, const char *const 
         std::unique_lock<std::mutex> g(job.mu);
         job.cv.wait(g, [&]() { return job.finished == nthr - 1; });
     };
-    int rc = TD_OK;
     const size_t cap = (size_t)32 << 20;
     // two slots: the GPU decides piece k + 1 while the host writes piece k
     using Slot = td_handle::SplitSlot;
-    Slot (&slot)[2] = h->sp_slot;                      // (allocated on first use, freed by td_destroy)
-    auto cleanup = [&]() {
-        zsrc.close();
-        if (pf) fclose(pf);
-        pf = nullptr;
-    };
-#define SPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(TD_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
+    Slot (&slot)[2] = h->sp_slot;                      // (allocated on first use, kept on the handle)
     for (auto &sl : slot) {
         sl.pending = false; sl.n = 0;
-        if (!sl.pin) SPCHK(hipHostMalloc((void **)&sl.pin, cap, hipHostMallocDefault));
-        if (!sl.dev) SPCHK(hipMalloc((void **)&sl.dev, cap));
-        if (!sl.res_dev) SPCHK(hipMalloc((void **)&sl.res_dev, max_seq_lines(cap) * sizeof(int2)));          // (a line holds at least its terminator)
-        if (!sl.res_pin) SPCHK(hipHostMalloc((void **)&sl.res_pin, max_seq_lines(cap) * sizeof(int2), hipHostMallocDefault));
-        if (!sl.done) SPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        if (!sl.pin.p) TD_HIPCHK(sl.pin.alloc(cap));
+        if (!sl.dev.p) TD_HIPCHK(sl.dev.alloc(cap));
+        if (!sl.res_dev.p) TD_HIPCHK(sl.res_dev.alloc(max_seq_lines(cap)));          // (a line holds at least its terminator)
+        if (!sl.res_pin.p) TD_HIPCHK(sl.res_pin.alloc(max_seq_lines(cap)));
+        if (!sl.done.e) TD_HIPCHK(sl.done.create(hipEventDisableTiming));
     }
     for (uint32_t b = 0; b < h->sp_barcodes.size(); b++) {
         FILE *f = fopen(out_paths[b], "wb");
-        if (!f) { cleanup(); return fail(TD_E_IO, std::string("cannot open ") + out_paths[b] + " for writing"); }
+        if (!f) return fail(TD_E_IO, std::string("cannot open ") + out_paths[b] + " for writing");
         setvbuf(f, nullptr, _IONBF, 0);          // (SplitWriter keeps its own buffer per file)
         files.out.push_back(f);
     }
@@ -3723,95 +3627,87 @@ static int split_file_impl(td_handle *h, const char *in_path, const char *const 
     const bool timing = getenv("TAGDIG_SPLIT_TIMING") != nullptr;
     double t_read = 0, t_wait = 0, t_write = 0;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    auto hipfail = [&](const char *what, hipError_t e) { return fail(TD_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    unsigned long long *terms_pin = nullptr;          // the piece's terminator count, read back before k_split
-    {
-        hipError_t e = hipHostMalloc((void **)&terms_pin, 16, hipHostMallocDefault);
-        if (e != hipSuccess) { cleanup(); return hipfail("hipHostMalloc", e); }
-    }
+    PinBuf<unsigned long long> terms_pin;             // the piece's terminator count, read back before k_split
+    TD_HIPCHK(terms_pin.alloc(2));
     // wait for the slot's decisions, then write its records (the host's share of the loop)
     auto write_out = [&](Slot &sl) -> int {
         if (!sl.pending) return TD_OK;
         const double t0 = now();
-        hipError_t e = hipEventSynchronize(sl.done);
-        if (e != hipSuccess) return hipfail("hipEventSynchronize", e);
+        TD_HIPCHK(hipEventSynchronize(sl.done.e));
         sl.pending = false;
         const double t1 = now();
-        if (!w.stop) write_piece(sl.pin, sl.n, sl.res_pin);
+        if (!w.stop) write_piece(sl.pin.p, sl.n, sl.res_pin.p);
         t_wait += t1 - t0; t_write += now() - t1;
+        return TD_OK;
+    };
+    // a piece's first steps on the GPU: its copy, its line prefix, the terminator count on its way back
+    auto start_piece = [&](Slot &sl, size_t cut) -> int {
+        TD_HIPCHK(hipMemcpyAsync(sl.dev.p, sl.pin.p, cut, hipMemcpyHostToDevice, h->work_stream.s));
+        const int prc = launch_split_prefix(h, sl.dev.p, cut, h->work_stream.s);
+        if (prc) return prc;
+        TD_HIPCHK(hipMemcpyAsync(terms_pin.p, h->d_cursor.p, 8, hipMemcpyDeviceToHost, h->work_stream.s));
         return TD_OK;
     };
     // Per piece: read it and start its copy and its line prefix on the GPU while the writer threads
     // write the PREVIOUS piece's records (that also tells the exact line index this piece starts at),
     // then have the GPU decide this piece's reads (a millisecond) and fetch the decisions.
-    int cur = 0;
-    Slot *prev = nullptr;
-    while (!eof && !w.stop && !rc) {
-        Slot &sl = slot[cur];
-        int wrc = TD_OK;
-        std::thread wt;
-        if (prev) {
-            Slot *pv = prev;
-            wt = std::thread([&, pv]() { (void)hipSetDevice(h->device); wrc = write_out(*pv); });
-        }
-        prev = nullptr;
-        const double tr0 = now();
-        size_t have = carry.size();
-        if (have) memcpy(sl.pin, carry.data(), have);
-        carry.clear();
-        while (have < cap) {
-            long got = reader(sl.pin + have, cap - have);
-            if (got < 0) { rc = TD_E_IO; break; }
-            if (got == 0) { eof = true; break; }
-            have += (size_t)got;
-        }
-        size_t cut = have;
-        if (!rc && !eof) {
-            cut = cut_at_line_end(sl.pin, have);
-            if (cut == 0) rc = TD_E_LIMIT;
-            else carry.assign(sl.pin + cut, sl.pin + have);
-        }
-        sl.n = cut;
-        t_read += now() - tr0;
-        hipError_t e = hipSuccess;
-        const char *what = "";
-        if (!rc && cut) {
-            e = hipMemcpyAsync(sl.dev, sl.pin, cut, hipMemcpyHostToDevice, h->work_stream); what = "hipMemcpyAsync";
-            if (e == hipSuccess) {
-                const int prc = launch_split_prefix(h, sl.dev, cut, h->work_stream);
-                if (prc) rc = prc;
-                else e = hipMemcpyAsync(terms_pin, h->d_cursor.p, 8, hipMemcpyDeviceToHost, h->work_stream);
+    auto pieces = [&]() -> int {
+        int cur = 0;
+        Slot *prev = nullptr;
+        while (!eof && !w.stop) {
+            Slot &sl = slot[cur];
+            int wrc = TD_OK;
+            std::thread wt;
+            if (prev) {
+                Slot *pv = prev;
+                wt = std::thread([&, pv]() { (void)hipSetDevice(h->device); wrc = write_out(*pv); });
             }
+            prev = nullptr;
+            const double tr0 = now();
+            int rc = TD_OK;
+            size_t have = carry.size();
+            if (have) memcpy(sl.pin.p, carry.data(), have);
+            carry.clear();
+            while (have < cap) {
+                long got = reader(sl.pin.p + have, cap - have);
+                if (got < 0) { rc = TD_E_IO; break; }
+                if (got == 0) { eof = true; break; }
+                have += (size_t)got;
+            }
+            size_t cut = have;
+            if (!rc && !eof) {
+                cut = cut_at_line_end(sl.pin.p, have);
+                if (cut == 0) rc = TD_E_LIMIT;
+                else carry.assign(sl.pin.p + cut, sl.pin.p + have);
+            }
+            sl.n = cut;
+            t_read += now() - tr0;
+            const int src = !rc && cut ? start_piece(sl, cut) : TD_OK;
+            if (wt.joinable()) wt.join();
+            if (rc == TD_E_IO) return fail(TD_E_IO, "read error while streaming FASTQ");
+            if (rc == TD_E_LIMIT) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
+            if (src) return src;
+            if (wrc) return wrc;
+            if (cut && !w.stop) {
+                const double t0 = now();
+                TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));            // (copy + prefix ran under the writing)
+                t_wait += now() - t0;
+                const uint64_t lines = *terms_pin.p + 1;                      // (+1: an unterminated last line, at most)
+                rc = launch_split(h, sl.dev.p, cut, w.lineindex, sl.res_dev.p, h->work_stream.s); if (rc) return rc;
+                TD_HIPCHK(hipMemcpyAsync(sl.res_pin.p, sl.res_dev.p, max_seq_lines(lines) * sizeof(int2), hipMemcpyDeviceToHost, h->work_stream.s));
+                (void)hipEventRecord(sl.done.e, h->work_stream.s);
+                sl.pending = true;
+                prev = &sl;
+            }
+            cur ^= 1;
         }
-        if (wt.joinable()) wt.join();
-        if (rc == TD_E_IO) { rc = fail(TD_E_IO, "read error while streaming FASTQ"); break; }
-        if (rc == TD_E_LIMIT) { rc = fail(TD_E_LIMIT, "a single line exceeds the staging buffer"); break; }
-        if (rc) break;
-        if (e != hipSuccess) { rc = hipfail(what, e); break; }
-        if (wrc) { rc = wrc; break; }
-        if (cut && !w.stop) {
-            const double t0 = now();
-            e = hipStreamSynchronize(h->work_stream);                     // (copy + prefix ran under the writing)
-            if (e != hipSuccess) { rc = hipfail("hipStreamSynchronize", e); break; }
-            t_wait += now() - t0;
-            const uint64_t lines = *terms_pin + 1;                        // (+1: an unterminated last line, at most)
-            rc = launch_split(h, sl.dev, cut, w.lineindex, sl.res_dev, h->work_stream); if (rc) break;
-            e = hipMemcpyAsync(sl.res_pin, sl.res_dev, max_seq_lines(lines) * sizeof(int2), hipMemcpyDeviceToHost, h->work_stream);
-            if (e != hipSuccess) { rc = hipfail("hipMemcpyAsync", e); break; }
-            (void)hipEventRecord(sl.done, h->work_stream);
-            sl.pending = true;
-            prev = &sl;
-        }
-        cur ^= 1;
-    }
-    if (!rc && prev) rc = write_out(*prev);
-    for (auto &sl : slot) if (sl.pending) { (void)hipEventSynchronize(sl.done); sl.pending = false; }
-    if (terms_pin) (void)hipHostFree(terms_pin);
-    (void)hipStreamSynchronize(h->work_stream);
+        return prev ? write_out(*prev) : TD_OK;
+    };
+    int rc = pieces();
+    for (auto &sl : slot) if (sl.pending) { (void)hipEventSynchronize(sl.done.e); sl.pending = false; }
+    (void)hipStreamSynchronize(h->work_stream.s);
     unsigned long long st[TD_STAT_NSTATS];
     const bool have_st = hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess;
-    cleanup();
-#undef SPCHK
     bool io_error = false;
     uint64_t n_barcut = 0, n_clipped = 0;
     for (size_t k = 0; k < files.out.size(); k++) if (!w.flush(k)) io_error = true;

@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -26,8 +27,8 @@
 struct td_tagset {
     int device;
     uint32_t n, W;
-    uint64_t *key;     // W * n words, sorted order, word-major
-    uint16_t *len;     // n, sorted order
+    tdi::DevBuf<uint64_t> key;     // W * n words, sorted order, word-major
+    tdi::DevBuf<uint16_t> len;     // n, sorted order
 };
 
 namespace {
@@ -329,8 +330,9 @@ extern "C" int td_tagset_load(td_handle *h, const char *seqs, const uint64_t *of
         TD_HIPCHK(hist.alloc(256ull * tdrs::rs_blocks(n)));
         TD_HIPCHK(tdrs::rs_sort(key.p, len.p, n, W, &perm0.p, &perm1.p, differ.p, hist.p, &npass));
     }
-    tdi::DevBuf<uint64_t> skey;                    // the sorted set: the caller's once everything has succeeded
-    tdi::DevBuf<uint16_t> slen;
+    std::unique_ptr<td_tagset> set(new td_tagset{td_handle_device(h), n, W, {}, {}});      // the sorted set: the caller's once everything has succeeded
+    tdi::DevBuf<uint64_t> &skey = set->key;
+    tdi::DevBuf<uint16_t> &slen = set->len;
     const hipError_t e1 = skey.alloc((size_t)W * n), e2 = slen.alloc(n);
     if (e1 != hipSuccess || e2 != hipSuccess) return td_fail_internal(TD_E_HIP, "hipMalloc of the sorted set failed");
     if (n) hipLaunchKernelGGL(k_rs_gather, dim3((n + 255) / 256), dim3(256), 0, 0, key.p, len.p, perm0.p, n, W, skey.p, slen.p);
@@ -344,7 +346,7 @@ extern "C" int td_tagset_load(td_handle *h, const char *seqs, const uint64_t *of
         ms[1] = ev.elapsed(2, 3);
     }
     if (passes) *passes = npass;
-    *out = new td_tagset{td_handle_device(h), n, W, skey.release(), slen.release()};
+    *out = set.release();
     return TD_OK;
 }
 
@@ -352,8 +354,6 @@ extern "C" int td_tagset_free(td_handle *h, td_tagset *s) {
     (void)h;
     if (!s) return TD_OK;
     (void)hipSetDevice(s->device);
-    if (s->key) (void)hipFree(s->key);
-    if (s->len) (void)hipFree(s->len);
     delete s;
     return TD_OK;
 }
@@ -380,7 +380,7 @@ extern "C" int td_tagset_lookup(td_handle *h, const td_tagset *s, const char *se
     if ((rc = ts_bad(bad))) return rc;
     TD_HIPCHK(dout.alloc(nq));
     TD_HIPCHK(hipEventRecord(ev.e[0], 0));
-    hipLaunchKernelGGL(k_tag_lookup, dim3((nq + 255) / 256), dim3(256), 0, 0, s->key, s->len, s->n, s->W, key.p, len.p, nq, Wq,
+    hipLaunchKernelGGL(k_tag_lookup, dim3((nq + 255) / 256), dim3(256), 0, 0, s->key.p, s->len.p, s->n, s->W, key.p, len.p, nq, Wq,
                        allow_diff_lengths ? 1 : 0, dout.p);
     TD_HIPCHK(hipGetLastError());
     TD_HIPCHK(hipEventRecord(ev.e[1], 0));

@@ -1,14 +1,15 @@
 // What the library's translation units share on the host side and the C-ABI does not show ("The modules
 // beside tagdig.hip"): the hooks into the handle that tagdig.hip and census.hip define, the check macro for HIP calls,
-// and the owners of the device buffers, pinned buffers and events that an entry point holds while it runs.  Every
-// module beside tagdig.hip includes this header; tagdig.hip and census.hip include it too, so that a hook's definition
-// is checked against the declaration its callers see.
+// and the owners of the device buffers, pinned buffers, events and streams that the handle keeps or an entry point holds
+// while it runs (nothing else in the library frees one).  Every module beside tagdig.hip includes this header; tagdig.hip
+// and census.hip include it too, so that a hook's definition is checked against the declaration its callers see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <string>
+#include <utility>
 
 #include "../../include/tagdig.h"
 
@@ -59,13 +60,25 @@ namespace [[gnu::visibility("hidden")]] tdi {
 
 // max(n, 1) elements of device memory, freed with the object unless released
 template <typename T> struct DevBuf {
-    T *p = nullptr;
+    T *p = nullptr; size_t n = 0;                 // n: the elements asked for
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)); }
-    T *release() { T *q = p; p = nullptr; return q; }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t want) {               // (of an empty buffer)
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(want, 1) * sizeof(T));
+        if (e == hipSuccess) n = want; else p = nullptr;
+        return e;
+    }
+    // room for `want` elements: grows only, and what the buffer held is gone after a growth
+    hipError_t ensure(size_t want) {
+        if (want <= n && p) return hipSuccess;
+        reset();
+        return alloc(want);
+    }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }        // free now
+    T *release() { T *q = p; p = nullptr; n = 0; return q; }              // hand off: the caller frees
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
 };
 
 // the same in pinned host memory
@@ -74,8 +87,31 @@ template <typename T> struct PinBuf {
     PinBuf() = default;
     PinBuf(const PinBuf &) = delete;
     PinBuf &operator=(const PinBuf &) = delete;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t alloc(size_t n) { return hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault); }
+    ~PinBuf() { reset(); }
+    hipError_t alloc(size_t n, unsigned flags = hipHostMallocDefault) { return hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), flags); }
+    void reset() { if (p) (void)hipHostFree(p); p = nullptr; }
+};
+
+// one event, created with the flags its use needs; movable, for the handle's pool of timing events
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+};
+
+// a non-blocking stream; its work is waited for before it goes, so an owner declared behind the buffers its work uses
+// (and so destroyed before them) never lets one be freed under a running kernel or copy
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
 };
 
 // N events, destroyed with the object
