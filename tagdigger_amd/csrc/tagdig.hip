@@ -592,6 +592,25 @@ int launch_count(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
     return TD_OK;
 }
 
+// terminators before the end of every tile of tile_kb (16 | 24) KiB -> h->d_state (FLAG_INC | count; good until the handle's
+// next launch), their total -> *d_total (device; may be NULL); asynchronous on `s`.  `counted`: the count pass just enqueued
+// on `s` ran over the same bytes -- where it left every 24 KiB tile's count in d_tileinfo, k_info_counts takes them from there
+int line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, int tile_kb, hipStream_t s, unsigned long long *d_total, bool counted = false) {
+    const uint64_t tile = (uint64_t)tile_kb * 1024;
+    const uint64_t nt = (nbytes + tile - 1) / tile;
+    if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
+    TD_HIPCHK(h->d_tilecounts.ensure(nt));
+    TD_HIPCHK(h->d_state.ensure(nt));
+    const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
+    if (counted && tile_kb == 24 && h->last_fast_tile_kb == 24 && h->last_fast_ntiles == (uint32_t)nt)
+        hipLaunchKernelGGL(tdk::k_info_counts, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, s, h->d_tileinfo.p, (uint32_t)nt, h->d_tilecounts.p);
+    else if (tile_kb == 24) hipLaunchKernelGGL((tdk::k_count_lines<6>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
+    else hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
+    hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, d_total);
+    TD_HIPCHK(hipGetLastError());
+    return TD_OK;
+}
+
 int check_device_errors(td_handle *h, const unsigned long long *st) {
     unsigned long long e = st[tdk::ST_ERR];
     if (e & tdk::ERR_SPIN) return fail(TD_E_INTERNAL, "look-back wait timed out inside the count kernel");
@@ -662,10 +681,8 @@ __attribute__((visibility("hidden"))) int td_handle_device(const td_handle *h) {
 uint32_t td_last_bad_index(void) { return g_bad; }
 
 }  // extern "C"
-namespace { inline int stage_threads(); }
-// for csrc/md5.hip (hidden): the "md5_piece" option and the number of staging threads
+// for csrc/md5.hip (hidden): the "md5_piece" option (the number of staging threads: td_stage_thread_count, below)
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h) { return h->md5_piece; }
-extern "C" __attribute__((visibility("hidden"))) int td_stage_thread_count(void) { return stage_threads(); }
 // the "tagnet_max_compares" option (csrc/tagnet.hip), and the index td_last_bad_index reports
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_compares(const td_handle *h) { return h->tagnet_max_compares; }
 extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx) { g_bad = idx; }
@@ -702,20 +719,12 @@ extern "C" __attribute__((visibility("hidden"))) int td_barcut_blob(const char *
     *bytes = (uint32_t)blob.size();
     return TD_OK;
 }
-// terminators before the end of every 16 KiB tile (k_count_lines<4>; census.hip asserts that its tile is this one) of the buffer -> *prefix (FLAG_INC | count; the handle's scratch, good
-// until its next launch), their total -> *d_total; asynchronous on `s`
+// for census.hip and qc.hip (they assert that their tile is this one): the line prefix over 16 KiB tiles -> *prefix
 extern "C" __attribute__((visibility("hidden"))) int td_line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, void *s, const uint64_t **prefix,
                                                                     unsigned long long *d_total) {
-    const uint64_t nt = (nbytes + 16383) / 16384;
-    if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    TD_HIPCHK(h->d_tilecounts.ensure(nt));
-    TD_HIPCHK(h->d_state.ensure(nt));
-    const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
-    hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, (hipStream_t)s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
-    hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, (hipStream_t)s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, d_total);
-    TD_HIPCHK(hipGetLastError());
+    const int rc = line_prefix(h, d_fastq, nbytes, 16, (hipStream_t)s, d_total);
     *prefix = h->d_state.p;
-    return TD_OK;
+    return rc;
 }
 namespace { void handle_born(); void handle_gone(); }   // (the pinned pool of the gzip decoder follows the handles' lives: below)
 extern "C" {
@@ -908,16 +917,8 @@ int td_count_lines_device(td_handle *h, const void *d_fastq, uint64_t nbytes, vo
     TD_HIPCHK(hipSetDevice(h->device));
     *out = 0;
     if (nbytes == 0) return TD_OK;
-    const uint64_t tile = 16 * 1024;
-    const uint64_t nt = (nbytes + tile - 1) / tile;
-    if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    TD_HIPCHK(h->d_tilecounts.ensure(nt));
-    TD_HIPCHK(h->d_state.ensure(nt));
     hipStream_t s = (hipStream_t)stream;
-    uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
-    hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
-    hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, h->d_cursor.p);
-    TD_HIPCHK(hipGetLastError());
+    { const int rc = line_prefix(h, d_fastq, nbytes, 16, s, h->d_cursor.p); if (rc) return rc; }
     unsigned long long v = 0;
     TD_HIPCHK(hipMemcpyAsync(&v, h->d_cursor.p, 8, hipMemcpyDeviceToHost, s));
     TD_HIPCHK(hipStreamSynchronize(s));
@@ -1041,36 +1042,70 @@ uint64_t count_line_ends(const uint8_t *p, size_t n) {
     for (size_t i = 0; i < n; i++) k += p[i] == '\n' || (p[i] == '\r' && !(i + 1 < n && p[i + 1] == '\n'));
     return k;
 }
-// The same for a piece that lies on the device, d_buf[0..total), whose last `ntail` bytes the host holds in `tail`: *c is the
-// cut inside the tail.  The line phase at the cut comes from the line-count kernels over the piece up to the cut (a pass
-// more, and a wait for it: weighted counting only).  *line_at: index of the line the piece starts with, moved on to the cut.
-int cut_before_header_device(td_handle *h, const uint8_t *d_buf, size_t total, const uint8_t *tail, size_t ntail, hipStream_t st,
-                             uint64_t *line_at, size_t *c) {
-    if (*c == 0) return TD_OK;
-    const uint64_t nbytes = total - ntail + *c, nt = (nbytes + 16383) / 16384;
-    if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    TD_HIPCHK(h->d_tilecounts.ensure(nt));
-    TD_HIPCHK(h->d_state.ensure(nt));
-    TD_HIPCHK(h->d_seam_lines.ensure(1));
-    const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
-    hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, st, d_buf, nbytes, (uint32_t)nt, h->d_tilecounts.p);
-    hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, st, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, h->d_seam_lines.p);
-    TD_HIPCHK(hipGetLastError());
-    unsigned long long lines = 0;
-    TD_HIPCHK(hipMemcpyAsync(&lines, h->d_seam_lines.p, 8, hipMemcpyDeviceToHost, st));
-    TD_HIPCHK(hipStreamSynchronize(st));
-    const size_t c2 = cut_before_header(tail, *c, *line_at + lines);
-    if (c2 != *c) {
-        if (c2 == 0 && ntail < total) return fail(TD_E_LIMIT, "a header line exceeds the staging buffer");
-        *c = c2; lines--;
-    }
-    *line_at += lines;
-    return TD_OK;
-}
+constexpr size_t ZB_CARRY = (size_t)4 << 20;                 // longest line end-less tail of a device piece carried to the next one
+constexpr size_t ZB_TAIL = (size_t)1 << 20;                  // bytes of a device piece's end looked at for its last line end
 
-// Staging a piece into pinned memory on several host threads (one memcpy or pread stream does not
-// reach PCIe speed): `part(offset, n)` fills bytes [offset, offset + n) of the piece.
-inline int stage_threads() {
+// The piece loop of the three routes whose text lies on the device (BGZF, and ordinary gzip resolved or decoded there): where
+// a piece is cut and how it is counted.  The line index travels from piece to piece through d_cursor[pieces & 1] on the
+// device; pin_cursor[0] holds it after the newest counted piece once the stream has drained.
+struct PieceCutter {
+    td_handle *h = nullptr;
+    uint64_t max_reads = 0; int weights = 0;
+    uint64_t bytes_submitted = 0;             // every line holds >= 1 byte: bounds the line index from above
+    unsigned pieces = 0;
+    uint64_t line_at = 0;                     // weights: index of the line the next piece starts with
+    uint64_t stop_line = ~0ull;               // (reference :272: the loop ends at maxreads; the kernels ignore reads past it either way)
+    int start(td_handle *hh, uint64_t max_reads_, int weights_) {      // (zeroes the cursors on the work stream)
+        h = hh; max_reads = max_reads_; weights = weights_;
+        TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream.s));
+        if (!h->pin_cursor.p) TD_HIPCHK(h->pin_cursor.alloc(2));
+        h->pin_cursor.p[0] = 0;
+        stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
+        return TD_OK;
+    }
+    // the pieces counted so far already hold read number max_reads (as of the last wait for the stream)
+    bool done() const { return h->pin_cursor.p[0] >= stop_line; }
+    // d_text[0..total), whose last min(total, ZB_TAIL) bytes the host holds in `tail` unless `last`: -> *cut, the bytes up to
+    // its last line end (weights: short of a header line that would end the piece), counted by a launch enqueued on `st`
+    // with the line index on its way to pin_cursor; the caller carries d_text[*cut..total) to the front of the next piece
+    int submit(const uint8_t *d_text, size_t total, const uint8_t *tail, bool last, hipStream_t st, size_t *cut) {
+        *cut = total;
+        if (!last && total) {
+            const size_t ntail = std::min(total, ZB_TAIL);
+            size_t c = cut_at_line_end(tail, ntail);
+            if (weights && c) {
+                // (a header stays with its record: cut_before_header.  The line phase at the cut comes from the line prefix over
+                // the piece up to the cut -- a pass more, and a wait for it: weighted counting only)
+                TD_HIPCHK(h->d_seam_lines.ensure(1));
+                { const int rc = line_prefix(h, d_text, total - ntail + c, 16, st, h->d_seam_lines.p); if (rc) return rc; }
+                unsigned long long lines = 0;
+                TD_HIPCHK(hipMemcpyAsync(&lines, h->d_seam_lines.p, 8, hipMemcpyDeviceToHost, st));
+                TD_HIPCHK(hipStreamSynchronize(st));
+                const size_t c2 = cut_before_header(tail, c, line_at + lines);
+                if (c2 != c) {
+                    if (c2 == 0 && ntail < total) return fail(TD_E_LIMIT, "a header line exceeds the staging buffer");
+                    c = c2; lines--;
+                }
+                line_at += lines;
+            }
+            // (c == 0: no line end in sight -- a gzip member that stops inside a line, say, followed by one of a few bytes:
+            // everything waits for the next piece)
+            if ((c ? ntail - c : total) > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
+            *cut = c ? total - ntail + c : 0;
+        }
+        if (*cut) {
+            const int rc = launch_count(h, d_text, *cut, 0, max_reads, weights, st, h->d_cursor.p + (pieces & 1), h->d_cursor.p + ((pieces + 1) & 1), bytes_submitted);
+            if (rc) return rc;
+            bytes_submitted += *cut; pieces++;
+            TD_HIPCHK(hipMemcpyAsync(h->pin_cursor.p, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, st));
+        }
+        return TD_OK;
+    }
+};
+
+}  // namespace
+// the number of staging threads (hidden; csrc/md5.hip asks too)
+extern "C" __attribute__((visibility("hidden"))) int td_stage_thread_count(void) {
     static const int n = []() {
         const char *env = getenv("TAGDIG_STAGE_THREADS");
         // (default: 16 where the host has the cores -- measured 46 vs 45 GB/s from a host buffer, 36 vs 32 GB/s from a
@@ -1080,9 +1115,12 @@ inline int stage_threads() {
     }();
     return n;
 }
+namespace {
+// Staging a piece into pinned memory on several host threads (one memcpy or pread stream does not
+// reach PCIe speed): `part(offset, n)` fills bytes [offset, offset + n) of the piece.
 template <typename Part>
 bool stage_parallel(size_t total, Part &&part) {
-    const int nt = (int)std::min<size_t>((size_t)stage_threads(), (total >> 20) + 1);      // (a thread per MiB at most)
+    const int nt = (int)std::min<size_t>((size_t)td_stage_thread_count(), (total >> 20) + 1);      // (a thread per MiB at most)
     if (nt <= 1) return part(0, total);
     std::atomic<bool> ok{true};
     std::vector<std::thread> pool;
@@ -1151,8 +1189,6 @@ namespace {
 constexpr uint32_t ZB_MEMBERS = 49152;
 constexpr size_t ZB_IN = (size_t)1280 << 20;                 // compressed bytes per batch, at most
 constexpr size_t ZB_PIECE = (size_t)64 << 20;                // ... staged through pinned memory in pieces of this size
-constexpr size_t ZB_CARRY = (size_t)4 << 20;                 // longest line end-less tail carried to the next batch
-constexpr size_t ZB_TAIL = (size_t)1 << 20;                  // bytes of a batch's end looked at for its last line end
 
 // count_bgzf_gpu's / td_bgzf_inflate_range's batch buffers (kept on the handle between files; grown when a larger
 // file comes), the CRC tables, the kernel's LDS attribute.  *ok = false: no room on the device.
@@ -1189,52 +1225,36 @@ int ensure_bgzf_buffers(td_handle *h, uint32_t need_members, size_t need_in, boo
     return TD_OK;
 }
 
-int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weights, bool *not_bgzf) {
-    *not_bgzf = false;
-    tdhost::GzSource src;
-    if (!src.map_only(path)) { *not_bgzf = true; return TD_OK; }           // (empty or unreadable: the host path reports it)
-    uint32_t bs0 = 0, hs0 = 0;
-    if (!tdhost::GzSource::bgzf_header(src.map, src.bsize, &bs0, &hs0)) { *not_bgzf = true; return TD_OK; }
-    // Batch buffers sized from the file: a small file is walked first (headers only), which also tells whether EVERY
-    // member is BGZF -- gzip.open (reference :240-241) reads a file whose later members are plain gzip, so such a file
-    // goes to the host inflater; a file beyond 1 GiB compressed takes the full batch (49 152 members, ~9.5 GB of HBM).
-    uint32_t need_members = ZB_MEMBERS;
-    size_t need_in = ZB_IN;
-    if (src.bsize <= ((size_t)1 << 30)) {
-        size_t at = 0;
-        uint32_t n = 0;
-        while (at < src.bsize) {
-            uint32_t bs = 0, hs = 0;
-            if (!tdhost::GzSource::bgzf_header(src.map + at, src.bsize - at, &bs, &hs) || bs < hs + 8 || at + bs > src.bsize) {
-                *not_bgzf = true;                                  // (a damaged file too: the host path reports it)
-                return TD_OK;
-            }
-            at += bs; n++;
-        }
-        need_members = std::min<uint32_t>(ZB_MEMBERS, std::max<uint32_t>(64, (n + 63) / 64 * 64));
-        need_in = std::min<size_t>(ZB_IN, (src.bsize + 4095) / 4096 * 4096);
+// members of src.map[begin, end) by their headers alone; false: bytes that are no BGZF member (or a damaged one)
+bool bgzf_count_members(const tdhost::GzSource &src, size_t begin, size_t end, uint32_t *n) {
+    *n = 0;
+    for (size_t at = begin; at < end; (*n)++) {
+        uint32_t bs = 0, hs = 0;
+        if (!tdhost::GzSource::bgzf_header(src.map + at, src.bsize - at, &bs, &hs) || bs < hs + 8 || at + bs > src.bsize) return false;
+        at += bs;
     }
-    {
-        bool ok = true;
-        const int rc_b = ensure_bgzf_buffers(h, need_members, need_in, &ok);
-        if (rc_b) return rc_b;
-        if (!ok) { *not_bgzf = true; return TD_OK; }          // no room on the device: the host inflater takes the file
-    }
-    const uint32_t batch_members = std::min<uint32_t>(h->bgzf->cap_members, h->zb_members);
-    const size_t batch_in = h->bgzf->cap_in, piece_cap = std::min(ZB_PIECE, h->bgzf->cap_in + 64);
-    TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream.s));
+    return true;
+}
+
+// The members of a file's next batch, for count_bgzf_gpu and td_bgzf_inflate_range: the walk over the member headers from
+// `pos` to `end`, descriptors and compressed bytes into the slot's pinned buffers, then on their way to the device.
+struct BgzfFeeder {
+    td_handle *h; const tdhost::GzSource &src;
+    size_t pos, end;
+    bool zeros_end;                           // bytes that are no member but all zero end the walk quietly (padding: gzip.open skips it)
+    const char *bad_header;                   // ... anything else that is no member is refused with this text
     struct Batch { uint32_t n = 0; size_t out_total = 0; bool last = false; };
-    size_t pos = 0;
-    // members of the next batch: descriptors and compressed bytes into the slot's pinned buffers, then on their way to the device
-    auto prepare = [&](int slot, Batch &b) -> int {
+    int prepare(int slot, Batch &b) {
+        const uint32_t batch_members = std::min<uint32_t>(h->bgzf->cap_members, h->zb_members);
+        const size_t batch_in = h->bgzf->cap_in, piece_cap = std::min(ZB_PIECE, h->bgzf->cap_in + 64);
         td_handle::ZSlot &z = h->bgzf->slot[slot];
         b = Batch();
         const size_t first = pos;
-        while (pos < src.bsize && b.n < batch_members) {
+        while (pos < end && b.n < batch_members) {
             uint32_t bs = 0, hs = 0;
             if (!tdhost::GzSource::bgzf_header(src.map + pos, src.bsize - pos, &bs, &hs) || bs < hs + 8 || pos + bs > src.bsize) {
-                if (tdhost::GzSource::only_zeros(src.map + pos, src.bsize - pos)) { pos = src.bsize; break; }     // (padding: gzip.open skips it)
-                return fail(TD_E_IO, "damaged BGZF member header (or a member that is not BGZF) in a file that began as BGZF");
+                if (zeros_end && tdhost::GzSource::only_zeros(src.map + pos, src.bsize - pos)) { pos = end; break; }
+                return fail(TD_E_IO, bad_header);
             }
             if (pos + bs - first > batch_in) break;
             const uint8_t *tail = src.map + pos + bs - 8;
@@ -1245,7 +1265,7 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
             b.out_total += isize; b.n++;
             pos += bs;
         }
-        b.last = pos >= src.bsize;
+        b.last = pos >= end;
         const size_t nin = pos - first;
         // the compressed bytes, through the two pinned pieces in turn (+ 64 zero bytes: the decoder reads a little ahead)
         int k = 0;
@@ -1262,19 +1282,39 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         if (b.n) TD_HIPCHK(hipMemcpyAsync(z.d_mem.p, z.pin_mem.p, (size_t)b.n * sizeof(tdinf::Member), hipMemcpyHostToDevice, h->copy_stream.s));
         TD_HIPCHK(hipEventRecord(z.copied.e, h->copy_stream.s));
         return TD_OK;
-    };
-    Batch cur, nxt;
+    }
+};
+
+int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weights, bool *not_bgzf) {
+    *not_bgzf = false;
+    tdhost::GzSource src;
+    if (!src.map_only(path)) { *not_bgzf = true; return TD_OK; }           // (empty or unreadable: the host path reports it)
+    uint32_t bs0 = 0, hs0 = 0;
+    if (!tdhost::GzSource::bgzf_header(src.map, src.bsize, &bs0, &hs0)) { *not_bgzf = true; return TD_OK; }
+    // Batch buffers sized from the file: a small file is walked first (headers only), which also tells whether EVERY
+    // member is BGZF -- gzip.open (reference :240-241) reads a file whose later members are plain gzip, so such a file
+    // goes to the host inflater; a file beyond 1 GiB compressed takes the full batch (49 152 members, ~9.5 GB of HBM).
+    uint32_t need_members = ZB_MEMBERS;
+    size_t need_in = ZB_IN;
+    if (src.bsize <= ((size_t)1 << 30)) {
+        uint32_t n = 0;
+        if (!bgzf_count_members(src, 0, src.bsize, &n)) { *not_bgzf = true; return TD_OK; }      // (a damaged file too: the host path reports it)
+        need_members = std::min<uint32_t>(ZB_MEMBERS, std::max<uint32_t>(64, (n + 63) / 64 * 64));
+        need_in = std::min<size_t>(ZB_IN, (src.bsize + 4095) / 4096 * 4096);
+    }
+    {
+        bool ok = true;
+        const int rc_b = ensure_bgzf_buffers(h, need_members, need_in, &ok);
+        if (rc_b) return rc_b;
+        if (!ok) { *not_bgzf = true; return TD_OK; }          // no room on the device: the host inflater takes the file
+    }
+    PieceCutter cutter;
+    int rc = cutter.start(h, max_reads, weights); if (rc) return rc;
+    BgzfFeeder feed{h, src, 0, src.bsize, true, "damaged BGZF member header (or a member that is not BGZF) in a file that began as BGZF"};
+    BgzfFeeder::Batch cur, nxt;
     int slot = 0;
-    // (reference :272: the loop ends at maxreads -- no further batch is inflated once a counted batch's line index shows
-    // that the bound has been passed; the kernels ignore reads past it either way)
-    if (!h->pin_cursor.p) TD_HIPCHK(h->pin_cursor.alloc(2));
-    h->pin_cursor.p[0] = 0;
-    const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
-    int rc = prepare(0, cur); if (rc) return rc;
+    rc = feed.prepare(0, cur); if (rc) return rc;
     size_t carry = 0;                                       // bytes of an unfinished line at the front of this slot's output
-    uint64_t line_at = 0;                                   // weights: index of the line the next piece starts with
-    uint64_t bytes_submitted = 0;
-    unsigned pieces = 0;
     for (;;) {
         td_handle::ZSlot &z = h->bgzf->slot[slot];
         TD_HIPCHK(hipStreamWaitEvent(h->work_stream.s, z.copied.e, 0));
@@ -1288,30 +1328,13 @@ int count_bgzf_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         if (cur.n) TD_HIPCHK(hipMemcpyAsync(z.pin_status.p, z.d_status.p, (size_t)cur.n * 4, hipMemcpyDeviceToHost, h->work_stream.s));
         if (ntail && !cur.last) TD_HIPCHK(hipMemcpyAsync(z.pin_tail.p, z.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, h->work_stream.s));
         // the next batch is read and sent while this one inflates
-        if (!cur.last) { rc = prepare(slot ^ 1, nxt); if (rc) return rc; }
+        if (!cur.last) { rc = feed.prepare(slot ^ 1, nxt); if (rc) return rc; }
         TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
-        if (h->pin_cursor.p[0] >= stop_line) break;               // (the batches counted so far already hold read number max_reads)
+        if (cutter.done()) break;                               // (no further batch is inflated)
         for (uint32_t i = 0; i < cur.n; i++)
             if (z.pin_status.p[i]) return fail(TD_E_IO, z.pin_status.p[i] == 100 ? "BGZF member fails its CRC-32" : "inflate error in a BGZF member");
-        size_t cut = total;
-        if (!cur.last && total) {
-            size_t c = cut_at_line_end(z.pin_tail.p, ntail);
-            if (weights) { rc = cut_before_header_device(h, z.d_out.p, total, z.pin_tail.p, ntail, h->work_stream.s, &line_at, &c); if (rc) return rc; }
-            if (c == 0) {                                       // (no line end in sight: everything waits for the next batch)
-                if (total > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
-                cut = 0;
-            } else {
-                if (ntail - c > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
-                cut = total - ntail + c;
-            }
-        }
-        if (cut) {
-            rc = launch_count(h, z.d_out.p, cut, 0, max_reads, weights, h->work_stream.s, h->d_cursor.p + (pieces & 1),
-                              h->d_cursor.p + ((pieces + 1) & 1), bytes_submitted);
-            if (rc) return rc;
-            bytes_submitted += cut; pieces++;
-            TD_HIPCHK(hipMemcpyAsync(h->pin_cursor.p, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream.s));
-        }
+        size_t cut = 0;
+        rc = cutter.submit(z.d_out.p, total, z.pin_tail.p, cur.last, h->work_stream.s, &cut); if (rc) return rc;
         if (cur.last) break;
         carry = total - cut;
         if (carry) TD_HIPCHK(hipMemcpyAsync(h->bgzf->slot[slot ^ 1].d_out.p, z.d_out.p + cut, carry, hipMemcpyDeviceToDevice, h->work_stream.s));
@@ -1388,9 +1411,8 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
     TD_HIPCHK(hipMemsetAsync(h->d_gzflag.p, 0, 16, h->work_stream.s));
     int rc = TD_OK;
     if (!h->d_crctab.p) { bool ok = true; rc = ensure_bgzf_buffers(h, 0, 0, &ok); if (rc) return rc; }      // (the CRC tables)
-    TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, h->work_stream.s));
-    if (!h->pin_cursor.p) TD_HIPCHK(h->pin_cursor.alloc(2));
-    h->pin_cursor.p[0] = 0;
+    PieceCutter cutter;
+    rc = cutter.start(h, max_reads, weights); if (rc) return rc;
     // (events the host waits on sleeping: a spinning wait would take a core from the decoder's threads)
     for (auto &g : h->gslot) {
         if (!g.copied.e) TD_HIPCHK(g.copied.create(hipEventDisableTiming | hipEventBlockingSync));
@@ -1403,7 +1425,6 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
         size_t total = 0;
         std::vector<std::pair<uint32_t, size_t>> crc_len;       // filled from pin_crc after the batch has been resolved
     };
-    const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
     size_t carry = 0;                                           // bytes of an unfinished line at the front of the current slot's output
     // the next batch from the decoder: block table, symbols and windows on their way to the device; the decoder's buffers
     // are handed back as soon as the copies have been made
@@ -1473,9 +1494,6 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
     Batch cur, nxt;
     int slot = 0;
     rc = prepare(0, cur); if (rc) return rc;
-    uint64_t line_at = 0;                                       // weights: index of the line the next piece starts with
-    uint64_t bytes_submitted = 0;
-    unsigned pieces = 0;
     while (cur.valid) {
         td_handle::GSlot &g = h->gslot[slot];
         TD_HIPCHK(hipStreamWaitEvent(h->work_stream.s, g.copied.e, 0));
@@ -1500,28 +1518,10 @@ int count_gzip_dev(td_handle *h, const char *path, uint64_t max_reads, int weigh
         if (*flag) return fail(TD_E_IO, "gzip: distance reaches before the start of the output");
         for (uint32_t k = 0; k < cur.nblk; k++) cur.crc_len[k].first = g.pin_crc.p[k];
         if (!src.pi.dev_check(cur.crc_len, cur.member_done, cur.want_crc)) return fail(TD_E_IO, std::string("gzip: ") + src.pi.error());
-        if (h->pin_cursor.p[0] >= stop_line) break;               // (the batches counted so far already hold read number max_reads)
-        size_t cut = total;
-        if (!cur.last && total) {
-            size_t c = cut_at_line_end(g.pin_tail.p, ntail);
-            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, g.pin_tail.p, ntail, h->work_stream.s, &line_at, &c); if (rc) return rc; }
-            if (c == 0) {
-                // no line end in sight -- a member that stops inside a line, followed by an empty one or one of a few bytes
-                // (a batch closes at every member end): everything waits for the next batch
-                if (total > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
-                cut = 0;
-            } else {
-                if (ntail - c > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
-                cut = total - ntail + c;
-            }
-        }
-        if (cut) {
-            rc = launch_count(h, g.d_out.p, cut, 0, max_reads, weights, h->work_stream.s, h->d_cursor.p + (pieces & 1),
-                              h->d_cursor.p + ((pieces + 1) & 1), bytes_submitted);
-            if (rc) return rc;
-            bytes_submitted += cut; pieces++;
-            TD_HIPCHK(hipMemcpyAsync(h->pin_cursor.p, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, h->work_stream.s));
-        }
+        if (cutter.done()) break;
+        // (a batch closes at every member end: one that stops inside a line may leave no line end in sight)
+        size_t cut = 0;
+        rc = cutter.submit(g.d_out.p, total, g.pin_tail.p, cur.last, h->work_stream.s, &cut); if (rc) return rc;
         if (cur.last) break;
         const size_t carry_next = total - cut;
         if (carry_next) TD_HIPCHK(hipMemcpyAsync(h->gslot[slot ^ 1].d_out.p, g.d_out.p + cut, carry_next, hipMemcpyDeviceToDevice, h->work_stream.s));
@@ -1561,7 +1561,6 @@ struct MappedFile {
 // against the member's CRC-32 and length, and counted where they lie.  *not_applicable: nothing has been counted and the
 // host decoder (count_gzip_dev) should take the file -- too small, no room on the device, a second member, or a stream this
 // decoder does not chain.
-extern "C" int td_load_file_range(td_handle *h, const char *path, uint64_t offset, uint64_t length, void *d_dst);
 // The file goes through the device in SEGMENTS of compressed bytes (1 GiB; what the buffers are sized for): a segment's first
 // chunk starts exactly where the segment before ended -- a block boundary, or a member's first block -- its other chunks
 // where k_gz_find finds block starts, its last chunk ends at the first block boundary at or past the segment's end (the
@@ -1934,50 +1933,31 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         return TD_OK;
     }
     hipStream_t st = h->work_stream.s;
-    TD_HIPCHK(hipMemsetAsync(h->d_cursor.p, 0, 16, st));
-    if (!h->pin_cursor.p) TD_HIPCHK(h->pin_cursor.alloc(2));
-    h->pin_cursor.p[0] = 0;
+    PieceCutter cutter;
+    { const int rc = cutter.start(h, max_reads, weights); if (rc) return rc; }
     PinBuf<uint8_t> pin_tail;
-    const uint64_t stop_line = max_reads >= (1ull << 60) ? ~0ull : 4 * (std::max<uint64_t>(1, max_reads) - 1) + 2;
     size_t carry = 0;
-    uint64_t line_at = 0;                                                  // weights: index of the line the next piece starts with
-    uint64_t bytes_submitted = 0;
-    unsigned pieces = 0;
     const double t0 = tdhost::ParInflate::now();
     for (;;) {
         uint64_t nb = 0; bool last = false, gave_up = false;
         int rc = zs.next(carry, &nb, &last, &gave_up);
         if (rc) { *not_applicable = false; return rc; }
         if (gave_up) {
-            if (pieces == 0 && zs.segments == 0) { if (zs.verbose) fprintf(stderr, "gz_gpu_inflate: the host decoder takes the file\n"); return TD_OK; }
+            if (cutter.pieces == 0 && zs.segments == 0) { if (zs.verbose) fprintf(stderr, "gz_gpu_inflate: the host decoder takes the file\n"); return TD_OK; }
             *not_applicable = false;
             return fail(TD_E_IO, std::string("gzip (device decoder): ") + zs.why);
         }
         *not_applicable = false;                                           // (from here on the file's verdict is this decoder's)
         td_handle::GzGpu &g = *h->gzgpu;
         const size_t total = carry + nb;
-        size_t cut = total;
         if (!last && total) {
             if (!pin_tail.p) TD_HIPCHK(pin_tail.alloc(ZB_TAIL));
             const size_t ntail = std::min(total, ZB_TAIL);
             TD_HIPCHK(hipMemcpyAsync(pin_tail.p, g.d_out.p + total - ntail, ntail, hipMemcpyDeviceToHost, st));
             TD_HIPCHK(hipStreamSynchronize(st));
-            size_t c = cut_at_line_end(pin_tail.p, ntail);
-            if (weights) { rc = cut_before_header_device(h, g.d_out.p, total, pin_tail.p, ntail, st, &line_at, &c); if (rc) return rc; }
-            if (c == 0) {
-                if (total > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
-                cut = 0;
-            } else {
-                if (ntail - c > ZB_CARRY) return fail(TD_E_LIMIT, "a single line exceeds the staging buffer");
-                cut = total - ntail + c;
-            }
         }
-        if (cut) {
-            rc = launch_count(h, g.d_out.p, cut, 0, max_reads, weights, st, h->d_cursor.p + (pieces & 1), h->d_cursor.p + ((pieces + 1) & 1), bytes_submitted);
-            if (rc) return rc;
-            bytes_submitted += cut; pieces++;
-            TD_HIPCHK(hipMemcpyAsync(h->pin_cursor.p, h->d_cursor.p + (pieces & 1), 8, hipMemcpyDeviceToHost, st));
-        }
+        size_t cut = 0;
+        rc = cutter.submit(g.d_out.p, total, pin_tail.p, last, st, &cut); if (rc) return rc;
         const size_t carry_next = total - cut;
         if (!last && carry_next) {
             // (to the front of the same buffer, behind the count: the pieces do not overlap when the text is longer than twice the carry)
@@ -1992,7 +1972,7 @@ int count_gzip_gpu(td_handle *h, const char *path, uint64_t max_reads, int weigh
         TD_HIPCHK(hipStreamSynchronize(st));
         carry = carry_next;
         if (last) break;
-        if (h->pin_cursor.p[0] >= stop_line) break;                          // (the segments counted so far already hold read number max_reads)
+        if (cutter.done()) break;
     }
     if (!h->sink) h->last_gz_route = 1;       // (td_last_gz_route speaks of the files td_count_file counted only)
     if (zs.verbose)
@@ -2296,36 +2276,6 @@ int td_count_host(td_handle *h, const void *fastq, uint64_t nbytes, uint64_t fir
     return pump(h, reader, nbytes + 1, first_line, max_reads, weights, lines_out);
 }
 
-static int gunzip_fast(const char *path, void *dst, uint64_t capacity, uint64_t chunk, uint64_t *n_out);
-int td_gunzip_file(const char *path, void *dst, uint64_t capacity, uint64_t chunk, uint64_t *n_out) {
-    if (!path || !dst || !n_out) return fail(TD_E_ARG, "NULL argument");
-    {
-        struct stat sb0;
-        if (stat(path, &sb0) == 0 && S_ISREG(sb0.st_mode) && sb0.st_size == 0) { *n_out = 0; return TD_OK; }     // (gzip.open: no data)
-    }
-    const int rc = gunzip_fast(path, dst, capacity, chunk, n_out);
-    if (rc != TD_E_IO) return rc;
-    // a decoder has refused the file: the reference's reading rules say how this ends (gz_pyrules.hpp)
-    const std::string refusal = g_err;
-    MappedFile mf(path);
-    if (!mf.ok) return fail(rc, refusal);
-    tdhost::PyGzipReader pr(mf.p, mf.n);
-    uint64_t n = 0;
-    uint8_t extra[tdhost::PyGzipReader::CHUNK];
-    for (;;) {
-        const bool full = n + tdhost::PyGzipReader::CHUNK > capacity;      // (a request's bytes may not fit any more: aside, then copied)
-        const long got = pr.read(full ? extra : (uint8_t *)dst + n, tdhost::PyGzipReader::CHUNK);
-        if (got < 0) return fail(gz_code(pr.kind), pr.message);
-        if (got == 0) break;
-        if (full) {
-            if (n + (uint64_t)got > capacity) return fail(TD_E_LIMIT, "destination too small");
-            memcpy((uint8_t *)dst + n, extra, (size_t)got);
-        }
-        n += (uint64_t)got;
-    }
-    *n_out = n;
-    return TD_OK;
-}
 static int gunzip_fast(const char *path, void *dst, uint64_t capacity, uint64_t chunk, uint64_t *n_out) {
     if (getenv("TAGDIG_GUNZIP_PIPELINE")) {
         // the decoder as count_gzip_dev drives it (dev_next / dev_release / dev_check), markers resolved by the host: the
@@ -2382,20 +2332,34 @@ static int gunzip_fast(const char *path, void *dst, uint64_t capacity, uint64_t 
     return TD_OK;
 }
 
-static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, int weights);
-int td_count_file(td_handle *h, const char *path, uint64_t max_reads, int weights) {
-    if (!h || !path) return fail(TD_E_ARG, "NULL argument");
-    if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
-    TD_HIPCHK(hipSetDevice(h->device));
-    return count_file_impl(h, path, max_reads, weights);
-}
-// for csrc/census.hip (hidden): the file through td_count_file's readers, its pieces handed to `sink`
-__attribute__((visibility("hidden"))) int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink) {
-    TD_HIPCHK(hipSetDevice(h->device));
-    h->sink = sink;
-    const int rc = count_file_impl(h, path, max_reads, 0);
-    h->sink = nullptr;
-    return rc;
+int td_gunzip_file(const char *path, void *dst, uint64_t capacity, uint64_t chunk, uint64_t *n_out) {
+    if (!path || !dst || !n_out) return fail(TD_E_ARG, "NULL argument");
+    {
+        struct stat sb0;
+        if (stat(path, &sb0) == 0 && S_ISREG(sb0.st_mode) && sb0.st_size == 0) { *n_out = 0; return TD_OK; }     // (gzip.open: no data)
+    }
+    const int rc = gunzip_fast(path, dst, capacity, chunk, n_out);
+    if (rc != TD_E_IO) return rc;
+    // a decoder has refused the file: the reference's reading rules say how this ends (gz_pyrules.hpp)
+    const std::string refusal = g_err;
+    MappedFile mf(path);
+    if (!mf.ok) return fail(rc, refusal);
+    tdhost::PyGzipReader pr(mf.p, mf.n);
+    uint64_t n = 0;
+    uint8_t extra[tdhost::PyGzipReader::CHUNK];
+    for (;;) {
+        const bool full = n + tdhost::PyGzipReader::CHUNK > capacity;      // (a request's bytes may not fit any more: aside, then copied)
+        const long got = pr.read(full ? extra : (uint8_t *)dst + n, tdhost::PyGzipReader::CHUNK);
+        if (got < 0) return fail(gz_code(pr.kind), pr.message);
+        if (got == 0) break;
+        if (full) {
+            if (n + (uint64_t)got > capacity) return fail(TD_E_LIMIT, "destination too small");
+            memcpy((uint8_t *)dst + n, extra, (size_t)got);
+        }
+        n += (uint64_t)got;
+    }
+    *n_out = n;
+    return TD_OK;
 }
 static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, int weights) {
     const size_t len = strlen(path);
@@ -2439,6 +2403,7 @@ static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, i
     }
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(TD_E_IO, std::string("cannot open ") + path);
+    struct FdEnd { int fd; ~FdEnd() { close(fd); } } fd_end{fd};
     struct stat sb;
     const bool regular = fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode);
     uint64_t fpos = 0;
@@ -2462,8 +2427,21 @@ static int count_file_impl(td_handle *h, const char *path, uint64_t max_reads, i
         fpos += n;
         return (long)n;
     };
-    int rc = pump(h, reader, 0, 0, max_reads, weights, nullptr);
-    close(fd);
+    return pump(h, reader, 0, 0, max_reads, weights, nullptr);
+}
+
+int td_count_file(td_handle *h, const char *path, uint64_t max_reads, int weights) {
+    if (!h || !path) return fail(TD_E_ARG, "NULL argument");
+    if (!h->have_index) return fail(TD_E_STATE, "td_set_index has not been called");
+    TD_HIPCHK(hipSetDevice(h->device));
+    return count_file_impl(h, path, max_reads, weights);
+}
+// for csrc/census.hip (hidden): the file through td_count_file's readers, its pieces handed to `sink`
+__attribute__((visibility("hidden"))) int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink) {
+    TD_HIPCHK(hipSetDevice(h->device));
+    h->sink = sink;
+    const int rc = count_file_impl(h, path, max_reads, 0);
+    h->sink = nullptr;
     return rc;
 }
 
@@ -2542,59 +2520,18 @@ int td_bgzf_inflate_range(td_handle *h, const char *path, uint64_t off_begin, ui
         need_members = (uint32_t)std::min<uint64_t>(ZB_MEMBERS, std::max<uint64_t>(64, ((off_end - off_begin) / 28 + 64) / 64 * 64));   // (a member is 28 bytes at least)
         // (an upper bound only: walk the range when it is small enough for the bound to be wasteful)
         uint32_t n = 0;
-        for (size_t at = off_begin; at < off_end; n++) {
-            uint32_t bs = 0, hs = 0;
-            if (!tdhost::GzSource::bgzf_header(src.map + at, src.bsize - at, &bs, &hs) || bs < hs + 8 || at + bs > src.bsize)
-                return fail(TD_E_IO, "damaged BGZF member header");
-            at += bs;
-        }
+        if (!bgzf_count_members(src, off_begin, off_end, &n)) return fail(TD_E_IO, "damaged BGZF member header");
         need_members = std::min<uint32_t>(ZB_MEMBERS, std::max<uint32_t>(64, (n + 63) / 64 * 64));
     }
     bool ok = true;
     int rc = ensure_bgzf_buffers(h, need_members, need_in, &ok);
     if (rc) return rc;
     if (!ok) return fail(TD_E_HIP, "no room on the device for the BGZF batch buffers");
-    const uint32_t batch_members = std::min<uint32_t>(h->bgzf->cap_members, h->zb_members);
-    const size_t batch_in = h->bgzf->cap_in, piece_cap = std::min(ZB_PIECE, h->bgzf->cap_in + 64);
-    size_t pos = off_begin;
     uint64_t out_pos = 0;
-    struct Batch { uint32_t n = 0; size_t out_total = 0; };
-    auto prepare = [&](int slot, Batch &b) -> int {
-        td_handle::ZSlot &z = h->bgzf->slot[slot];
-        b = Batch();
-        const size_t first = pos;
-        while (pos < off_end && b.n < batch_members) {
-            uint32_t bs = 0, hs = 0;
-            if (!tdhost::GzSource::bgzf_header(src.map + pos, src.bsize - pos, &bs, &hs) || bs < hs + 8 || pos + bs > src.bsize)
-                return fail(TD_E_IO, "damaged BGZF member header");
-            if (pos + bs - first > batch_in) break;
-            const uint8_t *tail = src.map + pos + bs - 8;
-            const uint32_t crc = tail[0] | (tail[1] << 8) | (tail[2] << 16) | ((uint32_t)tail[3] << 24);
-            const uint32_t isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
-            if (isize > 65536) return fail(TD_E_IO, "BGZF member larger than 64 KiB");
-            z.pin_mem.p[b.n] = tdinf::Member{pos + hs - first, b.out_total, bs - hs - 8, isize, crc, 0};
-            b.out_total += isize; b.n++;
-            pos += bs;
-        }
-        const size_t nin = pos - first;
-        int k = 0;
-        for (size_t off = 0; off < nin + 64; off += piece_cap, k ^= 1) {
-            td_handle::ZPiece &zp = h->bgzf->piece[k];
-            if (zp.busy) { TD_HIPCHK(hipEventSynchronize(zp.sent.e)); zp.busy = false; }
-            const size_t want = std::min(piece_cap, nin + 64 - off), have = off < nin ? std::min(want, nin - off) : 0;
-            if (have) stage_parallel(have, [&](size_t o2, size_t len) { memcpy(zp.pin.p + o2, src.map + first + off + o2, len); return true; });
-            if (want > have) memset(zp.pin.p + have, 0, want - have);
-            { const int urc = upload(h, z.d_in.p + off, zp.pin.p, want); if (urc) return urc; }
-            TD_HIPCHK(hipEventRecord(zp.sent.e, h->copy_stream.s));
-            zp.busy = true;
-        }
-        if (b.n) TD_HIPCHK(hipMemcpyAsync(z.d_mem.p, z.pin_mem.p, (size_t)b.n * sizeof(tdinf::Member), hipMemcpyHostToDevice, h->copy_stream.s));
-        TD_HIPCHK(hipEventRecord(z.copied.e, h->copy_stream.s));
-        return TD_OK;
-    };
-    Batch cur, nxt;
+    BgzfFeeder feed{h, src, (size_t)off_begin, (size_t)off_end, false, "damaged BGZF member header"};
+    BgzfFeeder::Batch cur, nxt;
     int slot = 0;
-    rc = prepare(0, cur); if (rc) return rc;
+    rc = feed.prepare(0, cur); if (rc) return rc;
     while (cur.n) {
         td_handle::ZSlot &z = h->bgzf->slot[slot];
         if (out_pos + cur.out_total > capacity) return fail(TD_E_LIMIT, "destination too small for the inflated members");
@@ -2604,7 +2541,7 @@ int td_bgzf_inflate_range(td_handle *h, const char *path, uint64_t off_begin, ui
         TD_HIPCHK(hipGetLastError());
         TD_HIPCHK(hipMemcpyAsync(z.pin_status.p, z.d_status.p, (size_t)cur.n * 4, hipMemcpyDeviceToHost, h->work_stream.s));
         // the next batch is read and sent while this one inflates
-        rc = prepare(slot ^ 1, nxt); if (rc) return rc;
+        rc = feed.prepare(slot ^ 1, nxt); if (rc) return rc;
         TD_HIPCHK(hipStreamSynchronize(h->work_stream.s));
         for (uint32_t i = 0; i < cur.n; i++)
             if (z.pin_status.p[i]) return fail(TD_E_IO, z.pin_status.p[i] == 100 ? "BGZF member fails its CRC-32" : "inflate error in a BGZF member");
@@ -3009,21 +2946,7 @@ bool use_split2(const td_handle *h) {
 }
 
 int launch_split_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, hipStream_t s, bool counted = false) {
-    const uint64_t tile = use_split2(h) ? 24 * 1024 : 16 * 1024;
-    const uint64_t nt = (nbytes + tile - 1) / tile;
-    if (nt > 0x7FFFFFFFull) return fail(TD_E_LIMIT, "buffer too large for one launch; split it");
-    TD_HIPCHK(h->d_tilecounts.ensure(nt));
-    TD_HIPCHK(h->d_state.ensure(nt));
-    const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
-    // `counted`: the count pass just enqueued on this stream ran over the same bytes in tiles of this size and left
-    // every tile's terminator count in d_tileinfo
-    if (counted && use_split2(h) && h->last_fast_tile_kb == 24 && h->last_fast_ntiles == (uint32_t)nt)
-        hipLaunchKernelGGL(tdk::k_info_counts, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, s, h->d_tileinfo.p, (uint32_t)nt, h->d_tilecounts.p);
-    else if (use_split2(h)) hipLaunchKernelGGL((tdk::k_count_lines<6>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
-    else hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
-    hipLaunchKernelGGL(tdk::k_scan_tiles, dim3(1), dim3(1024), 0, s, h->d_tilecounts.p, (uint32_t)nt, h->d_state.p, h->d_cursor.p);
-    TD_HIPCHK(hipGetLastError());
-    return TD_OK;
+    return line_prefix(h, d_fastq, nbytes, use_split2(h) ? 24 : 16, s, h->d_cursor.p, counted);
 }
 
 // k_split on `s` (after launch_split_prefix); out must hold one int2 per sequence line of the buffer
@@ -3459,14 +3382,6 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
     return TD_OK;
 }
 
-static int split_device_impl(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, int32_t *d_out,
-                             uint64_t out_capacity, void *stream, uint64_t *n_terminators, bool counted);
-
-int td_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, int32_t *d_out,
-                    uint64_t out_capacity, void *stream, uint64_t *n_terminators) {
-    return split_device_impl(h, d_fastq, nbytes, first_line, d_out, out_capacity, stream, n_terminators, false);
-}
-
 // (counted: a count pass over the same bytes was just enqueued on `stream` -- its per-tile terminator counts serve)
 static int split_device_impl(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, int32_t *d_out,
                              uint64_t out_capacity, void *stream, uint64_t *n_terminators, bool counted) {
@@ -3490,6 +3405,11 @@ static int split_device_impl(td_handle *h, const void *d_fastq, uint64_t nbytes,
     return check_device_errors(h, st);
 }
 
+int td_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, int32_t *d_out,
+                    uint64_t out_capacity, void *stream, uint64_t *n_terminators) {
+    return split_device_impl(h, d_fastq, nbytes, first_line, d_out, out_capacity, stream, n_terminators, false);
+}
+
 int td_count_and_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads,
                               int32_t *d_out, uint64_t out_capacity, void *stream, uint64_t *n_terminators) {
     // BASELINE config 5: the counting path and the adapter-trim branch over ONE buffer resident in HBM -- the count
@@ -3503,25 +3423,6 @@ int td_count_and_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes
     return split_device_impl(h, d_fastq, nbytes, first_line, d_out, out_capacity, stream, n_terminators, true);
 }
 
-static int split_file_impl(td_handle *h, const char *in_path, const char *const *out_paths, uint64_t max_reads, uint64_t stats[3],
-                           bool by_reference_rules, bool *gz_refused);
-int td_split_file(td_handle *h, const char *in_path, const char *const *out_paths, uint64_t max_reads, uint64_t stats[3]) {
-    if (!h || !in_path || !out_paths) return fail(TD_E_ARG, "NULL argument");
-    if (!h->have_splitter) return fail(TD_E_STATE, "td_set_splitter has not been called");
-    bool gz_refused = false;
-    const int rc = split_file_impl(h, in_path, out_paths, max_reads, stats, false, &gz_refused);
-    if (!gz_refused) return rc;
-    // a decoder has refused the .gz input: barcodeSplitter reads it through gzip.open too (reference :1318-1319) and leaves
-    // its loop behind the quality line of read number maxreads (:1361-1362) -- its exception, or, where the loop is through
-    // before the damage, the split taken again through the reference's own reading rules (gz_pyrules.hpp)
-    const std::string refusal = g_err;
-    MappedFile mf(in_path);
-    if (!mf.ok) return fail(rc, refusal);
-    const uint64_t r = std::max<uint64_t>(1, max_reads);
-    const tdhost::GzVerdict v = tdhost::gz_verdict_lines(mf.p, mf.n, r >= (1ull << 60) ? ~0ull : 4 * r);
-    if (v.kind != tdhost::GZ_OK) return fail(gz_code(v.kind), v.message);
-    return split_file_impl(h, in_path, out_paths, max_reads, stats, true, &gz_refused);
-}
 static int split_file_impl(td_handle *h, const char *in_path, const char *const *out_paths, uint64_t max_reads, uint64_t stats[3],
                            bool by_reference_rules, bool *gz_refused) {
     TD_HIPCHK(hipSetDevice(h->device));
@@ -3724,6 +3625,25 @@ static int split_file_impl(td_handle *h, const char *in_path, const char *const 
     if (w.nonascii) return fail(TD_E_NONASCII, "the splitter accepts ASCII FASTQ only (a byte >= 0x80 was found)");
     if (have_st) return check_device_errors(h, st);
     return TD_OK;
+}
+
+
+int td_split_file(td_handle *h, const char *in_path, const char *const *out_paths, uint64_t max_reads, uint64_t stats[3]) {
+    if (!h || !in_path || !out_paths) return fail(TD_E_ARG, "NULL argument");
+    if (!h->have_splitter) return fail(TD_E_STATE, "td_set_splitter has not been called");
+    bool gz_refused = false;
+    const int rc = split_file_impl(h, in_path, out_paths, max_reads, stats, false, &gz_refused);
+    if (!gz_refused) return rc;
+    // a decoder has refused the .gz input: barcodeSplitter reads it through gzip.open too (reference :1318-1319) and leaves
+    // its loop behind the quality line of read number maxreads (:1361-1362) -- its exception, or, where the loop is through
+    // before the damage, the split taken again through the reference's own reading rules (gz_pyrules.hpp)
+    const std::string refusal = g_err;
+    MappedFile mf(in_path);
+    if (!mf.ok) return fail(rc, refusal);
+    const uint64_t r = std::max<uint64_t>(1, max_reads);
+    const tdhost::GzVerdict v = tdhost::gz_verdict_lines(mf.p, mf.n, r >= (1ull << 60) ? ~0ull : 4 * r);
+    if (v.kind != tdhost::GZ_OK) return fail(gz_code(v.kind), v.message);
+    return split_file_impl(h, in_path, out_paths, max_reads, stats, true, &gz_refused);
 }
 
 }  // extern "C"
