@@ -501,6 +501,80 @@ int td_tagnet_pairs(td_handle *h, const td_tagnet *net, uint32_t *ij_out, uint64
 int td_tagnet_degrees(td_handle *h, const td_tagnet *net, uint32_t *deg_out);
 int td_tagnet_free(td_handle *h, td_tagnet *net);
 
+/* ---- tag placement (csrc/place.hip; tagdigger_amd/tagdigger_fun.py genome_cut_sites and place_tags drive these) -------
+ *
+ * Where on a genome the tags of a census come from.  A GBS tag begins at a cut site, so the only
+ * places it can come from are the genome's cut sites: an in-silico digest, the window behind every site, and a bounded
+ * Hamming join of the tags against those windows.  The rule, in integers only:
+ *   genome     the bytes td_fasta_frame_device writes, d_seq[0 .. seq_bytes); record r = 0 .. R - 1 is
+ *              [rec_start[r], rec_start[r + 1]), rec_start[0] = 0, rec_start[R] = seq_bytes, non-decreasing
+ *   remnants   1 .. TD_PLACE_MAX_SITES non-empty ACGT strings no longer than taglen (what follows the barcode in a read)
+ *   forward locus (r, x)   rec_start[r] <= x, x + L <= rec_start[r + 1], every byte of G[x, x + L) is one of ACGT, and
+ *              G[x ...] begins with a remnant.  Window G[x, x + L); SAM position x - rec_start[r] + 1 = cut position
+ *   reverse locus (r, x)   the same bounds and alphabet; reverseComplement(G[x, x + L)) begins with a remnant.  Window:
+ *              that reverse complement; SAM position as above; cut position = SAM position + L - 1
+ *   order      loci ascend by (r, x, strand), forward before reverse; a locus's id is its rank
+ *   dropped    a remnant met on a strand whose window leaves its record (the record of the window's first base on the
+ *              forward strand, of its last base on the reverse strand) or holds a byte outside ACGT is no locus and is
+ *              counted; several remnants at one (x, strand) are one hit
+ *   n_at[t][d] the loci whose window differs from tag t at exactly d positions, d = 0 .. k (plain Hamming distance over
+ *              all L bases; loci are counted, not distinct windows)
+ *   dist[t]    the smallest d with n_at[t][d] > 0, or 255; locus[t] the smallest locus id at that distance, or UINT64_MAX
+ *   compares   the L bases are cut into P = k + 1 parts, part p = bases [floor(p L / P), floor((p + 1) L / P)); two
+ *              sequences within distance k agree on at least one part; compares = sum over p and t of the DISTINCT
+ *              windows that agree with tag t on all of part p.  A pair is reported in the lowest part it agrees on.
+ * Nothing is ever sized by tags x loci.
+ *
+ * td_place_sites: the digest (count, scan, emit: loci come out in order without a sort), then the windows sorted and
+ *   equal ones collapsed to (window, multiplicity, first locus id).  The result stays in *out until td_place_free or
+ *   td_destroy: the handle owns it.  stats[TD_PLACE_*] (optional); ms (optional, 4 entries): device time of count, scan,
+ *   emit, dedupe -- events around the launches only, every buffer allocated before; the radix sort inside dedupe (and
+ *   inside td_place_tags' parts) reads 12 bytes back before its passes, which those two figures include.  seq_bytes = 0 gives an empty place without a launch.  Errors: TD_E_ARG (taglen outside 1..64, no or
+ *   more than 16 remnants, a remnant empty, longer than taglen or outside ACGT, rec_start not as above), TD_E_LIMIT (more
+ *   than TD_PLACE_MAX_LOCI loci, or 2^31 records and more).
+ * td_place_loci: x_out[n] (offset in the genome), rec_out[n], strand_out[n] (0 forward, 1 reverse), and, unless NULL,
+ *   windows_out[n * L] as ASCII; n = stats[TD_PLACE_LOCI].  Each pointer may be NULL.
+ * td_place_tags: n tags of the place's L bases, upper-case ACGT, n * L ASCII bytes; equal tags are allowed, every tag
+ *   is decided on its own.  n_at_out[4 n] (entries d > k are 0), dist_out[n], locus_out[n]; stats[TD_PLACED_*]
+ *   (optional); ms (optional, 4 entries): device time of pack, the parts' sorted window tables (0 when this place has
+ *   them for this k already), runs, join.  Zero tags or zero loci give all-none results without a launch.  Errors:
+ *   TD_E_ARG (k > 3, L < k + 1), TD_E_ALPHABET (td_last_bad_index gives the tag), TD_E_LIMIT (more than 2^30 tags; or
+ *   compares above the cap -- the message names both numbers, stats[TD_PLACED_TAGS] and stats[TD_PLACED_COMPARES] are
+ *   set, and no comparing kernel has been launched).  The cap is TD_PLACE_DEFAULT_MAX_COMPARES unless the option
+ *   "place_max_compares" sets another.
+ * td_place_free: frees a place now. */
+typedef struct td_place td_place;
+enum {
+    TD_PLACE_LOCI = 0,          /* loci                                                                     */
+    TD_PLACE_FORWARD = 1,       /* ... on the forward strand                                                */
+    TD_PLACE_REVERSE = 2,       /* ... on the reverse strand                                                */
+    TD_PLACE_DISTINCT = 3,      /* distinct windows                                                         */
+    TD_PLACE_DROP_BOUNDS = 4,   /* remnant hits whose window leaves its record                              */
+    TD_PLACE_DROP_ALPHABET = 5, /* remnant hits whose window holds a byte outside ACGT                      */
+    TD_PLACE_RECORDS = 6,       /* R                                                                        */
+    TD_PLACED_TAGS = 0,         /* n                                                                        */
+    TD_PLACED_UNIQUE = 1,       /* tags with exactly one locus at their smallest distance                   */
+    TD_PLACED_MULTI = 2,        /* ... with more than one                                                   */
+    TD_PLACED_NONE = 3,         /* ... with no locus within k                                               */
+    TD_PLACED_COMPARES = 4,     /* tag x distinct window comparisons of the device path                     */
+    TD_PLACE_MAX_TAGLEN = 64,
+    TD_PLACE_MAX_SITES = 16,
+    TD_PLACE_MAX_MISMATCH = 3
+};
+/* A 4-base degenerate site (CWGC) has about 2 * 2 * 3e9 / 256 = 4.7e7 loci in 3 GB; 2^27 leaves room for a genome three
+ * times as dense.  A locus costs 28 bytes (x, record, window) and 10 more while the place is built, a distinct window
+ * 24, and every part of a k 40 bytes per distinct window: under 30 GB at the limit with k = 3. */
+#define TD_PLACE_MAX_LOCI (1u << 27)
+/* k_pl_join on long runs (200 000 windows sharing a part, 7.1e9 compares): 6.56e11 compares / s on an MI355X
+ * (profiles/place/bench_mi355x.txt); times 2 s, so that the kernel stays near two seconds on a shared card */
+#define TD_PLACE_DEFAULT_MAX_COMPARES 1300000000000ull
+int td_place_sites(td_handle *h, const void *d_seq, uint64_t seq_bytes, const uint64_t *rec_start /* HOST, R + 1 */, uint32_t R,
+                   const char *const *remnants, uint32_t n_remnants, uint32_t taglen, td_place **out, uint64_t stats[8], double *ms);
+int td_place_loci(td_handle *h, const td_place *pl, uint64_t *x_out, uint32_t *rec_out, uint8_t *strand_out, char *windows_out);
+int td_place_tags(td_handle *h, td_place *pl, const char *seqs, uint32_t n, uint32_t max_mismatch, uint32_t *n_at_out,
+                  uint8_t *dist_out, uint64_t *locus_out, uint64_t stats[8], double *ms);
+int td_place_free(td_handle *h, td_place *pl);
+
 /* ---- genotype calls and marker filters (csrc/genocall.hip; tagdigger_amd/tagdigger_fun.py call_genotypes drives it) --
  *
  * From the samples x tags count matrix to genotype calls, without bringing the matrix to the host.
@@ -797,6 +871,7 @@ int64_t td_format_csv_row(const int64_t *vals, uint64_t n, char *out, uint64_t c
  *                    one workgroup takes every tile, run after run; 0 = no cap, the default).  The fix-up pass follows it
  *   "md5_piece"      td_md5_files: bytes a file contributes per round (tests; a multiple of 64, 0 = the built-in size)
  *   "tagnet_max_compares"  td_tagnet_build: the compare cap (tests; 0 = TD_TAGNET_DEFAULT_MAX_COMPARES)
+ *   "place_max_compares"   td_place_tags: the compare cap (tests; 0 = TD_PLACE_DEFAULT_MAX_COMPARES)
  *   "debug_ablate"   timing-only ablation bits -- the counts are WRONG when non-zero
  * Returns TD_E_ARG for unknown names. */
 int td_set_option(td_handle *h, const char *name, int64_t value);

@@ -179,6 +179,10 @@ def load():
     sig("td_tagnet_pairs", i32, vp, vp, vp, u64, C.POINTER(u64))
     sig("td_tagnet_degrees", i32, vp, vp, vp)
     sig("td_tagnet_free", i32, vp, vp)
+    sig("td_place_sites", i32, vp, vp, u64, vp, u32, pp, u32, u32, C.POINTER(vp), C.POINTER(u64), dp)
+    sig("td_place_loci", i32, vp, vp, vp, vp, vp, vp)
+    sig("td_place_tags", i32, vp, vp, vp, u32, u32, vp, vp, vp, C.POINTER(u64), dp)
+    sig("td_place_free", i32, vp, vp)
     sig("td_geno_call", i32, vp, vp, u32, u32, u32, vp, vp, vp, C.POINTER(GenoParams), vp, C.POINTER(vp), vp, vp,
         C.POINTER(u64), dp)
     sig("td_relate_joint", i32, vp, vp, u32, u32, vp, vp, C.POINTER(vp), dp)
@@ -208,6 +212,7 @@ EXPORTS = [
     "td_census_begin", "td_census_device", "td_census_file", "td_census_stats", "td_census_fetch", "td_census_end",
     "td_qc_begin", "td_qc_device", "td_qc_file", "td_qc_stats", "td_qc_fetch", "td_qc_end",
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
+    "td_place_sites", "td_place_loci", "td_place_tags", "td_place_free",
     "td_geno_call", "td_relate_joint", "td_ld_pairs", "td_ld_last_times",
     "td_impute_knn", "td_impute_last_times",
     "td_parent_trios", "td_parent_last_times",

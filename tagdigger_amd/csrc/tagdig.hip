@@ -145,6 +145,7 @@ struct td_handle {
     const td_piece_sink *sink = nullptr;
     void *census = nullptr;                   // csrc/census.hip's state (td_census_begin .. td_census_end)
     void *qc = nullptr;                       // csrc/qc.hip's state (td_qc_begin .. td_qc_end)
+    void *places = nullptr;                   // csrc/place.hip's list of the places alive (td_place_sites .. td_place_free)
     uint32_t qc_flush_tiles = 0;              // (tests: tiles between two merges of k_qc's LDS tables; 0 = the built-in 4096)
     int num_cu = 256;
     // index
@@ -232,6 +233,7 @@ struct td_handle {
     uint64_t gz_gpu_min = (uint64_t)8 << 20;  // ... for files of this many compressed bytes and more
     uint64_t md5_piece = 0;                   // (tests) td_md5_files: bytes a file contributes per round; 0 = the built-in 1 MiB
     uint64_t tagnet_max_compares = 0;         // (tests) td_tagnet_build: the compare cap; 0 = TD_TAGNET_DEFAULT_MAX_COMPARES
+    uint64_t place_max_compares = 0;          // (tests) td_place_tags: the compare cap; 0 = TD_PLACE_DEFAULT_MAX_COMPARES
     uint32_t gz_gpu_terr_kb = 128;            // ... one chunk per this much compressed data
     int gz_gpu_verify = 0;                    // ... the block search decodes a block before it believes its header
     uint32_t gz_gpu_seg_kb = 1u << 20, gz_gpu_margin_kb = 16384;      // ... a segment of compressed data (1 GiB), and how far its last chunk may run past it
@@ -685,6 +687,9 @@ uint32_t td_last_bad_index(void) { return g_bad; }
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h) { return h->md5_piece; }
 // the "tagnet_max_compares" option (csrc/tagnet.hip), and the index td_last_bad_index reports
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_compares(const td_handle *h) { return h->tagnet_max_compares; }
+// for csrc/place.hip (hidden): its list's place on the handle, and the "place_max_compares" option
+extern "C" __attribute__((visibility("hidden"))) void **td_handle_places(td_handle *h) { return &h->places; }
+extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_place_max_compares(const td_handle *h) { return h->place_max_compares; }
 extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx) { g_bad = idx; }
 // every launch enqueued through this handle (they may be on its own streams) has finished
 extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h) {
@@ -763,6 +768,7 @@ void td_destroy(td_handle *h) {
     (void)hipDeviceSynchronize();
     td_census_release(h);
     td_qc_release(h);
+    td_place_release(h);
     delete h;
 }
 
@@ -2655,6 +2661,7 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
     else if (n == "md5_piece") { if (value < 0 || value % 64) return fail(TD_E_ARG, "md5_piece: a multiple of 64, or 0"); h->md5_piece = (uint64_t)value; }
     else if (n == "tagnet_max_compares") { if (value < 0) return fail(TD_E_ARG, "tagnet_max_compares: 0 or more"); h->tagnet_max_compares = (uint64_t)value; }
     else if (n == "gz_gpu_terr_kb") { if (value < 16 || value > 4096) return fail(TD_E_ARG, "gz_gpu_terr_kb: 16..4096"); h->gz_gpu_terr_kb = (uint32_t)value; }
+    else if (n == "place_max_compares") { if (value < 0) return fail(TD_E_ARG, "place_max_compares: 0 or more"); h->place_max_compares = (uint64_t)value; }
     else if (n == "gz_gpu_release") { h->gzgpu.reset(new td_handle::GzGpu()); }
     else if (n == "gz_gpu_verify") h->gz_gpu_verify = value ? 1 : 0;
     else if (n == "gz_gpu_seg_kb") { if (value < 64 || value > (4 << 20)) return fail(TD_E_ARG, "gz_gpu_seg_kb: 64..4194304"); h->gz_gpu_seg_kb = (uint32_t)value; }

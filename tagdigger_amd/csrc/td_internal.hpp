@@ -46,6 +46,11 @@ TD_HIDDEN uint32_t td_handle_qc_flush_tiles(const td_handle *h);
 TD_HIDDEN uint32_t td_handle_max_grid(const td_handle *h);
 // qc.hip, for td_destroy: frees the handle's QC state, if any
 TD_HIDDEN void td_qc_release(td_handle *h);
+// tagdig.hip, for place.hip: the list of places' place on the handle; the option "place_max_compares" (0: not set)
+TD_HIDDEN void **td_handle_places(td_handle *h);
+TD_HIDDEN uint64_t td_handle_place_max_compares(const td_handle *h);
+// place.hip, for td_destroy: frees every place the handle still owns
+TD_HIDDEN void td_place_release(td_handle *h);
 }
 
 // a failed HIP call ends the calling function with TD_E_HIP and "<the call as written>: <HIP's text>"

@@ -117,6 +117,32 @@ class TagNet:
             pass
 
 
+class Place:
+    """A genome's cut sites resident on the device (td_place_sites); freed by close(), when collected, or with the
+    engine.  `.stats`: loci, forward, reverse, distinct, dropped_bounds, dropped_alphabet, records; `.ms`: device time."""
+
+    def __init__(self, eng, ptr, taglen, stats, ms):
+        self._eng, self.ptr, self.taglen, self.stats, self.ms = eng, ptr, taglen, stats, ms
+        self.n = stats["loci"]
+
+    def close(self):
+        if self.ptr and self.ptr.value and getattr(self._eng, "_h", None):
+            self._eng._L.td_place_free(self._eng._h, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+PLACE_STATS = ("loci", "forward", "reverse", "distinct", "dropped_bounds", "dropped_alphabet", "records")   # TD_PLACE_* slots
+PLACE_MS = ("count", "scan", "emit", "dedupe")
+PLACED_STATS = ("tags", "unique", "multi", "none", "compares")      # TD_PLACED_* slots
+PLACED_MS = ("pack", "parts", "runs", "join")
+
+
 TAGNET_STATS = ("tags", "edges", "kept", "deg0", "deg1", "hubs", "pairs", "compares")
 TAGNET_MS = ("pack", "sort", "runs", "compare", "select", "host_order")
 TAGNET_TILE = 256           # TD_TAGNET_TILE: rows and columns of a compare tile of csrc/tagnet.hip
@@ -593,6 +619,55 @@ class Engine:
 
     def tagnet_free(self, net):
         net.close()
+
+    # ------------------------------------------------------------------ tag placement (td_place_*; csrc/place.hip)
+    def place_sites(self, d_seq, nbytes, rec_start, remnants, taglen):
+        """td_place_sites over a framed genome in device memory: rec_start holds the R + 1 record bounds.  Returns a
+        Place.  A failure raises TagdigError with `.stats` holding what is known."""
+        import numpy as np
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        out, st, ms = C.c_void_p(), (C.c_uint64 * 8)(), (C.c_double * 4)()
+        rc = self._L.td_place_sites(self._h, C.c_void_p(d_seq) if d_seq else None, int(nbytes), rs.ctypes.data_as(C.c_void_p),
+                                    len(rs) - 1, _c_strings(remnants), len(remnants), int(taglen), C.byref(out), st, ms)
+        stats = dict(zip(PLACE_STATS, (int(x) for x in st)))
+        if rc:
+            err = self._error(rc)
+            err.stats = stats
+            raise err
+        return Place(self, out, int(taglen), stats, dict(zip(PLACE_MS, ms)))
+
+    def place_loci(self, place, windows=False):
+        """td_place_loci: (x uint64 [n], record uint32 [n], strand uint8 [n], windows as a list of str or None)."""
+        import numpy as np
+        n, L = place.n, place.taglen
+        x, rec, strand = np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint32), np.zeros(max(1, n), np.uint8)
+        win = C.create_string_buffer(max(1, n * L)) if windows else None
+        B.check(self._L.td_place_loci(self._h, place.ptr, x.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p),
+                                      strand.ctypes.data_as(C.c_void_p), win))
+        text = win.raw[:n * L].decode("ascii") if windows else None
+        return x[:n], rec[:n], strand[:n], [text[i * L:(i + 1) * L] for i in range(n)] if windows else None
+
+    def place_tags(self, place, seqs, n, max_mismatch):
+        """td_place_tags: seqs is the n * taglen ASCII bytes of n ACGT tags.  Returns (n_at uint32 [n, 4], dist uint8 [n],
+        locus uint64 [n], stats, ms).  A failure raises TagdigError; `.bad_index` holds the tag for TD_E_ALPHABET,
+        `.stats` what is known at a TD_E_LIMIT."""
+        import numpy as np
+        n = int(n)
+        if len(seqs) != n * place.taglen:
+            raise ValueError("seqs must hold n * taglen bytes")
+        buf = np.frombuffer(bytes(seqs), dtype=np.uint8) if len(seqs) else np.zeros(1, dtype=np.uint8)
+        n_at, dist, locus = np.zeros((max(1, n), 4), np.uint32), np.zeros(max(1, n), np.uint8), np.zeros(max(1, n), np.uint64)
+        st, ms = (C.c_uint64 * 8)(), (C.c_double * 4)()
+        rc = self._L.td_place_tags(self._h, place.ptr, buf.ctypes.data_as(C.c_void_p), n, int(max_mismatch),
+                                   n_at.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
+                                   locus.ctypes.data_as(C.c_void_p), st, ms)
+        stats = dict(zip(PLACED_STATS, (int(x) for x in st)))
+        if rc:
+            err = self._error(rc)
+            err.bad_index = self._L.td_last_bad_index() if rc == -6 else None
+            err.stats = stats
+            raise err
+        return n_at[:n], dist[:n], locus[:n], stats, dict(zip(PLACED_MS, ms))
 
     # ------------------------------------------------------------------ what the matrix calls below share
     @contextlib.contextmanager

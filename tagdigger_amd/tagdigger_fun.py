@@ -371,6 +371,333 @@ def census_markers(seqs, counts, min_ratio=0.03, prefix="Mrkr", numdig=7, start=
     return out
 
 
+# ------------------------------------------------------------------ tag placement (csrc/place.hip)
+PLACE_NONE = 255                      # dist of a tag without a locus within k
+PLACE_NO_LOCUS = 0xFFFFFFFFFFFFFFFF   # its locus
+
+
+class CutSites:
+    """What genome_cut_sites returns: the in-silico digest of a genome.  `.names` and `.rec_start` (R + 1 offsets into
+    the framed genome) describe the records; `.x`, `.rec`, `.strand` (0 forward, 1 reverse) the loci in id order;
+    `.pos1` their SAM positions and `.cutpos` their cut positions; `.windows()` their windows; `.stats`: loci, forward,
+    reverse, distinct, dropped_bounds, dropped_alphabet, records, backend.  With backend "gpu" the digest stays on the
+    device until close(), so that several tag sets can be placed against it."""
+
+    def __init__(self, names, rec_start, remnants, taglen, x, rec, strand, stats, place=None, windows=None):
+        import numpy as np
+        self.names, self.rec_start, self.remnants, self.taglen = list(names), [int(v) for v in rec_start], list(remnants), taglen
+        self.x = np.asarray(x, dtype=np.int64)
+        self.rec = np.asarray(rec, dtype=np.int64)
+        self.strand = np.asarray(strand, dtype=np.int64)
+        self.stats, self._place, self._windows, self._distinct = stats, place, windows, None
+        starts = np.asarray(self.rec_start, dtype=np.int64)
+        self.pos1 = self.x - starts[self.rec] + 1 if len(self.x) else self.x
+        self.cutpos = self.pos1 + (taglen - 1) * self.strand
+
+    @property
+    def records(self):
+        """[(name, length)] in genome order"""
+        return [(nm, self.rec_start[r + 1] - self.rec_start[r]) for r, nm in enumerate(self.names)]
+
+    def windows(self):
+        if self._windows is None:
+            self._windows = self._place._eng.place_loci(self._place, windows=True)[3] if len(self.x) else []
+        return self._windows
+
+    def distinct(self):
+        """{window: [loci that have it, the smallest of their ids]}"""
+        if self._distinct is None:
+            d = {}
+            for i, w in enumerate(self.windows()):
+                e = d.get(w)
+                if e is None:
+                    d[w] = [1, i]
+                else:
+                    e[0] += 1
+            self._distinct = d
+        return self._distinct
+
+    def close(self):
+        if self._place is not None:
+            self._place.close()
+            self._place = None
+
+
+def _place_remnants(cutsite, taglen):
+    taglen = int(taglen)
+    if not 1 <= taglen <= 64:
+        raise ValueError("taglen must be 1..64")
+    cutsite = cutsite.upper()
+    if cutsite == "":
+        raise ValueError("tags cannot be placed without a cut site: the loci are the genome's cut sites")
+    if not set(cutsite) <= set('ACGTNRYKMSWBDHV'):
+        raise ValueError("invalid cut site {!r}".format(cutsite))
+    remnants = enumerate_cut_sites(cutsite)
+    if len(remnants) > 16:
+        raise ValueError("the cut site {} stands for {} sequences; at most 16 are taken".format(cutsite, len(remnants)))
+    if len(cutsite) > taglen:
+        raise ValueError("the cut site is longer than the tags")
+    return remnants, taglen
+
+
+def _place_records(genome, nbytes):
+    """SAM names and record bounds from the headers a genome reader recorded (exp_frag_size's HostGenome / DeviceGenome)."""
+    events = []
+    for evs, exc in genome.files:
+        events.extend(evs)
+        if exc is not None:
+            raise exc
+    if nbytes and (not events or events[0][1] > 0):
+        raise ValueError("the genome holds sequence before its first header line: a record without a name")
+    names = [(nm.split() or [""])[0] for nm, _ in events]
+    seen = set()
+    for nm in names:
+        if nm == "":
+            raise ValueError("a genome record has an empty name")
+        if nm in seen:
+            raise ValueError("the record name {} occurs twice in the genome".format(nm))
+        seen.add(nm)
+    return names, [off for _, off in events] + [nbytes]
+
+
+def _find_all(text, pat):
+    k = text.find(pat)
+    while k != -1:
+        yield k
+        k = text.find(pat, k + 1)
+
+
+def _sites_host(text, rec_start, remnants, L):
+    """The digest rule of DESIGN 4.20 on a str: (x, rec, strand, windows, stats) in locus order."""
+    cand = set()
+    for c in remnants:
+        cand.update((x, 0) for x in _find_all(text, c))
+        cand.update((y + len(c) - L, 1) for y in _find_all(text, reverseComplement(c)))
+    xs, recs, strands, wins = [], [], [], []
+    stats = dict(loci=0, forward=0, reverse=0, distinct=0, dropped_bounds=0, dropped_alphabet=0, records=len(rec_start) - 1)
+    for x, strand in sorted(cand):
+        if x < 0:
+            stats["dropped_bounds"] += 1
+            continue
+        r = _bisect.bisect_right(rec_start, x + L - 1 if strand else x) - 1
+        if x < rec_start[r] or x + L > rec_start[r + 1]:
+            stats["dropped_bounds"] += 1
+            continue
+        w = text[x:x + L]
+        if not set(w) <= _ACGT:
+            stats["dropped_alphabet"] += 1
+            continue
+        xs.append(x)
+        recs.append(r)
+        strands.append(strand)
+        wins.append(reverseComplement(w) if strand else w)
+        stats["reverse" if strand else "forward"] += 1
+    stats["loci"] = len(xs)
+    stats["distinct"] = len(set(wins))
+    return xs, recs, strands, wins, stats
+
+
+def genome_cut_sites(genomefiles, cutsite, taglen, device=0, backend="gpu"):
+    """The in-silico digest of a genome: every place a tag of `taglen` bases could come from.
+
+    genomefiles: one FASTA file or a list of them, plain or .gz, read as exp_frag_size reads them (headers, and
+    line.strip().upper() of every other line).  A record's name is its header up to the first whitespace.  A locus is a
+    position where a record holds, on either strand, one of the cut site's remnants followed by ACGT only, `taglen`
+    bases in all, inside the record.  Returns a CutSites.
+
+    backend="gpu": the genome is framed into one device buffer and scanned there (csrc/place.hip); a genome file
+    holding a byte >= 0x80 goes to the host, like exp_frag_size's.  backend="host": str.find over the same rule.
+    ValueError: an empty cut site, more than 16 remnants, a cut site longer than taglen, a record with an empty name,
+    two records of one name."""
+    from . import exp_frag_size as efs
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    remnants, L = _place_remnants(cutsite, taglen)
+    paths = [genomefiles] if isinstance(genomefiles, (str, bytes)) else list(genomefiles)
+    if backend == "gpu":
+        eng = default_engine(device)
+        genome = None
+        try:
+            genome = efs.DeviceGenome(eng, paths)
+            names, rec_start = _place_records(genome, genome.nbytes)
+            place = eng.place_sites(genome.d_seq, genome.nbytes, rec_start, remnants, L)
+        except efs._NeedHost:
+            backend = "host"
+        finally:
+            if genome is not None:
+                genome.close()
+        if backend == "gpu":
+            x, rec, strand, _ = eng.place_loci(place)
+            return CutSites(names, rec_start, remnants, L, x, rec, strand, dict(place.stats, backend="gpu"), place=place)
+    genome = efs.HostGenome(paths)
+    names, rec_start = _place_records(genome, len(genome.text))
+    x, rec, strand, wins, stats = _sites_host(genome.text, rec_start, remnants, L)
+    return CutSites(names, rec_start, remnants, L, x, rec, strand, dict(stats, backend="host"), windows=wins)
+
+
+def _place_parts(L, k):
+    return [(p * L // (k + 1), (p + 1) * L // (k + 1)) for p in range(k + 1)]
+
+
+def _place_host(seqs, distinct, L, k):
+    """The placement rule of DESIGN 4.20 over dicts: per part, the distinct windows by their bases of that part; a tag is
+    compared with the windows that share one of its parts, and a pair counts in the lowest part it agrees on.
+    distinct: {window: (multiplicity, first locus id)}.  -> (n_at, dist, locus, compares)."""
+    parts = _place_parts(L, k)
+    tables = []
+    for lo, hi in parts:
+        tab = {}
+        for w in distinct:
+            tab.setdefault(w[lo:hi], []).append(w)
+        tables.append(tab)
+    n_at, dist, locus, compares = [], [], [], 0
+    for s in seqs:
+        row = [0, 0, 0, 0]
+        first = [PLACE_NO_LOCUS] * 4
+        for p, (lo, hi) in enumerate(parts):
+            run = tables[p].get(s[lo:hi], ())
+            compares += len(run)
+            for w in run:
+                if any(s[a:b] == w[a:b] for a, b in parts[:p]):
+                    continue
+                d = sum(1 for u, v in zip(s, w) if u != v)
+                if d <= k:
+                    mult, fid = distinct[w]
+                    row[d] += mult
+                    first[d] = min(first[d], fid)
+        best = next((d for d in range(k + 1) if row[d]), None)
+        n_at.append(row)
+        dist.append(PLACE_NONE if best is None else best)
+        locus.append(PLACE_NO_LOCUS if best is None else first[best])
+    return n_at, dist, locus, compares
+
+
+class PlacementResult:
+    """What place_tags returns, per tag: `.seqs`, `.n_at` (loci at distance 0..3), `.dist` (255: none), `.locus` (id, or
+    2^64 - 1), `.status` ('unique', 'multi', 'none'), `.nbest`, `.nwithin`, and for placed tags `.chrom`, `.pos` (SAM
+    position), `.cutpos`, `.strand` ('top' / 'bot'; None where there is no locus).  `.stats`: tags, unique, multi,
+    none, compares, backend.  `.records`: the genome's (name, length) list; `.taglen`, `.max_mismatch`."""
+
+    def __init__(self, seqs, n_at, dist, locus, sites, k, stats):
+        self.seqs, self.taglen, self.max_mismatch, self.records = seqs, sites.taglen, k, sites.records
+        self.n_at = [[int(v) for v in row] for row in n_at]
+        self.dist = [int(d) for d in dist]
+        self.locus = [int(v) for v in locus]
+        self.nbest = [row[d] if d != PLACE_NONE else 0 for row, d in zip(self.n_at, self.dist)]
+        self.nwithin = [sum(row) for row in self.n_at]
+        self.status = ["none" if d == PLACE_NONE else "unique" if b == 1 else "multi" for d, b in zip(self.dist, self.nbest)]
+        self.chrom, self.pos, self.cutpos, self.strand = [], [], [], []
+        for d, i in zip(self.dist, self.locus):
+            placed = d != PLACE_NONE
+            self.chrom.append(sites.names[int(sites.rec[i])] if placed else None)
+            self.pos.append(int(sites.pos1[i]) if placed else None)
+            self.cutpos.append(int(sites.cutpos[i]) if placed else None)
+            self.strand.append(("bot" if sites.strand[i] else "top") if placed else None)
+        self.stats = dict(stats, tags=len(seqs), unique=self.status.count("unique"), multi=self.status.count("multi"),
+                          none=self.status.count("none"))
+
+
+def place_tags(seqs, sites, max_mismatch=1, backend="gpu"):
+    """Where the tags of a census lie on a genome.
+
+    seqs: n ACGT tags of sites.taglen bases (lower case is upper-cased; equal tags are allowed); sites: what
+    genome_cut_sites returned.  For every tag the loci whose window differs from it at d = 0 .. max_mismatch positions are
+    counted (plain Hamming distance, remnant included, no indels); the tag's distance is the smallest d that has one, its
+    locus the first of those, and it is 'unique' when that d has exactly one locus, 'multi' when more, 'none' when no
+    locus lies within max_mismatch.  Returns a PlacementResult.
+
+    backend="gpu": the join runs on the device against the digest resident there (csrc/place.hip).  An input whose
+    `compares` exceed the device's cap is answered by the host restatement, as is a digest that was built on the host;
+    `.stats["backend"]` says which of the two it was.  backend="host": dicts over the same rule.
+    ValueError: max_mismatch outside 0..3, tags shorter than max_mismatch + 1, a length other than sites.taglen, a
+    character outside ACGT."""
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    k, L = int(max_mismatch), sites.taglen
+    if not 0 <= k <= 3:
+        raise ValueError("max_mismatch must be 0..3")
+    if L < k + 1:
+        raise ValueError("tags of {} bases cannot be placed with {} mismatches: max_mismatch + 1 bases are needed".format(L, k))
+    seqs = [s.upper() for s in seqs]
+    for i, s in enumerate(seqs):
+        if len(s) != L:
+            raise ValueError("tag {} has {} bases, the cut sites were taken for {}".format(i, len(s), L))
+        if not set(s) <= _ACGT:
+            raise ValueError("non-ACGT character in tag {}".format(i))
+    answered_by = "host"
+    if backend == "gpu" and sites._place is not None:
+        if seqs and len(sites.x):
+            from ._binding import TagdigError
+            eng = sites._place._eng
+            try:
+                n_at, dist, locus, stats, ms = eng.place_tags(sites._place, "".join(seqs).encode("ascii"), len(seqs), k)
+                res = PlacementResult(seqs, n_at, dist, locus, sites, k, dict(compares=stats["compares"], backend="gpu"))
+                res.ms = ms
+                return res
+            except TagdigError as exc:
+                if exc.code != -7 or not exc.detail.startswith("tag placement: compares"):
+                    raise
+        else:
+            answered_by = "gpu"           # (nothing to send to the device)
+    distinct = sites.distinct() if seqs and len(sites.x) else {}
+    n_at, dist, locus, compares = _place_host(seqs, distinct, L, k)
+    return PlacementResult(seqs, n_at, dist, locus, sites, k, dict(compares=compares, backend=answered_by))
+
+
+def writePlacementSAM(filename, result, names=None, multi="drop"):
+    """A PlacementResult as a SAM file that readTags_TASSELSAM and exp_frag_size read: @HD, one @SQ per genome record,
+    @PG, one line per tag.  QNAME names[t] or tagSeq=<sequence>; FLAG 0 forward, 16 reverse, 4 unplaced ('none', and
+    'multi' unless multi="first", which places a multi tag at its first locus); MAPQ 60 for a unique tag with no other
+    locus within k, 30 for another unique one, 0 otherwise; CIGAR <L>M; SEQ the tag, reverse-complemented for flag 16;
+    NM:i: the mismatches, X0:i: the loci at that distance, X1:i: the other loci within k."""
+    if multi not in ("drop", "first"):
+        raise ValueError("multi must be 'drop' or 'first'")
+    if names is not None and len(names) != len(result.seqs):
+        raise ValueError("names and tags differ in number")
+    L = result.taglen
+    with open(filename, "w") as fh:
+        fh.write("@HD\tVN:1.6\tSO:unknown\n")
+        for nm, ln in result.records:
+            fh.write("@SQ\tSN:{}\tLN:{}\n".format(nm, ln))
+        fh.write("@PG\tID:tag_place\tPN:tagdigger_amd.tag_place\n")
+        for t, s in enumerate(result.seqs):
+            qname = names[t] if names is not None else "tagSeq=" + s
+            status = result.status[t]
+            opt = "X0:i:{}\tX1:i:{}".format(result.nbest[t], result.nwithin[t] - result.nbest[t])
+            if status != "none":
+                opt = "NM:i:{}\t".format(result.dist[t]) + opt
+            if status == "unique" or (status == "multi" and multi == "first"):
+                rev = result.strand[t] == "bot"
+                mapq = 0 if status == "multi" else 60 if result.nwithin[t] == 1 else 30
+                fields = [qname, 16 if rev else 0, result.chrom[t], result.pos[t], mapq, "{}M".format(L), "*", 0, 0,
+                          reverseComplement(s) if rev else s, "*", opt]
+            else:
+                fields = [qname, 4, "*", 0, 0, "*", "*", 0, 0, s, "*", opt]
+            fh.write("\t".join(str(f) for f in fields) + "\n")
+
+
+def writePlacements(filename, result, counts=None):
+    """A PlacementResult as CSV: Tag sequence, Count (counts[t], or empty), Status, Chromosome, Position (the cut
+    position), Strand (top / bot), Mismatches, Best loci, Loci within k.  A multi tag shows its first locus."""
+    with open(filename, "w", newline="") as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Tag sequence", "Count", "Status", "Chromosome", "Position", "Strand", "Mismatches", "Best loci", "Loci within k"])
+        for t, s in enumerate(result.seqs):
+            placed = result.status[t] != "none"
+            out.writerow([s, "" if counts is None else counts[t], result.status[t],
+                          result.chrom[t] if placed else "", result.cutpos[t] if placed else "", result.strand[t] if placed else "",
+                          result.dist[t] if placed else "", result.nbest[t], result.nwithin[t]])
+
+
+def writeCutSites(filename, sites):
+    """The in-silico digest as CSV: Chromosome, Cut position, Strand (top / bot), Window, in locus order."""
+    with open(filename, "w", newline="") as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Chromosome", "Cut position", "Strand", "Window"])
+        for r, c, st, w in zip(sites.rec.tolist(), sites.cutpos.tolist(), sites.strand.tolist(), sites.windows()):
+            out.writerow([sites.names[r], c, "bot" if st else "top", w])
+
+
 # =============================================================================
 # Periphery of the counting path (SURVEY.md section 2, rows 6-13): plain host
 # Python, no acceleration -- kept so that the reference's command line stays a
