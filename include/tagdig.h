@@ -249,6 +249,14 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
 int td_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line,
                     int32_t *d_out, uint64_t out_capacity, void *stream, uint64_t *n_terminators);
 
+/* Which kernel the splitter's decisions will come from, for the splitter set last and the option "split_kernel" as it
+ * stands: *kernel_out = 2 (k_split2) or 1 (k_split).  k_split2 is asked for by default, and k_split runs all the same
+ * when the entries do not fit its compact form (a group of entries that share their last three characters holds more
+ * than eight, an entry is longer than 128 characters), a restriction site holds a letter outside ACGT, or the barcode
+ * index does not fit beside the tile.  Nothing runs on the device; no decision depends on it (tests: which kernel
+ * decided).  TD_E_STATE before td_set_splitter. */
+int td_split_kernel_in_use(td_handle *h, int *kernel_out);
+
 /* Both per-read branches over one resident buffer (BASELINE config 5: counting + adapter trim): td_count_device's
  * pass, then td_split_device's, enqueued on the same stream; arguments as theirs.  Synchronous. */
 int td_count_and_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line,
@@ -868,7 +876,9 @@ int64_t td_format_csv_row(const int64_t *vals, uint64_t n, char *out, uint64_t c
  *   "stage_kb"       KiB per staged piece of a host buffer, plain file or host-inflated stream (tests; 64 .. 32 768,
  *                    0 = the built-in 32 MiB)
  *   "max_grid"       cap on the workgroups of the free-running path's main pass, k_fast, k_fast2 or k_fast4 (tests: with 1,
- *                    one workgroup takes every tile, run after run; 0 = no cap, the default).  The fix-up pass follows it
+ *                    one workgroup takes every tile, run after run; 0 = no cap, the default).  The fix-up pass follows it.
+ *                    It caps the splitter's grid (k_split2, k_split) in the same way: a workgroup then takes tile after
+ *                    tile.  Every cap gives the same counts and the same decisions
  *   "md5_piece"      td_md5_files: bytes a file contributes per round (tests; a multiple of 64, 0 = the built-in size)
  *   "tagnet_max_compares"  td_tagnet_build: the compare cap (tests; 0 = TD_TAGNET_DEFAULT_MAX_COMPARES)
  *   "place_max_compares"   td_place_tags: the compare cap (tests; 0 = TD_PLACE_DEFAULT_MAX_COMPARES)

@@ -132,6 +132,7 @@ def load():
     sig("td_set_splitter", i32, vp, C.POINTER(C.c_char_p), u32, C.c_char_p, C.c_char_p, C.c_char_p,
         C.POINTER(u32), C.POINTER(C.c_char_p), C.POINTER(C.c_int32), u32)
     sig("td_split_device", i32, vp, vp, u64, u64, vp, u64, vp, C.POINTER(u64))
+    sig("td_split_kernel_in_use", i32, vp, C.POINTER(C.c_int))
     sig("td_count_and_split_device", i32, vp, vp, u64, u64, u64, vp, u64, vp, C.POINTER(u64))
     sig("td_split_file", i32, vp, C.c_char_p, C.POINTER(C.c_char_p), u64, C.POINTER(u64))
     sig("td_fold_rows", i32, vp, C.POINTER(u32), u32, vp, vp)
@@ -203,7 +204,7 @@ def runtime_path():
 EXPORTS = [
     "td_last_error", "td_last_bad_index", "td_create", "td_destroy", "td_set_index", "td_index_info",
     "td_bind_counts", "td_reset", "td_count_device", "td_count_host", "td_count_file",
-    "td_count_lines_device", "td_load_file_range", "td_bgzf_index", "td_bgzf_inflate_range", "td_gunzip_file", "td_gzip_check", "td_gunzip_file_gpu", "td_last_gz_route", "td_gz_shard_open", "td_gz_shard_decode", "td_gz_shard_resolve", "td_crc32_join", "td_set_splitter", "td_split_device", "td_count_and_split_device", "td_split_file", "td_fold_rows", "td_inflate_raw_host", "td_format_csv_row", "td_get_counts", "td_get_stats", "td_get_progress", "td_split_progress", "td_set_option",
+    "td_count_lines_device", "td_load_file_range", "td_bgzf_index", "td_bgzf_inflate_range", "td_gunzip_file", "td_gzip_check", "td_gunzip_file_gpu", "td_last_gz_route", "td_gz_shard_open", "td_gz_shard_decode", "td_gz_shard_resolve", "td_crc32_join", "td_set_splitter", "td_split_device", "td_split_kernel_in_use", "td_count_and_split_device", "td_split_file", "td_fold_rows", "td_inflate_raw_host", "td_format_csv_row", "td_get_counts", "td_get_stats", "td_get_progress", "td_split_progress", "td_set_option",
     "td_kernel_time_ms", "td_kernel_times_ms", "td_debug_counters", "td_dev_alloc", "td_dev_free", "td_memcpy_h2d", "td_memcpy_d2h",
     "td_device_sync", "td_synth_fill_device", "td_synth_expected_device",
     "td_fasta_frame_device", "td_frag_search_device", "td_frag_gather_device",

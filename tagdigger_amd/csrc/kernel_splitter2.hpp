@@ -285,6 +285,22 @@ __global__ __launch_bounds__(FBLOCK, 4) void k_split2(const SplitParams p) {
             const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rs, (uint32_t)tid * 16u, (int)TILE, 0);
             vh = make_uint4(q.x, q.y, q.z, q.w);
         }
+        // A buffer load is checked against the range dword by dword: where the buffer ends inside a dword, that dword's
+        // bytes came as zeros, a terminator among them was lost, and with it the line that starts behind it (a last line
+        // of one or two bytes without a terminator).  Those bytes are fetched one by one; only the buffer's last tile
+        // and the one before it get here.
+        if (__builtin_expect(rem < (uint64_t)(TILE + HALO) && (rem & 3u) != 0, 0)) {
+            const uint32_t w0 = (uint32_t)rem & ~3u;
+            uint32_t word = 0;
+            for (uint32_t q = w0; q < (uint32_t)rem; q++) word |= (uint32_t)p.buf[tbase + q] << (8u * (q - w0));
+            const uint32_t piece = w0 & ~15u, comp = (w0 >> 2) & 3u;
+            auto put = [&](uint4 &x) {
+                x.x = comp == 0u ? word : x.x; x.y = comp == 1u ? word : x.y; x.z = comp == 2u ? word : x.z; x.w = comp == 3u ? word : x.w;
+            };
+#pragma unroll
+            for (int j = 0; j < CPT; j++) if (piece == voff + (uint32_t)j * 1024u) put(v[j]);
+            if (has_halo && piece == TILE + (uint32_t)tid * 16u) put(vh);
+        }
         bool wave_crb = false;
         {
             uint32_t hiacc = vh.x | vh.y | vh.z | vh.w;

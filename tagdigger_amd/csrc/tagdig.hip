@@ -2961,7 +2961,8 @@ int launch_split(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t fi
     const bool two = use_split2(h);
     const uint64_t tile = two ? 24 * 1024 : 16 * 1024;
     const uint64_t nt = (nbytes + tile - 1) / tile;
-    const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * (two ? 4 : 8));
+    uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * (two ? 4 : 8));
+    if (h->max_grid) g = std::min(g, h->max_grid);       // (tests: few workgroups take many tiles each)
     tdk::SplitParams sp{};
     sp.buf = (const uint8_t *)d_fastq; sp.nbytes = nbytes; sp.first_line = first_line;
     sp.prefix = h->d_state.p; sp.ntiles = (uint32_t)nt;
@@ -3410,6 +3411,13 @@ static int split_device_impl(td_handle *h, const void *d_fastq, uint64_t nbytes,
     unsigned long long st[TD_STAT_NSTATS];
     TD_HIPCHK(hipMemcpy(st, h->d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
     return check_device_errors(h, st);
+}
+
+int td_split_kernel_in_use(td_handle *h, int *kernel_out) {
+    if (!h || !kernel_out) return fail(TD_E_ARG, "NULL argument");
+    if (!h->have_splitter) return fail(TD_E_STATE, "td_set_splitter has not been called");
+    *kernel_out = use_split2(h) ? 2 : 1;
+    return TD_OK;
 }
 
 int td_split_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, int32_t *d_out,

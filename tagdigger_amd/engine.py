@@ -408,6 +408,13 @@ class Engine:
                                         (C.c_uint32 * len(begin))(*begin), _c_strings(seqs),
                                         (C.c_int32 * max(1, len(slices)))(*slices), len(seqs)))
 
+    def split_kernel_in_use(self):
+        """td_split_kernel_in_use: 2 (k_split2) or 1 (k_split), the kernel that decides for the splitter set last and
+        the option split_kernel as it stands."""
+        k = C.c_int(0)
+        B.check(self._L.td_split_kernel_in_use(self._h, C.byref(k)))
+        return k.value
+
     def split_device(self, d_ptr, nbytes, first_line=0, stream=0):
         """[(barcode index or -1, findAdapterSeq value), ...] for the sequence lines of a device buffer."""
         import numpy as np
