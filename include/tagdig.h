@@ -462,6 +462,60 @@ int td_qc_stats(td_handle *h, uint64_t out[8]);
 int td_qc_fetch(td_handle *h, uint64_t *barcode_out, uint64_t *base_cycle_out, uint64_t *qual_cycle_out, uint64_t *length_out, uint64_t *meanq_out);
 int td_qc_end(td_handle *h);
 
+/* ---- tag rescue (csrc/rescue.hip; tagdigger_amd/tagdigger_fun.py rescue_tags_fastq drives these) ------------------------
+ *
+ * The reads the counter drops because they lie one or two substitutions from a known tag, per barcode and per tag
+ * (DESIGN.md 4.21).  Per read the rule is the counter's up to the barcode + cut site; then w = the stripped, upper-cased
+ * line from tagoff[b] on and avail = len(w).  A tag of n bases is a candidate iff n <= avail; its distance is the number
+ * of positions i < n with w[i] != tag[i], a character of w outside ACGT mismatching every base.  A candidate at distance
+ * 0: the read is `exact` and nothing is written (it is the counter's).  Otherwise, with m the smallest distance of a
+ * candidate: m <= max_mismatch and one tag attains it -> rescued[b][tag] += 1, rescued_at[m] += 1 and positions[i] += 1
+ * for every mismatching i; m <= max_mismatch and several attain it -> `ambiguous`; else `none`.  So
+ * barcut == exact + rescued1 + rescued2 + ambiguous + none.  Rescue state is independent of the count index and of a
+ * census or QC on the same handle.
+ *
+ * td_rescue_begin: barcut[n_barcut], barnum and tagoff[barnum] (at most 63) as td_set_index takes them, with its errors;
+ *   tags[n_tags] as stored: 1 .. TD_RESCUE_MAX_TAGLEN upper-case ACGT (TD_E_EMPTY / TD_E_LIMIT / TD_E_ALPHABET, the
+ *   tag in td_last_bad_index), none equal to or a prefix of another (TD_E_OVERLAP; of all such pairs the one whose
+ *   later tag comes first, that tag in td_last_bad_index); max_mismatch 1 or 2.  The index: max_mismatch + 1 parts of
+ *   P = min(32, shortest tag / (max_mismatch + 1)) bases at positions [pP, (p + 1)P) of every tag, per part the tags
+ *   sorted by those bases under a hash directory.  TD_E_LIMIT with a message that begins "tag rescue: run" when P < 1 or
+ *   when more tags share one part than the option "rescue_max_run" allows (td_set_option; 0: the built-in 4096).  The
+ *   matrix and the counters start at zero.  A rescue begun before is dropped.
+ * td_rescue_device: one pass over a resident buffer (arguments as td_count_device's).  Asynchronous, accumulates; ONE
+ *   stream in flight per handle.  "max_grid" caps the grid.
+ * td_rescue_file: a whole file, plain, gzip or BGZF, through td_count_file's readers.  Synchronous, accumulates.
+ * td_rescue_stats: out[TD_RESCUE_*], cumulative since td_rescue_begin.  Synchronises.
+ * td_rescue_work: what the passes cost: out[0] directory probes, out[1] tags verified, out[2] P, out[3] the longest
+ *   displacement in a directory.  Synchronises.
+ * td_rescue_fetch: rescued_out[barnum * n_tags] (uint32_t, row b column t) and positions_out[128]; each may be NULL.
+ *   Synchronises.
+ * td_rescue_matrix: the matrix where it lies in device memory, for callers that add it to a count matrix there; good
+ *   until td_rescue_end or the next td_rescue_begin.
+ * td_rescue_end: frees the rescue; TD_E_STATE without one.  td_destroy frees a rescue left open.
+ * Errors: TD_E_NONASCII as the counter's.  After it, and after a td_rescue_file that failed part-way, every call answers
+ *   with that error until td_rescue_begin. */
+enum {
+    TD_RESCUE_READS = 0,        /* read lines looked at                                                   */
+    TD_RESCUE_BARCUT = 1,       /* ... with barcode + cut site                                            */
+    TD_RESCUE_EXACT = 2,        /* ... that equal a tag: the counter's                                    */
+    TD_RESCUE_RESCUED1 = 3,     /* ... one mismatch from exactly one nearest tag                          */
+    TD_RESCUE_RESCUED2 = 4,     /* ... two mismatches from exactly one nearest tag                        */
+    TD_RESCUE_AMBIGUOUS = 5,    /* ... whose smallest distance several tags attain                        */
+    TD_RESCUE_NONE = 6,         /* ... with no tag within max_mismatch                                    */
+    TD_RESCUE_LONGEST_RUN = 7,  /* tags that share one part, at most (known at begin)                     */
+    TD_RESCUE_MAX_TAGLEN = 128
+};
+int td_rescue_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
+                    const char *const *tags, uint32_t n_tags, uint32_t max_mismatch);
+int td_rescue_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream);
+int td_rescue_file(td_handle *h, const char *path, uint64_t max_reads);
+int td_rescue_stats(td_handle *h, uint64_t out[8]);
+int td_rescue_work(td_handle *h, uint64_t out[4]);
+int td_rescue_fetch(td_handle *h, uint32_t *rescued_out, uint64_t *positions_out);
+int td_rescue_matrix(td_handle *h, void **d_matrix);
+int td_rescue_end(td_handle *h);
+
 /* ---- tag network (csrc/tagnet.hip; tagdigger_amd/tagdigger_fun.py tag_network and census_markers drive these) --------
  *
  * From a census to markers without a reference genome (the UNEAK network filter).  Input: n tags of one

@@ -1,0 +1,666 @@
+// Tag rescue: the reads that lie one or two substitutions from a known tag, per barcode and per tag.
+// Per read the rule is the counter's up to the barcode (reference tagdigger_fun.py:250-259: lines as text mode splits
+// them, line k a read when k % 4 == 1, line.strip().upper(), sequence_index_lookup on barcode + cut site); then
+// w = the line from tagoff[b] on, avail = len(w).  A tag t of n bases is a candidate iff n <= avail; d(t) = the positions
+// i < n with w[i] != t[i], a character outside ACGT mismatching every base.  A candidate at d = 0: `exact`, nothing is
+// written (that read is the counter's).  Otherwise m = the smallest d: m <= K and one tag attains it -> rescued[b][t],
+// rescued_at[m], positions[i] for every mismatching i; m <= K and several attain it -> `ambiguous`; else `none`.
+//
+// The index (built on the host in td_rescue_begin).  K + 1 parts of P = min(32, minlen / (K + 1)) bases at positions
+// [pP, (p + 1)P) of every tag: a tag within K substitutions of a window agrees with it on one part at least.  Per part
+// the tag ids sorted by the part's bases, and an open-addressing directory {key, run start, run length}; the tags
+// themselves at 2 bits a base, 32 bytes each, with their lengths.  Nothing in it is written after begin.
+//
+//   k_rescue   one workgroup per 16 KiB tile (the handle's k_count_lines + k_scan_tiles give every tile its line index):
+//              terminator masks -> the tile's read-line starts as a dense list in LDS -> one lane per read:
+//              barcode_lookup (kernels.hpp), the window of up to 128 bases as 2-bit words and a mask of the positions
+//              that hold no base, then per part without a masked position one directory probe and one XOR, pair-fold and
+//              popcount per tag of the run.
+//
+// No lane waits for another: the only shared writes are atomic adds on the matrix, on the workgroup's position
+// histogram in LDS and on the counters.  Every loop is bounded: a directory probe by the longest displacement and a run
+// by the longest run, both known at begin.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#define TD_INST_ONLY                    // (k_scan_tiles is defined in tagdig.hip's translation unit)
+#include "kernels.hpp"
+#include "piece_sink.hpp"
+#include "td_internal.hpp"
+
+namespace tdr {
+using namespace tdk;
+
+constexpr int CPT = 4;                                   // 16-byte chunks per thread: tiles of 16 KiB, as k_count_lines<4> counts them
+constexpr uint32_t TILE = CPT * BLOCK * 16u;
+static_assert(TILE == 16384, "td_line_prefix (tagdig.hip) counts terminators per 16 KiB tile with k_count_lines<4>");
+constexpr uint32_t LIST_CAP = TILE / 4 + 4;              // read-line starts per tile: every fourth terminator, the buffer's own first line
+constexpr uint32_t MAXLEN = TD_RESCUE_MAX_TAGLEN;        // bases of a tag and of the window
+static_assert(MAXLEN == 128, "the window is four 64-bit words");
+constexpr uint32_t NO_TAG = 0xFFFFFFFFu;
+// the rescue's words in device memory, behind the position histogram
+enum { RS_READS = 0, RS_BARCUT = 1, RS_EXACT = 2, RS_RESC1 = 3, RS_RESC2 = 4, RS_AMBIG = 5, RS_NONE = 6, RS_ERR = 7, RS_TOTAL = 8,
+       RS_PROBES = 9, RS_VERIFIED = 10, RS_NWORDS = 16 };
+
+struct RescueParams {
+    const uint8_t *buf;
+    uint64_t nbytes;
+    uint64_t first_line;       // global index of the buffer's first line (+ *cursor_in)
+    uint64_t limit_line;       // last read line that is looked at (maxreads)
+    const uint64_t *prefix;    // [ntiles] FLAG_INC | terminators up to the end of tile t
+    uint32_t ntiles;
+    const uint32_t *bblob;     // barcode + cut site index (the counting path's layout)
+    uint32_t bblob_bytes, off_bmeta, off_bdir;
+    const uint4 *tagw;         // [ntags][2]: the tag's 128 bases as four 64-bit words, first base in the top bits, zero padded
+    const uint32_t *taglen;    // [ntags]
+    const uint4 *dir;          // [nparts][dir_mask + 1] {key lo, key hi, run start, run length}; run length 0: empty
+    const uint32_t *ent;       // [nparts][ntags] tag ids, sorted by the part's bases
+    uint32_t ntags, nparts, P, K;
+    uint32_t dir_mask, max_probe;          // slots - 1 (a power of two); the farthest a key sits from its home slot
+    uint32_t *matrix;          // [barnum][ntags]
+    unsigned long long *positions;         // [128]
+    unsigned long long *rs;    // RS_*
+    const unsigned long long *cursor_in;
+    unsigned long long *cursor_out;
+};
+
+__host__ __device__ inline uint32_t part_hash(uint64_t k) {
+    uint32_t x = ((uint32_t)k * 0x9E3779B1u) ^ ((uint32_t)(k >> 32) * 0x85EBCA77u);
+    x ^= x >> 15; x *= 0x2C1B3C6Du;
+    x ^= x >> 13;
+    return x;
+}
+// the 2 * P bits of bases [s0, s0 + P) of four words that hold 32 bases each, first base in the top bits; s0 + P <= 128
+__host__ __device__ inline uint64_t part_bits(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t w3, uint32_t s0, uint32_t P) {
+    const uint32_t j = s0 >> 5, o = s0 & 31u;
+    const uint64_t hi = j == 0 ? w0 : j == 1 ? w1 : j == 2 ? w2 : w3;
+    const uint64_t lo = j == 0 ? w1 : j == 1 ? w2 : j == 2 ? w3 : 0ull;
+    const uint64_t x = o ? (hi << (2u * o)) | (lo >> (64u - 2u * o)) : hi;
+    return x >> (64u - 2u * P);
+}
+// bases of word w (32 each) that lie below n, as a mask over their bit pairs
+__host__ __device__ inline uint64_t len_mask(uint32_t n, uint32_t w) {
+    if (n <= 32u * w) return 0ull;
+    const uint32_t c = n - 32u * w;
+    return c >= 32u ? ~0ull : ~0ull << (64u - 2u * c);
+}
+// bit k of m (k = 0: the first base) -> bit 62 - 2k
+__device__ __forceinline__ uint64_t spread_mask(uint32_t m) {
+    uint64_t x = __brev(m);
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+// mismatching positions of word w between the window and a tag: bit 62 - 2i for base 32w + i
+__device__ __forceinline__ uint64_t diff_bits(uint64_t win, uint64_t tag, uint64_t mask, uint32_t n, uint32_t w) {
+    const uint64_t x = win ^ tag;
+    return (((x | (x >> 1)) & 0x5555555555555555ull) | mask) & len_mask(n, w);
+}
+
+struct Window {
+    uint64_t w[4];             // the bases, first in the top bits
+    uint64_t m[4];             // bit 62 - 2i of word j: base 32j + i is no ACGT, or lies behind the line's end
+    uint32_t avail;            // min(len(w), 128)
+};
+
+// The line's barcode: gpos moves over the leading blanks (strip), K = its first 32 bases.
+__device__ __forceinline__ bool rescue_barcode(const KParams &kp, const TileCtx &cx, uint64_t &gpos, uint32_t &meta) {
+    while (gpos < kp.nbytes && is_blank(kp.buf[gpos])) gpos++;          // ends at the terminator at the latest
+    const uint32_t a = (uint32_t)(gpos & 15u);
+    const uint64_t g0 = gpos & ~15ull;
+    const uint2 e0 = convert_chunk(load_chunk(kp, g0)), e1 = convert_chunk(load_chunk(kp, g0 + 16)), e2 = convert_chunk(load_chunk(kp, g0 + 32));
+    const uint64_t inv = ((((uint64_t)e2.y << 32) | ((uint64_t)e1.y << 16) | e0.y) >> a) | (1ull << 32);
+    const uint32_t nvalid = (uint32_t)__builtin_ctzll(inv);
+    const uint32_t r0 = (uint32_t)((((uint64_t)e0.x << 32) | e1.x) >> (32u - 2u * a));
+    const uint32_t r1 = (uint32_t)((((uint64_t)e1.x << 32) | e2.x) >> (32u - 2u * a));
+    return barcode_lookup(cx.L_bval, cx.L_bmeta, cx.L_bdir, ((uint64_t)r0 << 32) | r1, nvalid, meta);
+}
+
+// The window from absolute position ws on, which lies inside the line or on its terminator.
+__device__ __forceinline__ void rescue_window(const KParams &kp, uint64_t ws, Window &W) {
+    const uint32_t a = (uint32_t)(ws & 15u);
+    const uint64_t g0 = ws & ~15ull;
+    uint32_t codes[10], inv[10], term[10];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const uint4 v = load_chunk(kp, g0 + 16ull * i);
+        const uint2 e = convert_chunk(v);
+        codes[i] = e.x; inv[i] = e.y;
+        term[i] = eq_mask16(v, 0x0A0A0A0Au) | eq_mask16(v, 0x0D0D0D0Du);
+    }
+    codes[9] = 0; inv[9] = 0; term[9] = 0;
+    uint32_t m32[4], t32[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        m32[j] = (uint32_t)(((((uint64_t)inv[2 * j + 2]) << 32) | (inv[2 * j + 1] << 16) | inv[2 * j]) >> a);
+        t32[j] = (uint32_t)(((((uint64_t)term[2 * j + 2]) << 32) | (term[2 * j + 1] << 16) | term[2 * j]) >> a);
+        const uint32_t r0 = (uint32_t)((((uint64_t)codes[2 * j] << 32) | codes[2 * j + 1]) >> (32u - 2u * a));
+        const uint32_t r1 = (uint32_t)((((uint64_t)codes[2 * j + 1] << 32) | codes[2 * j + 2]) >> (32u - 2u * a));
+        W.w[j] = ((uint64_t)r0 << 32) | r1;
+    }
+    // where the line ends inside the window: its terminator, or the buffer's end
+    uint32_t q = MAXLEN;
+#pragma unroll
+    for (int j = 3; j >= 0; j--) if (t32[j]) q = 32u * j + (uint32_t)__builtin_ctz(t32[j]);
+    const uint64_t room = kp.nbytes - ws;
+    const uint32_t end = room < q ? (uint32_t)room : q;
+    uint64_t e = ws + end;
+    // strip: blanks before the end do not belong to the line.  Its last byte is a base in every read but a few
+    bool flagged = false;
+    if (end) {
+        const uint32_t k = end - 1u;
+        const uint32_t mw = (k >> 5) == 0 ? m32[0] : (k >> 5) == 1 ? m32[1] : (k >> 5) == 2 ? m32[2] : m32[3];
+        flagged = (mw >> (k & 31u)) & 1u;
+    }
+    if (flagged) {
+        if (end == MAXLEN) while (e < kp.nbytes && kp.buf[e] != 0x0Au && kp.buf[e] != 0x0Du) e++;      // the line goes on behind the window
+        while (e > ws && is_blank(kp.buf[e - 1])) e--;
+    }
+    const uint32_t avail = e - ws < MAXLEN ? (uint32_t)(e - ws) : MAXLEN;
+    W.avail = avail;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (avail < 32u * (j + 1)) m32[j] |= avail <= 32u * j ? ~0u : ~0u << (avail - 32u * j);
+        W.m[j] = spread_mask(m32[j]);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_rescue(const RescueParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint16_t L_mask[CPT * BLOCK];
+    __shared__ uint16_t L_list[LIST_CAP];
+    __shared__ uint32_t L_misc[16];
+    __shared__ uint32_t L_pos[MAXLEN];
+    const unsigned long long *L_bval = reinterpret_cast<const unsigned long long *>(lds);
+    const uint32_t *L_bmeta = reinterpret_cast<const uint32_t *>(lds + p.off_bmeta);
+    const uint16_t *L_bdir = reinterpret_cast<const uint16_t *>(lds + p.off_bdir);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (uint32_t i = tid; i < p.bblob_bytes / 4; i += BLOCK) reinterpret_cast<uint32_t *>(lds)[i] = p.bblob[i];
+    if (tid < (int)MAXLEN) L_pos[tid] = 0;
+    KParams kp{};
+    kp.buf = p.buf; kp.nbytes = p.nbytes;
+    TileCtx cx{};
+    cx.L_bval = L_bval; cx.L_bmeta = L_bmeta; cx.L_bdir = L_bdir;
+    const unsigned long long cin = p.cursor_in ? *p.cursor_in : 0ull;
+    const uint64_t fl = p.first_line + cin;
+    if (blockIdx.x == 0 && tid == 0 && p.cursor_out) *p.cursor_out = cin + p.rs[RS_TOTAL];
+    unsigned long long st_reads = 0, st_bar = 0, st_exact = 0, st_r1 = 0, st_r2 = 0, st_ambig = 0, st_none = 0, st_probes = 0, st_verified = 0;
+    const uint32_t dir_slots = p.dir_mask + 1u;
+
+    for (uint32_t t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
+        const uint64_t tbase = (uint64_t)t * TILE;
+        __syncthreads();
+        if (tid == 0) L_misc[9] = 0;
+        uint32_t hiacc = 0;
+#pragma unroll
+        for (int j = 0; j < CPT; j++) {
+            const uint32_t c = j * BLOCK + tid;
+            const uint64_t g = tbase + (uint64_t)c * 16u;
+            const uint4 v = load_chunk(kp, g);
+            hiacc |= v.x | v.y | v.z | v.w;
+            uint32_t nl = eq_mask16(v, 0x0A0A0A0Au), cr = eq_mask16(v, 0x0D0D0D0Du);
+            uint32_t term = nl | (cr & ~(nl >> 1));
+            if (cr & 0x8000u) { const uint64_t nx = g + 16; if (nx < p.nbytes && p.buf[nx] == 0x0A) term &= 0x7FFFu; }
+            if (g + 16 > p.nbytes) term &= g < p.nbytes ? ((1u << (uint32_t)(p.nbytes - g)) - 1u) : 0u;
+            L_mask[c] = (uint16_t)term;
+        }
+        __syncthreads();
+        if (hiacc & 0x80808080u) L_misc[9] = 1;
+        uint32_t mm[CPT / 2];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int i = 0; i < CPT / 2; i++) {
+            mm[i] = reinterpret_cast<const uint32_t *>(L_mask)[tid * (CPT / 2) + i];
+            cnt += __builtin_popcount(mm[i]);
+        }
+        const uint32_t incl = wave_incl_scan(cnt, lane);
+        if (lane == 63) L_misc[wave] = incl;
+        __syncthreads();
+        uint32_t wbase = 0, tile_terms = 0;
+        for (int w = 0; w < BLOCK / 64; w++) { if (w < wave) wbase += L_misc[w]; tile_terms += L_misc[w]; }
+        const bool tile_has_hi = L_misc[9] != 0;
+        // terminators before this tile: the previous tile's inclusive prefix.  The line behind the buffer's j-th
+        // terminator has index fl + j; this tile holds terminators P + 1 .. P + tile_terms
+        const uint64_t P = t ? (p.prefix[t - 1] & ~FLAG_INC) : 0ull;
+        const uint64_t j0 = P + 1 + ((1 - (fl + P + 1)) & 3);                        // the first of them that a read line follows
+        const uint32_t nlist = P + tile_terms >= j0 ? (uint32_t)((P + tile_terms - j0) >> 2) + 1u : 0u;
+        const bool own_first = t == 0 && (fl & 3) == 1;                             // the buffer's own first line is a read
+        uint64_t ord = P + wbase + incl - cnt;                                       // terminators before this thread's span
+        const uint64_t ord0 = ord;
+        const uint32_t span0 = tid * CPT * 16u;
+#pragma unroll
+        for (int k = 0; k < CPT / 2; k++) {
+            uint32_t m = mm[k];
+            while (m) {
+                const uint32_t bit = __builtin_ctz(m);
+                m &= m - 1;
+                ord++;
+                if (((fl + ord) & 3) == 1) {
+                    const uint32_t pos = span0 + 32u * k + bit + 1u;                 // (<= TILE: the line may start the next tile)
+                    L_list[(ord - j0) >> 2] = tbase + pos < p.nbytes ? (uint16_t)pos : (uint16_t)0xFFFFu;
+                }
+            }
+        }
+        if (own_first && tid == 0) L_list[nlist] = 0;
+        __syncthreads();
+
+        // ---------------- one lane per read line
+        const uint32_t ntot = nlist + (own_first ? 1u : 0u);
+        for (uint32_t base = 0; base < ntot; base += BLOCK) {
+            const uint32_t i = base + tid;
+            if (i >= ntot) continue;
+            const uint32_t pos = L_list[i];
+            const uint64_t line = i < nlist ? fl + j0 + 4ull * i : fl;
+            if (pos == 0xFFFFu || line > p.limit_line) continue;
+            st_reads++;
+            uint64_t gpos = tbase + pos;
+            uint32_t meta = 0;
+            if (!rescue_barcode(kp, cx, gpos, meta)) continue;
+            st_bar++;
+            const uint32_t blen = meta & 63u, off = (meta >> 6) & 63u, row = meta >> 16;
+            uint64_t ws = gpos + off;
+            // (an offset behind the barcode entry -- the C-ABI takes one -- may lie behind the line's end: then w is empty)
+            for (uint64_t g = gpos + blen; g < gpos + off; g++)
+                if (g >= p.nbytes || p.buf[g] == 0x0Au || p.buf[g] == 0x0Du) { ws = g; break; }
+            Window W;
+            rescue_window(kp, ws, W);
+            if (ws != gpos + off) W.avail = 0;
+
+            uint32_t best_d = 0xFFu, best_t = NO_TAG;
+            bool tied = false, exact = false;
+            for (uint32_t part = 0; part < p.nparts && !exact; part++) {
+                const uint32_t s0 = part * p.P;
+                if (s0 + p.P > W.avail) break;                                       // (no tag this short: every later part lies behind it too)
+                if (part_bits(W.m[0], W.m[1], W.m[2], W.m[3], s0, p.P)) continue;    // a part that holds no base cannot be intact
+                const uint64_t key = part_bits(W.w[0], W.w[1], W.w[2], W.w[3], s0, p.P);
+                st_probes++;
+                const uint4 *dir = p.dir + (uint64_t)part * dir_slots;
+                uint32_t slot = part_hash(key) & p.dir_mask, start = 0, len = 0;
+                for (uint32_t n = 0; n <= p.max_probe; n++) {
+                    const uint4 s = dir[slot];
+                    if (s.w == 0) break;
+                    if (s.x == (uint32_t)key && s.y == (uint32_t)(key >> 32)) { start = s.z; len = s.w; break; }
+                    slot = (slot + 1u) & p.dir_mask;
+                }
+                const uint32_t *ent = p.ent + (uint64_t)part * p.ntags + start;
+                for (uint32_t r = 0; r < len; r++) {
+                    const uint32_t tg = ent[r];
+                    const uint32_t n = p.taglen[tg];
+                    if (n > W.avail || tg == best_t) continue;                       // no candidate; or reached through an earlier part already
+                    st_verified++;
+                    const uint4 a = p.tagw[2ull * tg];
+                    uint32_t d = __builtin_popcountll(diff_bits(W.w[0], ((uint64_t)a.y << 32) | a.x, W.m[0], n, 0)) +
+                                 __builtin_popcountll(diff_bits(W.w[1], ((uint64_t)a.w << 32) | a.z, W.m[1], n, 1));
+                    if (n > 64u) {
+                        const uint4 b = p.tagw[2ull * tg + 1];
+                        d += __builtin_popcountll(diff_bits(W.w[2], ((uint64_t)b.y << 32) | b.x, W.m[2], n, 2)) +
+                             __builtin_popcountll(diff_bits(W.w[3], ((uint64_t)b.w << 32) | b.z, W.m[3], n, 3));
+                    }
+                    if (d == 0) { exact = true; break; }
+                    if (d > p.K) continue;
+                    if (d < best_d) { best_d = d; best_t = tg; tied = false; }
+                    else if (d == best_d) tied = true;
+                }
+            }
+            if (exact) st_exact++;
+            else if (best_t == NO_TAG) st_none++;
+            else if (tied) st_ambig++;
+            else {
+                if (best_d == 1) st_r1++; else st_r2++;
+                atomicAdd(p.matrix + (uint64_t)row * p.ntags + best_t, 1u);
+                const uint32_t n = p.taglen[best_t];
+                const uint4 a = p.tagw[2ull * best_t], b = p.tagw[2ull * best_t + 1];
+                const uint64_t T[4] = {((uint64_t)a.y << 32) | a.x, ((uint64_t)a.w << 32) | a.z, ((uint64_t)b.y << 32) | b.x, ((uint64_t)b.w << 32) | b.z};
+#pragma unroll
+                for (int w = 0; w < 4; w++) {
+                    uint64_t bits = diff_bits(W.w[w], T[w], W.m[w], n, w);
+                    while (bits) {
+                        const uint32_t lz = (uint32_t)__builtin_clzll(bits);
+                        bits &= ~(1ull << (63u - lz));
+                        atomicAdd(&L_pos[32u * w + (lz >> 1)], 1u);
+                    }
+                }
+            }
+        }
+
+        // ---------------- rare: bytes >= 0x80 in the tile -- are any inside a read line that is looked at?  (k_count's rule)
+        if (tile_has_hi) {
+            const uint64_t Lb = fl + ord0;               // index of the line this thread's span starts in
+            uint32_t seen = 0;
+#pragma unroll
+            for (int k = 0; k < CPT / 2; k++) {
+                const uint32_t m = mm[k];
+#pragma nounroll
+                for (uint32_t q = 0; q < 32u; q++) {
+                    const uint64_t g = tbase + span0 + 32u * k + q;
+                    if (g < p.nbytes && p.buf[g] >= 0x80u) {
+                        const uint64_t line = Lb + seen;
+                        if ((line & 3) == 1 && line <= p.limit_line) atomicOr(p.rs + RS_ERR, ERR_NONASCII);
+                    }
+                    seen += (m >> q) & 1u;
+                }
+            }
+        }
+        // the tile's share of the position histogram (a tile holds fewer than 2^13 reads: no cell wraps)
+        __syncthreads();
+        if (tid < (int)MAXLEN) {
+            const uint32_t v = L_pos[tid];
+            if (v) { L_pos[tid] = 0; atomicAdd(p.positions + tid, (unsigned long long)v); }
+        }
+    }
+    const unsigned long long sums[9] = {wave_sum64(st_reads), wave_sum64(st_bar), wave_sum64(st_exact), wave_sum64(st_r1), wave_sum64(st_r2),
+                                        wave_sum64(st_ambig), wave_sum64(st_none), wave_sum64(st_probes), wave_sum64(st_verified)};
+    if (lane == 0) {
+        const int at[9] = {RS_READS, RS_BARCUT, RS_EXACT, RS_RESC1, RS_RESC2, RS_AMBIG, RS_NONE, RS_PROBES, RS_VERIFIED};
+#pragma unroll
+        for (int k = 0; k < 9; k++) if (sums[k]) atomicAdd(p.rs + at[k], sums[k]);
+    }
+}
+
+}  // namespace tdr
+
+// ============================================================================ host side
+namespace {
+
+constexpr size_t RESCUE_LDS_INDEX = 40 * 1024;            // the barcode index's share of a workgroup's LDS, as the census's
+// The longest run of tags under one part key that the device takes.  Every tag of a run is verified by the lane that
+// reached it, so a run costs its length per read.  A GUESS: the sweep that would set it where one pass costs what the
+// host rule costs has not been measured.
+constexpr uint32_t RESCUE_DEFAULT_MAX_RUN = 4096;
+
+struct Rescue {
+    td_handle *h = nullptr;
+    uint32_t barnum = 0, ntags = 0, K = 0, P = 0, bblob_bytes = 0, off_bmeta = 0, off_bdir = 0;
+    uint32_t dir_mask = 0, max_probe = 0, longest_run = 0;
+    tdi::DevBuf<uint32_t> d_bblob, d_taglen, d_ent, d_matrix;
+    tdi::DevBuf<uint4> d_tagw, d_dir;
+    tdi::DevBuf<unsigned long long> d_words;  // positions[128] | RS_*
+    bool used = false;                        // something has been added since td_rescue_begin
+    int dead = 0;                             // the code every call answers with after a failure, until td_rescue_begin
+    std::string dead_msg;
+    size_t cells() const { return (size_t)barnum * ntags; }
+    unsigned long long *d_pos() const { return d_words.p; }
+    unsigned long long *d_rs() const { return d_words.p + tdr::MAXLEN; }
+};
+
+Rescue *rescue_of(td_handle *h) { return h ? (Rescue *)*td_handle_rescue(h) : nullptr; }
+
+int rescue_zero(Rescue *r, hipStream_t s) {
+    TD_HIPCHK(hipMemsetAsync(r->d_matrix.p, 0, std::max<size_t>(r->cells(), 1) * 4, s));
+    TD_HIPCHK(hipMemsetAsync(r->d_words.p, 0, (tdr::MAXLEN + tdr::RS_NWORDS) * 8, s));
+    TD_HIPCHK(hipStreamSynchronize(s));
+    r->used = false;
+    return TD_OK;
+}
+
+int rescue_launch(Rescue *r, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, hipStream_t stream,
+                  const unsigned long long *cursor_in, unsigned long long *cursor_out) {
+    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
+    if (((uintptr_t)d_fastq & 15) != 0) return td_fail_internal(TD_E_ARG, "device FASTQ pointer must be 16-byte aligned");
+    if (nbytes == 0) return TD_OK;
+    if (max_reads == 0) max_reads = 1;
+    r->used = true;
+    const uint64_t *prefix = nullptr;
+    int rc = td_line_prefix(r->h, d_fastq, nbytes, (void *)stream, &prefix, r->d_rs() + tdr::RS_TOTAL); if (rc) return rc;
+    tdr::RescueParams p{};
+    p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
+    // last read line that is looked at: ordinal r (1-based) sits on line 4 (r - 1) + 1
+    p.limit_line = max_reads >= (1ull << 60) ? ~0ull - 8 : 4 * (max_reads - 1) + 1;
+    p.prefix = prefix; p.ntiles = (uint32_t)((nbytes + tdr::TILE - 1) / tdr::TILE);
+    p.bblob = r->d_bblob.p; p.bblob_bytes = r->bblob_bytes; p.off_bmeta = r->off_bmeta; p.off_bdir = r->off_bdir;
+    p.tagw = r->d_tagw.p; p.taglen = r->d_taglen.p; p.dir = r->d_dir.p; p.ent = r->d_ent.p;
+    p.ntags = r->ntags; p.nparts = r->K + 1; p.P = r->P; p.K = r->K; p.dir_mask = r->dir_mask; p.max_probe = r->max_probe;
+    p.matrix = r->d_matrix.p; p.positions = r->d_pos(); p.rs = r->d_rs();
+    p.cursor_in = cursor_in; p.cursor_out = cursor_out;
+    uint32_t grid = (uint32_t)std::min<uint64_t>(p.ntiles, (uint64_t)td_handle_num_cu(r->h) * 8);
+    const uint32_t cap = td_handle_max_grid(r->h);
+    if (cap) grid = std::min(grid, cap);
+    hipLaunchKernelGGL(tdr::k_rescue, dim3(grid), dim3(tdk::BLOCK), r->bblob_bytes, stream, p);
+    TD_HIPCHK(hipGetLastError());
+    return TD_OK;
+}
+
+// after a synchronisation: what the kernel flagged
+int rescue_sync_stats(Rescue *r, unsigned long long rs[tdr::RS_NWORDS]) {
+    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
+    TD_HIPCHK(hipDeviceSynchronize());
+    TD_HIPCHK(hipMemcpy(rs, r->d_rs(), tdr::RS_NWORDS * 8, hipMemcpyDeviceToHost));
+    if (rs[tdr::RS_ERR] & tdk::ERR_NONASCII) {
+        r->dead = TD_E_NONASCII; r->dead_msg = "non-ASCII byte in a sequence line";
+        return td_fail_internal(r->dead, r->dead_msg.c_str());
+    }
+    return TD_OK;
+}
+
+int sink_piece(void *ctx, const void *d, uint64_t n, uint64_t first_line, uint64_t max_reads, hipStream_t s, const unsigned long long *cin,
+               unsigned long long *cout) {
+    return rescue_launch((Rescue *)ctx, d, n, first_line, max_reads, s, cin, cout);
+}
+int sink_restart(void *ctx) { Rescue *r = (Rescue *)ctx; return rescue_zero(r, (hipStream_t)td_handle_work_stream(r->h)); }
+
+int state_error(td_handle *h, bool args_ok) {
+    return td_fail_internal(h && args_ok ? TD_E_STATE : TD_E_ARG, h && args_ok ? "td_rescue_begin has not been called" : "NULL argument");
+}
+
+// What td_rescue_begin builds on the host.  No HIP in here.
+struct RescueIndex {
+    uint32_t P = 0, longest_run = 0, dir_slots = 0, max_probe = 0;
+    std::vector<uint64_t> words;              // [ntags][4]
+    std::vector<uint32_t> lens;               // [ntags]
+    std::vector<uint32_t> ent;                // [nparts][ntags]
+    std::vector<uint32_t> dir;                // [nparts][dir_slots][4]
+};
+
+// tags: 1 .. 128 upper-case ACGT, none equal to or a prefix of another
+int rescue_check_tags(const char *const *tags, uint32_t n_tags, std::vector<std::string> &ts) {
+    if (n_tags == 0) return td_fail_internal(TD_E_EMPTY, "empty tag list");
+    ts.resize(n_tags);
+    for (uint32_t i = 0; i < n_tags; i++) {
+        if (!tags[i]) return td_fail_internal(TD_E_ARG, "NULL argument");
+        ts[i] = tags[i];
+        if (ts[i].empty()) { td_set_bad_index(i); return td_fail_internal(TD_E_EMPTY, "empty tag"); }
+        if (ts[i].size() > TD_RESCUE_MAX_TAGLEN) { td_set_bad_index(i); return td_fail_internal(TD_E_LIMIT, "tag longer than 128 bases"); }
+        for (char c : ts[i])
+            if (c != 'A' && c != 'C' && c != 'G' && c != 'T') { td_set_bad_index(i); return td_fail_internal(TD_E_ALPHABET, "tags must be upper-case ACGT"); }
+    }
+    // sorted, the tags that begin the current one form a chain: the stack.  The pair reported is the one whose later
+    // tag comes first in the input
+    std::vector<uint32_t> order(n_tags);
+    for (uint32_t i = 0; i < n_tags; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { const int c = ts[a].compare(ts[b]); return c < 0 || (c == 0 && a < b); });
+    std::vector<std::pair<uint32_t, uint32_t>> stack;        // (tag, the smallest input position on the stack up to here)
+    uint32_t bad = 0xFFFFFFFFu;
+    for (uint32_t k : order) {
+        while (!stack.empty() && ts[k].compare(0, ts[stack.back().first].size(), ts[stack.back().first]) != 0) stack.pop_back();
+        uint32_t low = k;
+        if (!stack.empty()) { bad = std::min(bad, std::max(k, stack.back().second)); low = std::min(low, stack.back().second); }
+        stack.emplace_back(k, low);
+    }
+    if (bad != 0xFFFFFFFFu) { td_set_bad_index(bad); return td_fail_internal(TD_E_OVERLAP, "a tag equals another or begins it"); }
+    return TD_OK;
+}
+
+int rescue_build_index(const std::vector<std::string> &ts, uint32_t K, uint32_t max_run, RescueIndex &ix) {
+    const uint32_t n = (uint32_t)ts.size(), nparts = K + 1;
+    size_t minlen = ts[0].size();
+    for (auto &t : ts) minlen = std::min(minlen, t.size());
+    ix.P = (uint32_t)std::min<size_t>(32, minlen / nparts);
+    if (ix.P < 1)
+        return td_fail_internal(TD_E_LIMIT, ("tag rescue: run of all " + std::to_string(n) + " tags: the shortest tag has " + std::to_string(minlen) +
+                                             " bases, which leaves no part for " + std::to_string(K) + " mismatches").c_str());
+    ix.words.assign((size_t)n * 4, 0);
+    ix.lens.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        ix.lens[i] = (uint32_t)ts[i].size();
+        for (size_t q = 0; q < ts[i].size(); q++) {
+            const char c = ts[i][q];
+            const uint64_t code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'T' ? 2 : 3;       // (byte >> 1) & 3, as convert_chunk packs a read
+            ix.words[(size_t)i * 4 + (q >> 5)] |= code << (62 - 2 * (q & 31));
+        }
+    }
+    ix.dir_slots = 16;
+    while (ix.dir_slots < 2ull * n) ix.dir_slots <<= 1;
+    ix.ent.resize((size_t)nparts * n);
+    ix.dir.assign((size_t)nparts * ix.dir_slots * 4, 0);
+    std::vector<std::pair<uint64_t, uint32_t>> keyed(n);
+    for (uint32_t part = 0; part < nparts; part++) {
+        for (uint32_t i = 0; i < n; i++) {
+            const uint64_t *w = &ix.words[(size_t)i * 4];
+            keyed[i] = {tdr::part_bits(w[0], w[1], w[2], w[3], part * ix.P, ix.P), i};
+        }
+        std::sort(keyed.begin(), keyed.end());
+        uint32_t *dir = &ix.dir[(size_t)part * ix.dir_slots * 4];
+        for (uint32_t i = 0; i < n;) {
+            uint32_t j = i;
+            while (j < n && keyed[j].first == keyed[i].first) { ix.ent[(size_t)part * n + j] = keyed[j].second; j++; }
+            ix.longest_run = std::max(ix.longest_run, j - i);
+            uint32_t slot = tdr::part_hash(keyed[i].first) & (ix.dir_slots - 1), hops = 0;
+            while (dir[slot * 4 + 3]) { slot = (slot + 1) & (ix.dir_slots - 1); hops++; }
+            dir[slot * 4] = (uint32_t)keyed[i].first; dir[slot * 4 + 1] = (uint32_t)(keyed[i].first >> 32);
+            dir[slot * 4 + 2] = i; dir[slot * 4 + 3] = j - i;
+            ix.max_probe = std::max(ix.max_probe, hops);
+            i = j;
+        }
+    }
+    if (ix.longest_run > max_run)
+        return td_fail_internal(TD_E_LIMIT, ("tag rescue: run of " + std::to_string(ix.longest_run) + " tags share one part of " + std::to_string(ix.P) +
+                                             " bases, rescue_max_run is " + std::to_string(max_run)).c_str());
+    return TD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void td_rescue_release(td_handle *h) {
+    void **slot = td_handle_rescue(h);
+    delete (Rescue *)*slot;
+    *slot = nullptr;
+}
+
+int td_rescue_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
+                    const char *const *tags, uint32_t n_tags, uint32_t max_mismatch) {
+    if (!h || !barcut || !tagoff || !tags) return td_fail_internal(TD_E_ARG, "NULL argument");
+    if (max_mismatch < 1 || max_mismatch > 2) return td_fail_internal(TD_E_ARG, "max_mismatch must be 1 or 2");
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipDeviceSynchronize());
+    td_rescue_release(h);
+    uint8_t *blob = nullptr;
+    uint32_t bytes = 0, off_bmeta = 0, off_bdir = 0;
+    int rc = td_barcut_blob(barcut, n_barcut, barnum, tagoff, &blob, &bytes, &off_bmeta, &off_bdir);
+    if (rc) return rc;
+    std::vector<uint8_t> bblob(blob, blob + bytes);
+    free(blob);
+    if (bytes > RESCUE_LDS_INDEX) return td_fail_internal(TD_E_LIMIT, "barcode index does not fit the LDS budget");
+    std::vector<std::string> ts;
+    rc = rescue_check_tags(tags, n_tags, ts); if (rc) return rc;
+    const uint32_t opt = td_handle_rescue_max_run(h);
+    RescueIndex ix;
+    rc = rescue_build_index(ts, max_mismatch, opt ? opt : RESCUE_DEFAULT_MAX_RUN, ix); if (rc) return rc;
+    if ((uint64_t)barnum * n_tags >= (1ull << 32)) return td_fail_internal(TD_E_LIMIT, "rescue matrix beyond 2^32 cells");
+
+    Rescue *r = new Rescue();
+    r->h = h; r->barnum = barnum; r->ntags = n_tags; r->K = max_mismatch; r->P = ix.P;
+    r->bblob_bytes = bytes; r->off_bmeta = off_bmeta; r->off_bdir = off_bdir;
+    r->dir_mask = ix.dir_slots - 1; r->max_probe = ix.max_probe; r->longest_run = ix.longest_run;
+    hipError_t e = r->d_bblob.alloc((bytes + 3) / 4);
+    if (e == hipSuccess) e = hipMemcpy(r->d_bblob.p, bblob.data(), bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = r->d_tagw.alloc(ix.words.size() / 2);
+    if (e == hipSuccess) e = hipMemcpy(r->d_tagw.p, ix.words.data(), ix.words.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = r->d_taglen.alloc(ix.lens.size());
+    if (e == hipSuccess) e = hipMemcpy(r->d_taglen.p, ix.lens.data(), ix.lens.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = r->d_ent.alloc(ix.ent.size());
+    if (e == hipSuccess) e = hipMemcpy(r->d_ent.p, ix.ent.data(), ix.ent.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = r->d_dir.alloc(ix.dir.size() / 4);
+    if (e == hipSuccess) e = hipMemcpy(r->d_dir.p, ix.dir.data(), ix.dir.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = r->d_matrix.alloc(r->cells());
+    if (e == hipSuccess) e = r->d_words.alloc(tdr::MAXLEN + tdr::RS_NWORDS);
+    if (e != hipSuccess) { delete r; (void)hipGetLastError(); return td_fail_internal(TD_E_HIP, hipGetErrorString(e)); }
+    rc = rescue_zero(r, (hipStream_t)td_handle_work_stream(h));
+    if (rc) { delete r; return rc; }
+    *td_handle_rescue(h) = r;
+    return TD_OK;
+}
+
+int td_rescue_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream) {
+    Rescue *r = rescue_of(h);
+    if (!r) return state_error(h, true);
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    return rescue_launch(r, d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
+}
+
+int td_rescue_file(td_handle *h, const char *path, uint64_t max_reads) {
+    Rescue *r = rescue_of(h);
+    if (!r || !path) return state_error(h, path != nullptr);
+    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
+    const td_piece_sink sink{sink_piece, sink_restart, r, !r->used};
+    int rc = td_stream_file(h, path, max_reads, &sink);
+    if (rc) {
+        if (r->used && !r->dead) {            // the matrix holds a part of the file: never handed out
+            r->dead = rc; r->dead_msg = td_last_error();
+        }
+        return rc;
+    }
+    unsigned long long rs[tdr::RS_NWORDS];
+    return rescue_sync_stats(r, rs);
+}
+
+int td_rescue_stats(td_handle *h, uint64_t out[8]) {
+    Rescue *r = rescue_of(h);
+    if (!r || !out) return state_error(h, out != nullptr);
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    unsigned long long rs[tdr::RS_NWORDS];
+    const int rc = rescue_sync_stats(r, rs); if (rc) return rc;
+    out[TD_RESCUE_READS] = rs[tdr::RS_READS]; out[TD_RESCUE_BARCUT] = rs[tdr::RS_BARCUT]; out[TD_RESCUE_EXACT] = rs[tdr::RS_EXACT];
+    out[TD_RESCUE_RESCUED1] = rs[tdr::RS_RESC1]; out[TD_RESCUE_RESCUED2] = rs[tdr::RS_RESC2]; out[TD_RESCUE_AMBIGUOUS] = rs[tdr::RS_AMBIG];
+    out[TD_RESCUE_NONE] = rs[tdr::RS_NONE]; out[TD_RESCUE_LONGEST_RUN] = r->longest_run;
+    return TD_OK;
+}
+
+int td_rescue_work(td_handle *h, uint64_t out[4]) {
+    Rescue *r = rescue_of(h);
+    if (!r || !out) return state_error(h, out != nullptr);
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    unsigned long long rs[tdr::RS_NWORDS];
+    const int rc = rescue_sync_stats(r, rs); if (rc) return rc;
+    out[0] = rs[tdr::RS_PROBES]; out[1] = rs[tdr::RS_VERIFIED]; out[2] = r->P; out[3] = r->max_probe;
+    return TD_OK;
+}
+
+int td_rescue_fetch(td_handle *h, uint32_t *rescued_out, uint64_t *positions_out) {
+    Rescue *r = rescue_of(h);
+    if (!r) return state_error(h, true);
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    unsigned long long rs[tdr::RS_NWORDS];
+    const int rc = rescue_sync_stats(r, rs); if (rc) return rc;
+    if (rescued_out && r->cells()) TD_HIPCHK(hipMemcpy(rescued_out, r->d_matrix.p, r->cells() * 4, hipMemcpyDeviceToHost));
+    if (positions_out) TD_HIPCHK(hipMemcpy(positions_out, r->d_pos(), tdr::MAXLEN * 8, hipMemcpyDeviceToHost));
+    return TD_OK;
+}
+
+int td_rescue_matrix(td_handle *h, void **d_matrix) {
+    Rescue *r = rescue_of(h);
+    if (!r || !d_matrix) return state_error(h, d_matrix != nullptr);
+    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
+    *d_matrix = r->d_matrix.p;
+    return TD_OK;
+}
+
+int td_rescue_end(td_handle *h) {
+    if (!h) return td_fail_internal(TD_E_ARG, "handle is NULL");
+    if (!rescue_of(h)) return td_fail_internal(TD_E_STATE, "td_rescue_begin has not been called");
+    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
+    TD_HIPCHK(hipDeviceSynchronize());
+    td_rescue_release(h);
+    return TD_OK;
+}
+
+}  // extern "C"

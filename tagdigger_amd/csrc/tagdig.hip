@@ -146,6 +146,8 @@ struct td_handle {
     void *census = nullptr;                   // csrc/census.hip's state (td_census_begin .. td_census_end)
     void *qc = nullptr;                       // csrc/qc.hip's state (td_qc_begin .. td_qc_end)
     void *places = nullptr;                   // csrc/place.hip's list of the places alive (td_place_sites .. td_place_free)
+    void *rescue = nullptr;                   // csrc/rescue.hip's state (td_rescue_begin .. td_rescue_end)
+    uint32_t rescue_max_run = 0;              // td_rescue_begin: the longest run of tags under one part key it takes; 0 = the built-in value
     uint32_t qc_flush_tiles = 0;              // (tests: tiles between two merges of k_qc's LDS tables; 0 = the built-in 4096)
     int num_cu = 256;
     // index
@@ -690,6 +692,9 @@ extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_c
 // for csrc/place.hip (hidden): its list's place on the handle, and the "place_max_compares" option
 extern "C" __attribute__((visibility("hidden"))) void **td_handle_places(td_handle *h) { return &h->places; }
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_place_max_compares(const td_handle *h) { return h->place_max_compares; }
+// for csrc/rescue.hip (hidden): its state's place on the handle, and the "rescue_max_run" option
+extern "C" __attribute__((visibility("hidden"))) void **td_handle_rescue(td_handle *h) { return &h->rescue; }
+extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_rescue_max_run(const td_handle *h) { return h->rescue_max_run; }
 extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx) { g_bad = idx; }
 // every launch enqueued through this handle (they may be on its own streams) has finished
 extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_handle *h) {
@@ -769,6 +774,7 @@ void td_destroy(td_handle *h) {
     td_census_release(h);
     td_qc_release(h);
     td_place_release(h);
+    td_rescue_release(h);
     delete h;
 }
 
@@ -2662,6 +2668,7 @@ int td_set_option(td_handle *h, const char *name, int64_t value) {
     else if (n == "tagnet_max_compares") { if (value < 0) return fail(TD_E_ARG, "tagnet_max_compares: 0 or more"); h->tagnet_max_compares = (uint64_t)value; }
     else if (n == "gz_gpu_terr_kb") { if (value < 16 || value > 4096) return fail(TD_E_ARG, "gz_gpu_terr_kb: 16..4096"); h->gz_gpu_terr_kb = (uint32_t)value; }
     else if (n == "place_max_compares") { if (value < 0) return fail(TD_E_ARG, "place_max_compares: 0 or more"); h->place_max_compares = (uint64_t)value; }
+    else if (n == "rescue_max_run") { if (value < 0) return fail(TD_E_ARG, "rescue_max_run: 0 or more"); h->rescue_max_run = (uint32_t)std::min<int64_t>(value, 0x7FFFFFFF); }
     else if (n == "gz_gpu_release") { h->gzgpu.reset(new td_handle::GzGpu()); }
     else if (n == "gz_gpu_verify") h->gz_gpu_verify = value ? 1 : 0;
     else if (n == "gz_gpu_seg_kb") { if (value < 64 || value > (4 << 20)) return fail(TD_E_ARG, "gz_gpu_seg_kb: 64..4194304"); h->gz_gpu_seg_kb = (uint32_t)value; }

@@ -51,6 +51,11 @@ TD_HIDDEN void **td_handle_places(td_handle *h);
 TD_HIDDEN uint64_t td_handle_place_max_compares(const td_handle *h);
 // place.hip, for td_destroy: frees every place the handle still owns
 TD_HIDDEN void td_place_release(td_handle *h);
+// tagdig.hip, for rescue.hip: the rescue's place on the handle; the option "rescue_max_run" (0: not set)
+TD_HIDDEN void **td_handle_rescue(td_handle *h);
+TD_HIDDEN uint32_t td_handle_rescue_max_run(const td_handle *h);
+// rescue.hip, for td_destroy: frees the handle's rescue, if any
+TD_HIDDEN void td_rescue_release(td_handle *h);
 }
 
 // a failed HIP call ends the calling function with TD_E_HIP and "<the call as written>: <HIP's text>"

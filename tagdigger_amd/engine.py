@@ -53,9 +53,34 @@ def census_index(barcodes, cutsite):
     return barcut, len(barcodes), [len(x) for x in barcodes]
 
 
+def rescue_index(barcodes, tags, cutsite):
+    """What a tag rescue hands to td_rescue_begin: Engine.set_index's set-up (find_tags_fastq, tagdigger_fun.py:197-233)
+    with its asserts and its strip decision -- the barcode + cut site list over every cut-site variant, the number of
+    barcodes, where the tag comparison starts in a read of each barcode, and the tags as they are compared."""
+    assert all([set(barcode.upper()) <= set('ACGT') for barcode in barcodes]), "Non-ACGT barcode."
+    cutsite = cutsite.upper()
+    assert set(cutsite) <= set('ACGTNRYKMSWBDHV'), "Invalid cut site."
+    tags = [tag.upper() for tag in tags]
+    assert all([set(tag) <= set('ACGT') for tag in tags]), "Non-ACGT tag."
+    cutlen = len(cutsite)
+    tagoff = [len(x) + cutlen for x in barcodes]
+    cutsites = enumerate_cut_sites(cutsite)
+    barcut = []
+    for cut in cutsites:
+        barcut += combine_barcode_and_cutsite(barcodes, cut)
+    if set(x[:cutlen] for x in tags).issubset(set(cutsites)):
+        if len(cutsites) == 1:
+            tags = [x[cutlen:] for x in tags]          # site already checked with the barcode
+        else:
+            tagoff = [x - cutlen for x in tagoff]      # tags keep the (variable) site
+    return barcut, len(barcodes), tagoff, tags
+
+
 INDEX_INFO = ("W", "m_bases", "buckets", "spb", "nshort", "displaced", "longest", "wrapped", "nch", "nch2")     # TD_INDEX_* slots
 
 CENSUS_STATS = ("reads", "barcut", "short", "ambiguous", "counted", "distinct", "slots", "max_keys")
+RESCUE_STATS = ("reads", "barcut", "exact", "rescued1", "rescued2", "ambiguous", "none", "longest_run")     # TD_RESCUE_* slots
+RESCUE_MAX_TAGLEN = 128     # TD_RESCUE_MAX_TAGLEN
 QC_STATS = ("reads", "barcut", "qual_lines", "bases", "qual_bases", "qual_invalid", "empty_qual", "max_cycles")     # TD_QC_* slots
 
 
@@ -574,6 +599,63 @@ class Engine:
     def qc_end(self):
         B.check(self._L.td_qc_end(self._h))
         self._qc_shape = (0, 0)
+
+    # ------------------------------------------------------------------ tag rescue (td_rescue_*; csrc/rescue.hip)
+    def rescue_begin(self, barcodes, tags, cutsite="TGCAG", max_mismatch=1):
+        """A fresh rescue matrix for these barcodes and tags (set_index's set-up), at 1 or 2 mismatches."""
+        barcut, barnum, tagoff, stored = rescue_index(barcodes, tags, cutsite)
+        self._rescue_begin_lists(barcut, barnum, tagoff, stored, max_mismatch)
+
+    def _rescue_begin_lists(self, barcut, barnum, tagoff, tags, max_mismatch=1):
+        """td_rescue_begin as include/tagdig.h states it; called directly only by tests that need an offset or a tag list
+        rescue_begin never derives."""
+        self._rescue_shape = (0, 0)
+        B.check(self._L.td_rescue_begin(self._h, _c_strings(barcut), len(barcut), barnum, (C.c_uint32 * max(1, barnum))(*tagoff),
+                                        _c_strings(tags), len(tags), int(max_mismatch)))
+        self._rescue_shape = (barnum, len(tags))
+
+    def rescue_device(self, d_ptr, nbytes, first_line=0, maxreads=5e9, stream=0):
+        """Enqueue one rescue pass over a FASTQ buffer already in HBM (asynchronous, accumulates)."""
+        B.check(self._L.td_rescue_device(self._h, C.c_void_p(d_ptr), nbytes, first_line, effective_maxreads(maxreads),
+                                         C.c_void_p(stream) if stream else None))
+
+    def rescue_file(self, path, maxreads=5e9):
+        """The rescue over a file, plain or gzip by name, through count_file's readers (accumulates)."""
+        open(path, 'rb').close()
+        B.check(self._L.td_rescue_file(self._h, os.fsencode(path), effective_maxreads(maxreads)))
+
+    def rescue_stats(self):
+        """{reads, barcut, exact, rescued1, rescued2, ambiguous, none, longest_run}, cumulative since rescue_begin."""
+        st = (C.c_uint64 * 8)()
+        B.check(self._L.td_rescue_stats(self._h, st))
+        return dict(zip(RESCUE_STATS, (int(x) for x in st)))
+
+    def rescue_work(self):
+        """{probes, verified, part_bases, max_probe}: directory probes and verified tags of the passes so far, and the
+        shape of the index."""
+        st = (C.c_uint64 * 4)()
+        B.check(self._L.td_rescue_work(self._h, st))
+        return dict(zip(("probes", "verified", "part_bases", "max_probe"), (int(x) for x in st)))
+
+    def rescue_fetch(self):
+        """(rescued uint32 [barnum, ntags], positions uint64 [128]) as numpy arrays."""
+        import numpy as np
+        barnum, ntags = getattr(self, "_rescue_shape", (0, 0))
+        rescued = np.zeros((barnum, ntags), dtype=np.uint32)
+        positions = np.zeros(RESCUE_MAX_TAGLEN, dtype=np.uint64)
+        B.check(self._L.td_rescue_fetch(self._h, C.c_void_p(rescued.ctypes.data) if rescued.size else None,
+                                        C.c_void_p(positions.ctypes.data)))
+        return rescued, positions
+
+    def rescue_matrix(self):
+        """The device address of the rescue matrix (uint32 [barnum, ntags]); good until rescue_end or the next begin."""
+        p = C.c_void_p()
+        B.check(self._L.td_rescue_matrix(self._h, C.byref(p)))
+        return p.value
+
+    def rescue_end(self):
+        B.check(self._L.td_rescue_end(self._h))
+        self._rescue_shape = (0, 0)
 
     # ------------------------------------------------------------------ tag network (td_tagnet_*; csrc/tagnet.hip)
     def tagnet_build(self, seqs, counts, taglen, ratio_ppm):

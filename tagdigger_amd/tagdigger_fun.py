@@ -2763,6 +2763,206 @@ def writeQCQualityMatrix(filename, libraries, results):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Tag rescue: reads one or two substitutions from a known tag.
+RESCUE_MAX_TAGLEN = 128
+RESCUE_CLASSES = ("reads", "barcut", "exact", "rescued1", "rescued2", "ambiguous", "none")
+RESCUE_STAT_NAMES = RESCUE_CLASSES + ("longest_run",)
+
+
+class RescueResult:
+    """What rescue_tags_fastq returns: rescued ([len(barcodes)][len(tags)], lists or a numpy uint32 array), stats (dict:
+    reads, barcut, exact, rescued1, rescued2, ambiguous, none, longest_run), positions (128 ints: mismatches of the
+    rescued reads by position in the tag), backend ("gpu" or "host": which of the two answered)."""
+
+    def __init__(self, rescued, stats, positions, backend):
+        self.rescued, self.stats, self.positions, self.backend = rescued, stats, positions, backend
+
+
+def _rescue_check_tags(stored):
+    """td_rescue_begin's checks of the stored tags, with the exceptions its error codes are raised as."""
+    from ._binding import TagdigError
+    if not stored:
+        raise IndexError("list index out of range")
+    for t in stored:
+        if not t:
+            raise IndexError("list index out of range")
+        if len(t) > RESCUE_MAX_TAGLEN:
+            raise TagdigError(-7, "tag longer than 128 bases")
+    # sorted, the tags that begin the current one form a chain; of all pairs the one whose later tag comes first
+    chain, bad = [], None
+    for k in sorted(range(len(stored)), key=lambda i: (stored[i], i)):
+        while chain and not stored[k].startswith(stored[chain[-1][0]]):
+            chain.pop()
+        low = k
+        if chain:
+            cand = max(k, chain[-1][1])
+            bad = cand if bad is None else min(bad, cand)
+            low = min(low, chain[-1][1])
+        chain.append((k, low))
+    if bad is not None:
+        raise AssertionError("Problematic sequence: {}.  Likely due to overlapping tags.".format(bad))
+
+
+def _rescue_longest_run(stored, K):
+    """The longest run of tags that share one of the K + 1 parts of the device's index (len(stored) when the shortest
+    tag leaves no part)."""
+    P = min(32, min(len(t) for t in stored) // (K + 1))
+    if P < 1:
+        return len(stored)
+    longest = 0
+    for p in range(K + 1):
+        runs = {}
+        for t in stored:
+            key = t[p * P:(p + 1) * P]
+            runs[key] = runs.get(key, 0) + 1
+        longest = max(longest, max(runs.values()))
+    return longest
+
+
+def _rescue_host(fqfile, barcodes, tags, cutsite, maxreads, K):
+    """The rescue rule read by read: (rescued matrix as lists, statistics, positions, the matrix of the exact reads --
+    with tags none of which begins another, what find_tags_fastq counts).  Every tag of a length is held against the
+    window in one numpy comparison; a window seen before is answered from a dict."""
+    import numpy as np
+    from ._binding import NonAsciiSequence
+    from .engine import rescue_index
+    barcut, barnum, tagoff, stored = rescue_index(barcodes, tags, cutsite)
+    index = _census_host_index(barcodes, cutsite)
+    _rescue_check_tags(stored)
+    lengths = sorted({len(s) for s in index})
+    by_len = {}
+    for t, s in enumerate(stored):
+        by_len.setdefault(len(s), []).append(t)
+    groups = [(n, np.array(ids), np.frombuffer("".join(stored[t] for t in ids).encode("ascii"), dtype=np.uint8).reshape(len(ids), n))
+              for n, ids in sorted(by_len.items())]
+    maxlen = groups[-1][0]
+    bound = effective_maxreads(maxreads)
+    rescued = [[0] * len(stored) for _ in range(barnum)]
+    exact = [[0] * len(stored) for _ in range(barnum)]
+    positions = [0] * RESCUE_MAX_TAGLEN
+    st = dict.fromkeys(RESCUE_CLASSES, 0)
+    memo = {}
+
+    def classify(w):
+        """(class, tag, mismatching positions) of a window"""
+        best, who, several = K + 1, -1, False
+        for n, ids, mat in groups:
+            if n > len(w):
+                break
+            d = (mat != np.frombuffer(w[:n].encode("latin-1"), dtype=np.uint8)).sum(axis=1)
+            m = int(d.min())
+            if m == 0:
+                return "exact", int(ids[int(d.argmin())]), ()
+            if m <= best and m <= K:
+                hits = np.flatnonzero(d == m)
+                if m < best:
+                    best, who, several = m, int(ids[hits[0]]), len(hits) > 1
+                else:
+                    several = True
+        if who < 0:
+            return "none", -1, ()
+        if several:
+            return "ambiguous", -1, ()
+        t = stored[who]
+        return "rescued{}".format(best), who, tuple(i for i in range(len(t)) if w[i] != t[i])
+
+    opener = _gzip.open if fqfile[-2:].lower() == 'gz' else open
+    with opener(fqfile, 'rt', encoding='latin-1') as fh:
+        for k, line in enumerate(fh):
+            if k % 4 != 1:
+                continue
+            st["reads"] += 1
+            if any(ch >= '\x80' for ch in line):
+                raise NonAsciiSequence("non-ASCII byte in a sequence line")
+            line1 = line.strip().upper()
+            b = -1
+            for n in lengths:
+                if line1[:n] in index and len(line1) >= n:
+                    b = index[line1[:n]]
+                    break
+            if b != -1:
+                st["barcut"] += 1
+                w = line1[tagoff[b]:tagoff[b] + maxlen]
+                if w not in memo:
+                    memo[w] = classify(w)
+                kind, t, where = memo[w]
+                st[kind] += 1
+                if kind == "exact":
+                    exact[b][t] += 1
+                elif t >= 0:
+                    rescued[b][t] += 1
+                    for i in where:
+                        positions[i] += 1
+            if st["reads"] >= bound:
+                break
+    st["longest_run"] = _rescue_longest_run(stored, K)
+    return rescued, st, positions, exact
+
+
+def rescue_tags_fastq(fqfile, barcodes, tags, cutsite="TGCAG", maxreads=5e9, max_mismatch=1, device=0, backend="gpu",
+                      as_array=False):
+    """Count the reads of one FASTQ file (plain or .gz by name) that find_tags_fastq drops because they lie 1 ..
+    max_mismatch (1 or 2) substitutions from a known tag -> RescueResult.
+
+    The set-up is find_tags_fastq's (asserts, every cut-site variant, the strip decision).  Per read with a barcode +
+    cut site: w = the stripped, upper-cased line from where the tags are compared, a tag of n bases is a candidate iff
+    n <= len(w), and its distance is the number of positions i < n with w[i] != tag[i] (a character outside ACGT
+    mismatches every base; no indels, no qualities).  A candidate at distance 0: the read is `exact` -- the counter's,
+    nothing is written.  Otherwise the smallest distance m decides: m <= max_mismatch and one tag attains it -> that
+    cell of `.rescued`, `rescued<m>` and `.positions[i]` for every mismatching i; several tags attain it ->
+    `ambiguous`; else `none`.  barcut == exact + rescued1 + rescued2 + ambiguous + none.
+
+    The tags as compared must be 1..128 bases and none may equal or begin another (AssertionError naming the later tag).
+    backend="gpu": csrc/rescue.hip.  An index in which more tags share one part than the device takes ("rescue_max_run")
+    is answered by the host rule, as is a tag list too short for max_mismatch + 1 parts; `.backend` says which of the
+    two it was.  backend="host": the same rule in Python."""
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    K = int(max_mismatch)
+    if K not in (1, 2):
+        raise ValueError("max_mismatch must be 1 or 2")
+    answered_by = "host"
+    if backend == "gpu":
+        from ._binding import TagdigError
+        eng = default_engine(device)
+        try:
+            eng.rescue_begin(barcodes, tags, cutsite, K)
+            answered_by = "gpu"
+        except TagdigError as exc:
+            if exc.code != -7 or not exc.detail.startswith("tag rescue: run"):
+                raise
+    if answered_by == "gpu":
+        try:
+            eng.rescue_file(fqfile, maxreads)
+            stats = eng.rescue_stats()
+            matrix, pos = eng.rescue_fetch()
+        finally:
+            try:
+                eng.rescue_end()
+            except Exception:          # noqa: BLE001 -- the error that brought us here is the one to report
+                pass
+        rescued = matrix if as_array else matrix.tolist()
+        positions = [int(x) for x in pos]
+    else:
+        rescued, stats, positions, _ = _rescue_host(fqfile, barcodes, tags, cutsite, maxreads, K)
+        if as_array:
+            import numpy as np
+            rescued = np.array(rescued, dtype=np.uint32).reshape(len(barcodes), len(tags))
+    return RescueResult(rescued, {k: stats[k] for k in RESCUE_STAT_NAMES}, positions, answered_by)
+
+
+def writeRescueStats(filename, libraries, results):
+    """One row per library: Library, the seven classes, and the rescued reads' share of the reads with barcode + cut
+    site (six decimals; NA without any).  CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Library"] + list(RESCUE_CLASSES) + ["rescued_share"])
+        for lib, res in zip(libraries, results):
+            st = res.stats
+            out.writerow([lib] + [st[k] for k in RESCUE_CLASSES] + [_rate_text(st["rescued1"] + st["rescued2"], st["barcut"])])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Tag Manager (reference tagdigger_fun.py:1389-1905 and the prompts of :936-1028, :1182-1200).
 #
 # Every function keeps the reference's signature, return values, printed lines, files and exceptions.  Those with a
