@@ -30,16 +30,14 @@
 #include <vector>
 
 #define TD_INST_ONLY                    // (k_scan_tiles is defined in tagdig.hip's translation unit)
-#include "kernels.hpp"
-#include "piece_sink.hpp"
-#include "td_internal.hpp"
+#include "stream_pass.hpp"
 
 namespace tdc {
 using namespace tdk;
 
 constexpr int CPT = 4;                                   // 16-byte chunks per thread: tiles of 16 KiB, as k_count_lines<4> counts them
 constexpr uint32_t TILE = CPT * BLOCK * 16u;
-static_assert(TILE == 16384, "td_line_prefix (tagdig.hip) counts terminators per 16 KiB tile with k_count_lines<4>");
+static_assert(TILE == tdi::STREAM_TILE, "td_line_prefix (tagdig.hip) counts terminators per 16 KiB tile with k_count_lines<4>");
 constexpr uint32_t LIST_CAP = TILE / 4 + 4;              // read-line starts per tile: every fourth terminator, the buffer's own first line
 constexpr uint32_t CENSUS_SPIN_LIMIT = 1u << 20;
 constexpr unsigned long long CC_CLAIMED = 1ull << 62, CC_READY = 2ull << 62, CC_COUNT = (1ull << 62) - 1;
@@ -351,77 +349,46 @@ namespace {
 constexpr uint64_t CENSUS_MIN_SLOTS = 1024, CENSUS_DEFAULT_SLOTS = 1ull << 22, CENSUS_MAX_SLOTS = 1ull << 32;
 constexpr size_t CENSUS_LDS_INDEX = 40 * 1024;            // the barcode index's share of a workgroup's LDS
 
-struct Census {
-    td_handle *h = nullptr;
-    uint32_t taglen = 0, bblob_bytes = 0, off_bmeta = 0, off_bdir = 0;
-    tdi::DevBuf<uint32_t> d_bblob;
+struct Census : tdi::StreamPass {
+    uint32_t taglen = 0;
     tdi::DevBuf<unsigned long long> d_table, d_cs;
     uint64_t slots = 0, max_keys = 0;
     int combine = 1;
-    bool used = false;                        // something has been added since td_census_begin
-    int dead = 0;                             // the code every call answers with after a failure, until td_census_begin
-    std::string dead_msg;
     size_t slot_words() const { return taglen > 32 ? 4 : 2; }
+
+    int zero(hipStream_t s) override {
+        TD_HIPCHK(hipMemsetAsync(d_table.p, 0, slots * slot_words() * 8, s));
+        TD_HIPCHK(hipMemsetAsync(d_cs.p, 0, tdc::CS_NWORDS * 8, s));
+        return TD_OK;
+    }
+
+    int launch(const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, hipStream_t stream,
+               const unsigned long long *cursor_in, unsigned long long *cursor_out) override {
+        tdc::CensusParams p{};
+        const int rc = prologue(d_fastq, nbytes, max_reads, stream, d_cs.p + tdc::CS_TOTAL, p.prefix, p.ntiles);
+        if (rc || !p.ntiles) return rc;
+        p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
+        p.limit_line = limit_line(max_reads);
+        p.bblob = d_bblob.p; p.bblob_bytes = bblob_bytes; p.off_bmeta = off_bmeta; p.off_bdir = off_bdir;
+        p.taglen = taglen; p.table = d_table.p; p.slot_mask = slots - 1; p.max_keys = max_keys; p.cs = d_cs.p;
+        p.cursor_in = cursor_in; p.cursor_out = cursor_out; p.combine = (uint32_t)combine;
+        hipLaunchKernelGGL(tdc::k_census, dim3(grid(p.ntiles, 8, false)), dim3(tdk::BLOCK), bblob_bytes, stream, p);
+        TD_HIPCHK(hipGetLastError());
+        return TD_OK;
+    }
+
+    // after a synchronisation: what the kernels flagged
+    int sync_stats(unsigned long long cs[tdc::CS_NWORDS]) {
+        const int rc = sync_words(cs, d_cs.p, tdc::CS_NWORDS, tdc::CS_ERR);
+        if (rc || !cs[tdc::CS_ERR]) return rc;
+        if (cs[tdc::CS_ERR] & tdc::ERR_FULL)
+            return latch(TD_E_LIMIT, "census table full: " + std::to_string(slots) + " slots take " + std::to_string(max_keys) + " distinct keys, " +
+                                         std::to_string(std::min<unsigned long long>(cs[tdc::CS_DISTINCT], slots)) + " were placed; begin again with more slots");
+        return latch(TD_E_INTERNAL, "a wait for a claimed slot timed out inside the census kernel");
+    }
 };
 
-Census *census_of(td_handle *h) { return h ? (Census *)*td_handle_census(h) : nullptr; }
-
-int census_zero(Census *c, hipStream_t s) {
-    TD_HIPCHK(hipMemsetAsync(c->d_table.p, 0, c->slots * c->slot_words() * 8, s));
-    TD_HIPCHK(hipMemsetAsync(c->d_cs.p, 0, tdc::CS_NWORDS * 8, s));
-    TD_HIPCHK(hipStreamSynchronize(s));
-    c->used = false;
-    return TD_OK;
-}
-
-int census_launch(Census *c, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, hipStream_t stream,
-                  const unsigned long long *cursor_in, unsigned long long *cursor_out) {
-    if (c->dead) return td_fail_internal(c->dead, c->dead_msg.c_str());
-    if (((uintptr_t)d_fastq & 15) != 0) return td_fail_internal(TD_E_ARG, "device FASTQ pointer must be 16-byte aligned");
-    if (nbytes == 0) return TD_OK;
-    if (max_reads == 0) max_reads = 1;
-    c->used = true;
-    const uint64_t *prefix = nullptr;
-    int rc = td_line_prefix(c->h, d_fastq, nbytes, (void *)stream, &prefix, c->d_cs.p + tdc::CS_TOTAL); if (rc) return rc;
-    tdc::CensusParams p{};
-    p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
-    // last read line that is looked at: ordinal r (1-based) sits on line 4 (r - 1) + 1
-    p.limit_line = max_reads >= (1ull << 60) ? ~0ull - 8 : 4 * (max_reads - 1) + 1;
-    p.prefix = prefix; p.ntiles = (uint32_t)((nbytes + tdc::TILE - 1) / tdc::TILE);
-    p.bblob = c->d_bblob.p; p.bblob_bytes = c->bblob_bytes; p.off_bmeta = c->off_bmeta; p.off_bdir = c->off_bdir;
-    p.taglen = c->taglen; p.table = c->d_table.p; p.slot_mask = c->slots - 1; p.max_keys = c->max_keys; p.cs = c->d_cs.p;
-    p.cursor_in = cursor_in; p.cursor_out = cursor_out; p.combine = (uint32_t)c->combine;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(p.ntiles, (uint64_t)td_handle_num_cu(c->h) * 8);
-    hipLaunchKernelGGL(tdc::k_census, dim3(grid), dim3(tdk::BLOCK), c->bblob_bytes, stream, p);
-    TD_HIPCHK(hipGetLastError());
-    return TD_OK;
-}
-
-// after a synchronisation: what the kernels flagged
-int census_check(Census *c, const unsigned long long *cs) {
-    const unsigned long long e = cs[tdc::CS_ERR];
-    if (!e) return TD_OK;
-    if (e & tdk::ERR_NONASCII) { c->dead = TD_E_NONASCII; c->dead_msg = "non-ASCII byte in a sequence line"; }
-    else if (e & tdc::ERR_FULL) {
-        c->dead = TD_E_LIMIT;
-        c->dead_msg = "census table full: " + std::to_string(c->slots) + " slots take " + std::to_string(c->max_keys) + " distinct keys, " +
-                      std::to_string(std::min<unsigned long long>(cs[tdc::CS_DISTINCT], c->slots)) + " were placed; begin again with more slots";
-    } else { c->dead = TD_E_INTERNAL; c->dead_msg = "a wait for a claimed slot timed out inside the census kernel"; }
-    return td_fail_internal(c->dead, c->dead_msg.c_str());
-}
-
-int census_sync_stats(Census *c, unsigned long long cs[tdc::CS_NWORDS]) {
-    if (c->dead) return td_fail_internal(c->dead, c->dead_msg.c_str());
-    TD_HIPCHK(hipDeviceSynchronize());
-    TD_HIPCHK(hipMemcpy(cs, c->d_cs.p, tdc::CS_NWORDS * 8, hipMemcpyDeviceToHost));
-    return census_check(c, cs);
-}
-
-int sink_piece(void *ctx, const void *d, uint64_t n, uint64_t first_line, uint64_t max_reads, hipStream_t s, const unsigned long long *cin,
-               unsigned long long *cout) {
-    return census_launch((Census *)ctx, d, n, first_line, max_reads, s, cin, cout);
-}
-int sink_restart(void *ctx) { Census *c = (Census *)ctx; return census_zero(c, (hipStream_t)td_handle_work_stream(c->h)); }
+Census *census_of(td_handle *h) { return tdi::state_of<Census>(h, tdi::CENSUS); }
 
 // A 0, C 1, T 2, G 3 -> A 0, C 1, G 2, T 3 in every 2-bit field: numeric order = the order of the strings
 inline uint64_t acgt_order(uint64_t x) { return x ^ ((x >> 1) & 0x5555555555555555ull); }
@@ -430,12 +397,6 @@ inline uint64_t acgt_order(uint64_t x) { return x ^ ((x >> 1) & 0x55555555555555
 
 extern "C" {
 
-void td_census_release(td_handle *h) {
-    void **slot = td_handle_census(h);
-    delete (Census *)*slot;
-    *slot = nullptr;
-}
-
 int td_census_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *baroff,
                     uint32_t taglen, uint64_t slots) {
     if (!h || !barcut || !baroff) return td_fail_internal(TD_E_ARG, "NULL argument");
@@ -443,66 +404,44 @@ int td_census_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, 
     if (slots == 0) slots = CENSUS_DEFAULT_SLOTS;
     if (slots < CENSUS_MIN_SLOTS || slots > CENSUS_MAX_SLOTS || (slots & (slots - 1)))
         return td_fail_internal(TD_E_ARG, "slots must be a power of two, 1024 .. 2^32 (0: the default, 2^22)");
-    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    TD_HIPCHK(hipDeviceSynchronize());
-    td_census_release(h);
-    uint8_t *blob = nullptr;
-    uint32_t bytes = 0, off_bmeta = 0, off_bdir = 0;
-    int rc = td_barcut_blob(barcut, n_barcut, barnum, baroff, &blob, &bytes, &off_bmeta, &off_bdir);
-    if (rc) return rc;
-    if (bytes > CENSUS_LDS_INDEX) { free(blob); return td_fail_internal(TD_E_LIMIT, "barcode index does not fit the LDS budget"); }
+    int rc = tdi::quiet_reset(h, tdi::CENSUS); if (rc) return rc;
+    std::unique_ptr<Census> c(new Census());
+    rc = c->begin(h, barcut, n_barcut, barnum, baroff, CENSUS_LDS_INDEX); if (rc) return rc;
     for (uint32_t b = 0; b < barnum; b++)
-        if (baroff[b] > 32) { free(blob); return td_fail_internal(TD_E_LIMIT, "barcode longer than 32 bases"); }
-    Census *c = new Census();
-    c->h = h; c->taglen = taglen; c->bblob_bytes = bytes; c->off_bmeta = off_bmeta; c->off_bdir = off_bdir;
-    c->slots = slots; c->max_keys = slots / 4 * 3;
+        if (baroff[b] > 32) return td_fail_internal(TD_E_LIMIT, "barcode longer than 32 bases");
+    c->taglen = taglen; c->slots = slots; c->max_keys = slots / 4 * 3;
     const char *env = getenv("TAGDIG_CENSUS_COMBINE");
     c->combine = env ? (atoi(env) != 0) : 1;
-    hipError_t e = c->d_bblob.alloc((bytes + 3) / 4);
-    if (e == hipSuccess) e = hipMemcpy(c->d_bblob.p, blob, bytes, hipMemcpyHostToDevice);
-    free(blob);
-    if (e == hipSuccess) e = c->d_cs.alloc(tdc::CS_NWORDS);
-    if (e != hipSuccess) { delete c; (void)hipGetLastError(); return td_fail_internal(TD_E_HIP, hipGetErrorString(e)); }
-    e = c->d_table.alloc(slots * c->slot_words());
-    if (e != hipSuccess) {
-        delete c; (void)hipGetLastError();
+    const hipError_t e = c->d_cs.alloc(tdc::CS_NWORDS);
+    if (e != hipSuccess) return tdi::StreamPass::hip_failed(e);
+    if (c->d_table.alloc(slots * c->slot_words()) != hipSuccess) {
+        (void)hipGetLastError();
         return td_fail_internal(TD_E_HIP, ("no device memory for a census table of " + std::to_string(slots) + " slots").c_str());
     }
-    rc = census_zero(c, (hipStream_t)td_handle_work_stream(h));
-    if (rc) { delete c; return rc; }
-    *td_handle_census(h) = c;
-    return TD_OK;
+    return tdi::install(c, tdi::CENSUS);
 }
 
 int td_census_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream) {
     Census *c = census_of(h);
-    if (!c) return td_fail_internal(h ? TD_E_STATE : TD_E_ARG, h ? "td_census_begin has not been called" : "handle is NULL");
+    if (!c) return tdi::no_state("census", h, "handle is NULL");
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    return census_launch(c, d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
+    return c->launch(d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
 }
 
 int td_census_file(td_handle *h, const char *path, uint64_t max_reads) {
     Census *c = census_of(h);
-    if (!c || !path) return td_fail_internal(h && path ? TD_E_STATE : TD_E_ARG, h && path ? "td_census_begin has not been called" : "NULL argument");
-    if (c->dead) return td_fail_internal(c->dead, c->dead_msg.c_str());
-    const td_piece_sink sink{sink_piece, sink_restart, c, !c->used};
-    int rc = td_stream_file(h, path, max_reads, &sink);
-    if (rc) {
-        if (c->used && !c->dead) {            // the table holds a part of the file: never handed out
-            c->dead = rc; c->dead_msg = td_last_error();
-        }
-        return rc;
-    }
+    if (!c || !path) return tdi::no_state("census", h && path);
     unsigned long long cs[tdc::CS_NWORDS];
-    return census_sync_stats(c, cs);
+    const int rc = c->file(path, max_reads);
+    return rc ? rc : c->sync_stats(cs);
 }
 
 int td_census_stats(td_handle *h, uint64_t out[8]) {
     Census *c = census_of(h);
-    if (!c || !out) return td_fail_internal(h && out ? TD_E_STATE : TD_E_ARG, h && out ? "td_census_begin has not been called" : "NULL argument");
+    if (!c || !out) return tdi::no_state("census", h && out);
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     unsigned long long cs[tdc::CS_NWORDS];
-    const int rc = census_sync_stats(c, cs); if (rc) return rc;
+    const int rc = c->sync_stats(cs); if (rc) return rc;
     out[TD_CENSUS_READS] = cs[tdc::CS_READS]; out[TD_CENSUS_BARCUT] = cs[tdc::CS_BARCUT];
     out[TD_CENSUS_SHORT] = cs[tdc::CS_SHORT]; out[TD_CENSUS_AMBIGUOUS] = cs[tdc::CS_AMBIG];
     out[TD_CENSUS_COUNTED] = cs[tdc::CS_BARCUT] - cs[tdc::CS_SHORT] - cs[tdc::CS_AMBIG];
@@ -513,12 +452,12 @@ int td_census_stats(td_handle *h, uint64_t out[8]) {
 
 int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *counts_out, uint64_t capacity, uint64_t *n_out) {
     Census *c = census_of(h);
-    if (!c || !n_out) return td_fail_internal(h && n_out ? TD_E_STATE : TD_E_ARG, h && n_out ? "td_census_begin has not been called" : "NULL argument");
+    if (!c || !n_out) return tdi::no_state("census", h && n_out);
     if (capacity && (!seqs_out || !counts_out)) return td_fail_internal(TD_E_ARG, "NULL argument");
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     *n_out = 0;
     unsigned long long cs[tdc::CS_NWORDS];
-    int rc = census_sync_stats(c, cs); if (rc) return rc;
+    int rc = c->sync_stats(cs); if (rc) return rc;
     if (min_count == 0) min_count = 1;
     const uint32_t two = c->taglen > 32 ? 1u : 0u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((c->slots + 255) / 256, (uint64_t)td_handle_num_cu(h) * 8);
@@ -572,10 +511,7 @@ int td_census_fetch(td_handle *h, uint64_t min_count, char *seqs_out, uint64_t *
 
 int td_census_end(td_handle *h) {
     if (!h) return td_fail_internal(TD_E_ARG, "handle is NULL");
-    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    TD_HIPCHK(hipDeviceSynchronize());
-    td_census_release(h);
-    return TD_OK;
+    return tdi::quiet_reset(h, tdi::CENSUS);
 }
 
 }  // extern "C"

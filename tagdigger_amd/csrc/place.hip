@@ -82,10 +82,15 @@ struct td_place {
 
 namespace {
 
-std::vector<td_place *> *places_of(td_handle *h, bool make) {
-    void **slot = td_handle_places(h);
-    if (!*slot && make) *slot = new std::vector<td_place *>();
-    return (std::vector<td_place *> *)*slot;
+// the places alive on a handle: td_destroy frees those still open
+struct Places : tdi::ModuleState {
+    std::vector<td_place *> all;
+    ~Places() override { for (td_place *pl : all) delete pl; }
+};
+Places *places_of(td_handle *h, bool make) {
+    std::unique_ptr<tdi::ModuleState> &slot = tdi::module_slot(h, tdi::PLACES);
+    if (!slot && make) slot.reset(new Places());
+    return static_cast<Places *>(slot.get());
 }
 
 // ------------------------------------------------------------------ site scan
@@ -493,15 +498,6 @@ uint8_t pl_comp(uint8_t c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ?
 
 }  // namespace
 
-extern "C" void td_place_release(td_handle *h) {
-    void **slot = td_handle_places(h);
-    std::vector<td_place *> *all = (std::vector<td_place *> *)*slot;
-    if (!all) return;
-    for (td_place *pl : *all) delete pl;
-    delete all;
-    *slot = nullptr;
-}
-
 extern "C" int td_place_sites(td_handle *h, const void *d_seq, uint64_t seq_bytes, const uint64_t *rec_start, uint32_t R,
                               const char *const *remnants, uint32_t n_remnants, uint32_t taglen, td_place **out, uint64_t stats[8],
                               double *ms) {
@@ -631,7 +627,7 @@ extern "C" int td_place_sites(td_handle *h, const void *d_seq, uint64_t seq_byte
         }
     }
     if (stats) for (int k = 0; k < 8; ++k) stats[k] = pl->stats[k];
-    places_of(h, true)->push_back(pl.get());
+    places_of(h, true)->all.push_back(pl.get());
     *out = pl.release();
     return TD_OK;
 }
@@ -786,14 +782,11 @@ extern "C" int td_place_tags(td_handle *h, td_place *pl, const char *seqs, uint3
 extern "C" int td_place_free(td_handle *h, td_place *pl) {
     if (!pl) return TD_OK;
     if (!h) return td_fail_internal(TD_E_ARG, "NULL argument");
-    std::vector<td_place *> *all = places_of(h, false);
-    if (all) {
-        auto it = std::find(all->begin(), all->end(), pl);
-        if (it == all->end()) return td_fail_internal(TD_E_ARG, "not a place of this handle");
-        all->erase(it);
-    } else {
-        return td_fail_internal(TD_E_ARG, "not a place of this handle");
-    }
+    Places *places = places_of(h, false);
+    if (!places) return td_fail_internal(TD_E_ARG, "not a place of this handle");
+    auto it = std::find(places->all.begin(), places->all.end(), pl);
+    if (it == places->all.end()) return td_fail_internal(TD_E_ARG, "not a place of this handle");
+    places->all.erase(it);
     (void)hipSetDevice(td_handle_device(h));
     delete pl;
     return TD_OK;

@@ -29,16 +29,14 @@
 #include <string>
 
 #define TD_INST_ONLY                    // (k_scan_tiles is defined in tagdig.hip's translation unit)
-#include "kernels.hpp"
-#include "piece_sink.hpp"
-#include "td_internal.hpp"
+#include "stream_pass.hpp"
 
 namespace tdq {
 using namespace tdk;
 
 constexpr int CPT = 4;                                   // 16-byte chunks per thread: tiles of 16 KiB, as k_count_lines<4> counts them
 constexpr uint32_t TILE = CPT * BLOCK * 16u;
-static_assert(TILE == 16384, "td_line_prefix (tagdig.hip) counts terminators per 16 KiB tile with k_count_lines<4>");
+static_assert(TILE == tdi::STREAM_TILE, "td_line_prefix (tagdig.hip) counts terminators per 16 KiB tile with k_count_lines<4>");
 constexpr uint32_t QC_WIN = 152;                         // cycles whose tables live in LDS, at most (two workgroups per CU)
 constexpr uint32_t QC_WIN_MIN = 100;                     // ... and at least, when the index and the barcode rows are large (then one workgroup per CU)
 constexpr uint32_t QC_LDS_HALF = 80 * 1024;              // what a workgroup may take for two to fit a CU
@@ -403,15 +401,10 @@ namespace {
 constexpr size_t QC_LDS_INDEX = 40 * 1024;                // the barcode index's share of a workgroup's LDS, as the census's
 constexpr uint32_t QC_FLUSH_DEFAULT = 4096, QC_FLUSH_MAX = 1u << 20;
 
-struct Qc {
-    td_handle *h = nullptr;
-    uint32_t C = 0, nbar = 0, bblob_bytes = 0, off_bmeta = 0, off_bdir = 0;
-    tdi::DevBuf<uint32_t> d_bblob;
+struct Qc : tdi::StreamPass {
+    uint32_t C = 0, nbar = 0;
     tdi::DevBuf<unsigned long long> d_all;    // QS_* | barcode rows | base_cycle | qual_cycle | length | meanq
     uint64_t file_records = 0;                // td_qc_file's bound (the readers are handed one record more)
-    bool used = false;                        // something has been added since td_qc_begin
-    int dead = 0;                             // the code every call answers with after a failure, until td_qc_begin
-    std::string dead_msg;
     size_t n_bar() const { return ((size_t)nbar + 1) * 3; }
     size_t n_base() const { return ((size_t)C + 1) * tdq::NBASE; }
     size_t n_qual() const { return ((size_t)C + 1) * tdq::NQ; }
@@ -423,139 +416,92 @@ struct Qc {
     unsigned long long *d_qual() const { return d_base() + n_base(); }
     unsigned long long *d_len() const { return d_qual() + n_qual(); }
     unsigned long long *d_meanq() const { return d_len() + n_len(); }
+
+    int zero(hipStream_t s) override {
+        TD_HIPCHK(hipMemsetAsync(d_all.p, 0, words() * 8, s));
+        return TD_OK;
+    }
+
+    // records below max_records of one buffer
+    int run(const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_records, hipStream_t stream,
+            const unsigned long long *cursor_in, unsigned long long *cursor_out) {
+        tdq::QcParams p{};
+        const int rc = prologue(d_fastq, nbytes, max_records, stream, d_qs() + tdq::QS_TOTAL, p.prefix, p.ntiles);
+        if (rc || !p.ntiles) return rc;
+        p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
+        p.max_records = std::min<uint64_t>(max_records, 1ull << 61);
+        p.bblob = d_bblob.p; p.bblob_bytes = bblob_bytes; p.off_bmeta = off_bmeta; p.off_bdir = off_bdir;
+        p.nbar = nbar; p.C = C;
+        p.bar_lds = nbar + 1 <= tdq::BAR_LDS_ROWS ? 1u : 0u;
+        // the window: as many cycles as leave room for a second workgroup on the CU, within QC_WIN_MIN .. QC_WIN
+        p.win = tdq::QC_WIN;
+        while (p.win > tdq::QC_WIN_MIN && tdq::qc_lds_bytes(p.bblob_bytes, p.win, p.nbar, p.bar_lds != 0) > tdq::QC_LDS_HALF) p.win--;
+        p.win = std::min(C, p.win);
+        const uint32_t ft = td_handle_qc_flush_tiles(h);
+        p.flush_tiles = ft ? std::min(ft, QC_FLUSH_MAX) : QC_FLUSH_DEFAULT;
+        p.g_bar = d_bar(); p.g_base = d_base(); p.g_qual = d_qual(); p.g_len = d_len(); p.g_meanq = d_meanq(); p.qs = d_qs();
+        p.cursor_in = cursor_in; p.cursor_out = cursor_out;
+        const uint32_t lds = tdq::qc_lds_bytes(p.bblob_bytes, p.win, p.nbar, p.bar_lds != 0);
+        TD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(tdq::k_qc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(tdq::k_qc, dim3(grid(p.ntiles, 2, true)), dim3(tdk::BLOCK), lds, stream, p);
+        TD_HIPCHK(hipGetLastError());
+        return TD_OK;
+    }
+    // a reader's piece: the readers' max_reads is one record beyond the QC's bound, so that they bring the last record's
+    // quality line -- not used
+    int launch(const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t, hipStream_t stream, const unsigned long long *cursor_in,
+               unsigned long long *cursor_out) override {
+        return run(d_fastq, nbytes, first_line, file_records, stream, cursor_in, cursor_out);
+    }
+
+    // after a synchronisation: what the kernel flagged
+    int sync_stats(unsigned long long qs[tdq::QS_NWORDS]) { return sync_words(qs, d_qs(), tdq::QS_NWORDS, tdq::QS_ERR); }
 };
 
-Qc *qc_of(td_handle *h) { return h ? (Qc *)*td_handle_qc(h) : nullptr; }
-
-int qc_zero(Qc *q, hipStream_t s) {
-    TD_HIPCHK(hipMemsetAsync(q->d_all.p, 0, q->words() * 8, s));
-    TD_HIPCHK(hipStreamSynchronize(s));
-    q->used = false;
-    return TD_OK;
-}
-
-int qc_launch(Qc *q, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_records, hipStream_t stream,
-              const unsigned long long *cursor_in, unsigned long long *cursor_out) {
-    if (q->dead) return td_fail_internal(q->dead, q->dead_msg.c_str());
-    if (((uintptr_t)d_fastq & 15) != 0) return td_fail_internal(TD_E_ARG, "device FASTQ pointer must be 16-byte aligned");
-    if (nbytes == 0) return TD_OK;
-    if (max_records == 0) max_records = 1;
-    q->used = true;
-    const uint64_t *prefix = nullptr;
-    int rc = td_line_prefix(q->h, d_fastq, nbytes, (void *)stream, &prefix, q->d_qs() + tdq::QS_TOTAL); if (rc) return rc;
-    tdq::QcParams p{};
-    p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
-    p.max_records = std::min<uint64_t>(max_records, 1ull << 61);
-    p.prefix = prefix; p.ntiles = (uint32_t)((nbytes + tdq::TILE - 1) / tdq::TILE);
-    p.bblob = q->d_bblob.p; p.bblob_bytes = q->bblob_bytes; p.off_bmeta = q->off_bmeta; p.off_bdir = q->off_bdir;
-    p.nbar = q->nbar; p.C = q->C;
-    p.bar_lds = q->nbar + 1 <= tdq::BAR_LDS_ROWS ? 1u : 0u;
-    // the window: as many cycles as leave room for a second workgroup on the CU, within QC_WIN_MIN .. QC_WIN
-    p.win = tdq::QC_WIN;
-    while (p.win > tdq::QC_WIN_MIN && tdq::qc_lds_bytes(p.bblob_bytes, p.win, p.nbar, p.bar_lds != 0) > tdq::QC_LDS_HALF) p.win--;
-    p.win = std::min(q->C, p.win);
-    const uint32_t ft = td_handle_qc_flush_tiles(q->h);
-    p.flush_tiles = ft ? std::min(ft, QC_FLUSH_MAX) : QC_FLUSH_DEFAULT;
-    p.g_bar = q->d_bar(); p.g_base = q->d_base(); p.g_qual = q->d_qual(); p.g_len = q->d_len(); p.g_meanq = q->d_meanq(); p.qs = q->d_qs();
-    p.cursor_in = cursor_in; p.cursor_out = cursor_out;
-    const uint32_t lds = tdq::qc_lds_bytes(p.bblob_bytes, p.win, p.nbar, p.bar_lds != 0);
-    TD_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(tdq::k_qc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    uint32_t grid = (uint32_t)std::min<uint64_t>(p.ntiles, (uint64_t)td_handle_num_cu(q->h) * 2);
-    const uint32_t cap = td_handle_max_grid(q->h);
-    if (cap) grid = std::min(grid, cap);
-    hipLaunchKernelGGL(tdq::k_qc, dim3(grid), dim3(tdk::BLOCK), lds, stream, p);
-    TD_HIPCHK(hipGetLastError());
-    return TD_OK;
-}
-
-// after a synchronisation: what the kernel flagged
-int qc_sync_stats(Qc *q, unsigned long long qs[tdq::QS_NWORDS]) {
-    if (q->dead) return td_fail_internal(q->dead, q->dead_msg.c_str());
-    TD_HIPCHK(hipDeviceSynchronize());
-    TD_HIPCHK(hipMemcpy(qs, q->d_qs(), tdq::QS_NWORDS * 8, hipMemcpyDeviceToHost));
-    if (qs[tdq::QS_ERR] & tdk::ERR_NONASCII) {
-        q->dead = TD_E_NONASCII; q->dead_msg = "non-ASCII byte in a sequence line";
-        return td_fail_internal(q->dead, q->dead_msg.c_str());
-    }
-    return TD_OK;
-}
-
-// (the readers' max_reads is one record beyond the QC's bound, so that they bring the last record's quality line: not used)
-int sink_piece(void *ctx, const void *d, uint64_t n, uint64_t first_line, uint64_t, hipStream_t s, const unsigned long long *cin,
-               unsigned long long *cout) {
-    Qc *q = (Qc *)ctx;
-    return qc_launch(q, d, n, first_line, q->file_records, s, cin, cout);
-}
-int sink_restart(void *ctx) { Qc *q = (Qc *)ctx; return qc_zero(q, (hipStream_t)td_handle_work_stream(q->h)); }
+Qc *qc_of(td_handle *h) { return tdi::state_of<Qc>(h, tdi::QC); }
 
 }  // namespace
 
 extern "C" {
 
-void td_qc_release(td_handle *h) {
-    void **slot = td_handle_qc(h);
-    delete (Qc *)*slot;
-    *slot = nullptr;
-}
-
 int td_qc_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *baroff, uint32_t max_cycles) {
     if (!h || !barcut || !baroff) return td_fail_internal(TD_E_ARG, "NULL argument");
     if (max_cycles < 1 || max_cycles > TD_QC_MAX_CYCLES) return td_fail_internal(TD_E_ARG, "max_cycles must be 1..1024");
-    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    TD_HIPCHK(hipDeviceSynchronize());
-    td_qc_release(h);
-    uint8_t *blob = nullptr;
-    uint32_t bytes = 0, off_bmeta = 0, off_bdir = 0;
-    int rc = td_barcut_blob(barcut, n_barcut, barnum, baroff, &blob, &bytes, &off_bmeta, &off_bdir);
-    if (rc) return rc;
-    if (bytes > QC_LDS_INDEX) { free(blob); return td_fail_internal(TD_E_LIMIT, "barcode index does not fit the LDS budget"); }
+    int rc = tdi::quiet_reset(h, tdi::QC); if (rc) return rc;
+    std::unique_ptr<Qc> q(new Qc());
+    rc = q->begin(h, barcut, n_barcut, barnum, baroff, QC_LDS_INDEX); if (rc) return rc;
     for (uint32_t b = 0; b < barnum; b++)
-        if (baroff[b] > 32) { free(blob); return td_fail_internal(TD_E_LIMIT, "barcode longer than 32 bases"); }
-    Qc *q = new Qc();
-    q->h = h; q->C = max_cycles; q->nbar = barnum; q->bblob_bytes = bytes; q->off_bmeta = off_bmeta; q->off_bdir = off_bdir;
-    hipError_t e = q->d_bblob.alloc((bytes + 3) / 4);
-    if (e == hipSuccess) e = hipMemcpy(q->d_bblob.p, blob, bytes, hipMemcpyHostToDevice);
-    free(blob);
-    if (e == hipSuccess) e = q->d_all.alloc(q->words());
-    if (e != hipSuccess) { delete q; (void)hipGetLastError(); return td_fail_internal(TD_E_HIP, hipGetErrorString(e)); }
-    rc = qc_zero(q, (hipStream_t)td_handle_work_stream(h));
-    if (rc) { delete q; return rc; }
-    *td_handle_qc(h) = q;
-    return TD_OK;
+        if (baroff[b] > 32) return td_fail_internal(TD_E_LIMIT, "barcode longer than 32 bases");
+    q->C = max_cycles; q->nbar = barnum;
+    const hipError_t e = q->d_all.alloc(q->words());
+    if (e != hipSuccess) return tdi::StreamPass::hip_failed(e);
+    return tdi::install(q, tdi::QC);
 }
 
 int td_qc_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream) {
     Qc *q = qc_of(h);
-    if (!q) return td_fail_internal(h ? TD_E_STATE : TD_E_ARG, h ? "td_qc_begin has not been called" : "handle is NULL");
+    if (!q) return tdi::no_state("qc", h, "handle is NULL");
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    return qc_launch(q, d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
+    return q->run(d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
 }
 
 int td_qc_file(td_handle *h, const char *path, uint64_t max_reads) {
     Qc *q = qc_of(h);
-    if (!q || !path) return td_fail_internal(h && path ? TD_E_STATE : TD_E_ARG, h && path ? "td_qc_begin has not been called" : "NULL argument");
-    if (q->dead) return td_fail_internal(q->dead, q->dead_msg.c_str());
+    if (!q || !path) return tdi::no_state("qc", h && path);
     if (max_reads == 0) max_reads = 1;
     q->file_records = max_reads;
-    const td_piece_sink sink{sink_piece, sink_restart, q, !q->used};
     // the readers stop before the quality line of the last record they are asked for: ask for one more (saturating)
-    int rc = td_stream_file(h, path, max_reads >= (1ull << 60) ? max_reads : max_reads + 1, &sink);
-    if (rc) {
-        if (q->used && !q->dead) {            // the tables hold a part of the file: never handed out
-            q->dead = rc; q->dead_msg = td_last_error();
-        }
-        return rc;
-    }
+    const int rc = q->file(path, max_reads >= (1ull << 60) ? max_reads : max_reads + 1);
     unsigned long long qs[tdq::QS_NWORDS];
-    return qc_sync_stats(q, qs);
+    return rc ? rc : q->sync_stats(qs);
 }
 
 int td_qc_stats(td_handle *h, uint64_t out[8]) {
     Qc *q = qc_of(h);
-    if (!q || !out) return td_fail_internal(h && out ? TD_E_STATE : TD_E_ARG, h && out ? "td_qc_begin has not been called" : "NULL argument");
+    if (!q || !out) return tdi::no_state("qc", h && out);
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     unsigned long long qs[tdq::QS_NWORDS];
-    const int rc = qc_sync_stats(q, qs); if (rc) return rc;
+    const int rc = q->sync_stats(qs); if (rc) return rc;
     out[TD_QC_READS] = qs[tdq::QS_READS]; out[TD_QC_BARCUT] = qs[tdq::QS_BARCUT]; out[TD_QC_QUAL_LINES] = qs[tdq::QS_QLINES];
     out[TD_QC_BASES] = qs[tdq::QS_BASES]; out[TD_QC_QUAL_BASES] = qs[tdq::QS_QBASES]; out[TD_QC_QUAL_INVALID] = qs[tdq::QS_QINVALID];
     out[TD_QC_EMPTY_QUAL] = qs[tdq::QS_EMPTYQ]; out[TD_QC_CYCLES] = q->C;
@@ -564,10 +510,10 @@ int td_qc_stats(td_handle *h, uint64_t out[8]) {
 
 int td_qc_fetch(td_handle *h, uint64_t *barcode_out, uint64_t *base_cycle_out, uint64_t *qual_cycle_out, uint64_t *length_out, uint64_t *meanq_out) {
     Qc *q = qc_of(h);
-    if (!q) return td_fail_internal(h ? TD_E_STATE : TD_E_ARG, h ? "td_qc_begin has not been called" : "handle is NULL");
+    if (!q) return tdi::no_state("qc", h, "handle is NULL");
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     unsigned long long qs[tdq::QS_NWORDS];
-    const int rc = qc_sync_stats(q, qs); if (rc) return rc;
+    const int rc = q->sync_stats(qs); if (rc) return rc;
     if (barcode_out) TD_HIPCHK(hipMemcpy(barcode_out, q->d_bar(), q->n_bar() * 8, hipMemcpyDeviceToHost));
     if (base_cycle_out) TD_HIPCHK(hipMemcpy(base_cycle_out, q->d_base(), q->n_base() * 8, hipMemcpyDeviceToHost));
     if (qual_cycle_out) TD_HIPCHK(hipMemcpy(qual_cycle_out, q->d_qual(), q->n_qual() * 8, hipMemcpyDeviceToHost));
@@ -578,10 +524,7 @@ int td_qc_fetch(td_handle *h, uint64_t *barcode_out, uint64_t *base_cycle_out, u
 
 int td_qc_end(td_handle *h) {
     if (!h) return td_fail_internal(TD_E_ARG, "handle is NULL");
-    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    TD_HIPCHK(hipDeviceSynchronize());
-    td_qc_release(h);
-    return TD_OK;
+    return tdi::quiet_reset(h, tdi::QC);
 }
 
 }  // extern "C"

@@ -29,16 +29,14 @@
 #include <vector>
 
 #define TD_INST_ONLY                    // (k_scan_tiles is defined in tagdig.hip's translation unit)
-#include "kernels.hpp"
-#include "piece_sink.hpp"
-#include "td_internal.hpp"
+#include "stream_pass.hpp"
 
 namespace tdr {
 using namespace tdk;
 
 constexpr int CPT = 4;                                   // 16-byte chunks per thread: tiles of 16 KiB, as k_count_lines<4> counts them
 constexpr uint32_t TILE = CPT * BLOCK * 16u;
-static_assert(TILE == 16384, "td_line_prefix (tagdig.hip) counts terminators per 16 KiB tile with k_count_lines<4>");
+static_assert(TILE == tdi::STREAM_TILE, "td_line_prefix (tagdig.hip) counts terminators per 16 KiB tile with k_count_lines<4>");
 constexpr uint32_t LIST_CAP = TILE / 4 + 4;              // read-line starts per tile: every fourth terminator, the buffer's own first line
 constexpr uint32_t MAXLEN = TD_RESCUE_MAX_TAGLEN;        // bases of a tag and of the window
 static_assert(MAXLEN == 128, "the window is four 64-bit words");
@@ -376,79 +374,44 @@ constexpr size_t RESCUE_LDS_INDEX = 40 * 1024;            // the barcode index's
 // host rule costs has not been measured.
 constexpr uint32_t RESCUE_DEFAULT_MAX_RUN = 4096;
 
-struct Rescue {
-    td_handle *h = nullptr;
-    uint32_t barnum = 0, ntags = 0, K = 0, P = 0, bblob_bytes = 0, off_bmeta = 0, off_bdir = 0;
+struct Rescue : tdi::StreamPass {
+    uint32_t barnum = 0, ntags = 0, K = 0, P = 0;
     uint32_t dir_mask = 0, max_probe = 0, longest_run = 0;
-    tdi::DevBuf<uint32_t> d_bblob, d_taglen, d_ent, d_matrix;
+    tdi::DevBuf<uint32_t> d_taglen, d_ent, d_matrix;
     tdi::DevBuf<uint4> d_tagw, d_dir;
     tdi::DevBuf<unsigned long long> d_words;  // positions[128] | RS_*
-    bool used = false;                        // something has been added since td_rescue_begin
-    int dead = 0;                             // the code every call answers with after a failure, until td_rescue_begin
-    std::string dead_msg;
     size_t cells() const { return (size_t)barnum * ntags; }
     unsigned long long *d_pos() const { return d_words.p; }
     unsigned long long *d_rs() const { return d_words.p + tdr::MAXLEN; }
+
+    int zero(hipStream_t s) override {
+        TD_HIPCHK(hipMemsetAsync(d_matrix.p, 0, std::max<size_t>(cells(), 1) * 4, s));
+        TD_HIPCHK(hipMemsetAsync(d_words.p, 0, (tdr::MAXLEN + tdr::RS_NWORDS) * 8, s));
+        return TD_OK;
+    }
+
+    int launch(const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, hipStream_t stream,
+               const unsigned long long *cursor_in, unsigned long long *cursor_out) override {
+        tdr::RescueParams p{};
+        const int rc = prologue(d_fastq, nbytes, max_reads, stream, d_rs() + tdr::RS_TOTAL, p.prefix, p.ntiles);
+        if (rc || !p.ntiles) return rc;
+        p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
+        p.limit_line = limit_line(max_reads);
+        p.bblob = d_bblob.p; p.bblob_bytes = bblob_bytes; p.off_bmeta = off_bmeta; p.off_bdir = off_bdir;
+        p.tagw = d_tagw.p; p.taglen = d_taglen.p; p.dir = d_dir.p; p.ent = d_ent.p;
+        p.ntags = ntags; p.nparts = K + 1; p.P = P; p.K = K; p.dir_mask = dir_mask; p.max_probe = max_probe;
+        p.matrix = d_matrix.p; p.positions = d_pos(); p.rs = d_rs();
+        p.cursor_in = cursor_in; p.cursor_out = cursor_out;
+        hipLaunchKernelGGL(tdr::k_rescue, dim3(grid(p.ntiles, 8, true)), dim3(tdk::BLOCK), bblob_bytes, stream, p);
+        TD_HIPCHK(hipGetLastError());
+        return TD_OK;
+    }
+
+    // after a synchronisation: what the kernel flagged
+    int sync_stats(unsigned long long rs[tdr::RS_NWORDS]) { return sync_words(rs, d_rs(), tdr::RS_NWORDS, tdr::RS_ERR); }
 };
 
-Rescue *rescue_of(td_handle *h) { return h ? (Rescue *)*td_handle_rescue(h) : nullptr; }
-
-int rescue_zero(Rescue *r, hipStream_t s) {
-    TD_HIPCHK(hipMemsetAsync(r->d_matrix.p, 0, std::max<size_t>(r->cells(), 1) * 4, s));
-    TD_HIPCHK(hipMemsetAsync(r->d_words.p, 0, (tdr::MAXLEN + tdr::RS_NWORDS) * 8, s));
-    TD_HIPCHK(hipStreamSynchronize(s));
-    r->used = false;
-    return TD_OK;
-}
-
-int rescue_launch(Rescue *r, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, hipStream_t stream,
-                  const unsigned long long *cursor_in, unsigned long long *cursor_out) {
-    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
-    if (((uintptr_t)d_fastq & 15) != 0) return td_fail_internal(TD_E_ARG, "device FASTQ pointer must be 16-byte aligned");
-    if (nbytes == 0) return TD_OK;
-    if (max_reads == 0) max_reads = 1;
-    r->used = true;
-    const uint64_t *prefix = nullptr;
-    int rc = td_line_prefix(r->h, d_fastq, nbytes, (void *)stream, &prefix, r->d_rs() + tdr::RS_TOTAL); if (rc) return rc;
-    tdr::RescueParams p{};
-    p.buf = (const uint8_t *)d_fastq; p.nbytes = nbytes; p.first_line = first_line;
-    // last read line that is looked at: ordinal r (1-based) sits on line 4 (r - 1) + 1
-    p.limit_line = max_reads >= (1ull << 60) ? ~0ull - 8 : 4 * (max_reads - 1) + 1;
-    p.prefix = prefix; p.ntiles = (uint32_t)((nbytes + tdr::TILE - 1) / tdr::TILE);
-    p.bblob = r->d_bblob.p; p.bblob_bytes = r->bblob_bytes; p.off_bmeta = r->off_bmeta; p.off_bdir = r->off_bdir;
-    p.tagw = r->d_tagw.p; p.taglen = r->d_taglen.p; p.dir = r->d_dir.p; p.ent = r->d_ent.p;
-    p.ntags = r->ntags; p.nparts = r->K + 1; p.P = r->P; p.K = r->K; p.dir_mask = r->dir_mask; p.max_probe = r->max_probe;
-    p.matrix = r->d_matrix.p; p.positions = r->d_pos(); p.rs = r->d_rs();
-    p.cursor_in = cursor_in; p.cursor_out = cursor_out;
-    uint32_t grid = (uint32_t)std::min<uint64_t>(p.ntiles, (uint64_t)td_handle_num_cu(r->h) * 8);
-    const uint32_t cap = td_handle_max_grid(r->h);
-    if (cap) grid = std::min(grid, cap);
-    hipLaunchKernelGGL(tdr::k_rescue, dim3(grid), dim3(tdk::BLOCK), r->bblob_bytes, stream, p);
-    TD_HIPCHK(hipGetLastError());
-    return TD_OK;
-}
-
-// after a synchronisation: what the kernel flagged
-int rescue_sync_stats(Rescue *r, unsigned long long rs[tdr::RS_NWORDS]) {
-    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
-    TD_HIPCHK(hipDeviceSynchronize());
-    TD_HIPCHK(hipMemcpy(rs, r->d_rs(), tdr::RS_NWORDS * 8, hipMemcpyDeviceToHost));
-    if (rs[tdr::RS_ERR] & tdk::ERR_NONASCII) {
-        r->dead = TD_E_NONASCII; r->dead_msg = "non-ASCII byte in a sequence line";
-        return td_fail_internal(r->dead, r->dead_msg.c_str());
-    }
-    return TD_OK;
-}
-
-int sink_piece(void *ctx, const void *d, uint64_t n, uint64_t first_line, uint64_t max_reads, hipStream_t s, const unsigned long long *cin,
-               unsigned long long *cout) {
-    return rescue_launch((Rescue *)ctx, d, n, first_line, max_reads, s, cin, cout);
-}
-int sink_restart(void *ctx) { Rescue *r = (Rescue *)ctx; return rescue_zero(r, (hipStream_t)td_handle_work_stream(r->h)); }
-
-int state_error(td_handle *h, bool args_ok) {
-    return td_fail_internal(h && args_ok ? TD_E_STATE : TD_E_ARG, h && args_ok ? "td_rescue_begin has not been called" : "NULL argument");
-}
+Rescue *rescue_of(td_handle *h) { return tdi::state_of<Rescue>(h, tdi::RESCUE); }
 
 // What td_rescue_begin builds on the host.  No HIP in here.
 struct RescueIndex {
@@ -540,26 +503,13 @@ int rescue_build_index(const std::vector<std::string> &ts, uint32_t K, uint32_t 
 
 extern "C" {
 
-void td_rescue_release(td_handle *h) {
-    void **slot = td_handle_rescue(h);
-    delete (Rescue *)*slot;
-    *slot = nullptr;
-}
-
 int td_rescue_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
                     const char *const *tags, uint32_t n_tags, uint32_t max_mismatch) {
     if (!h || !barcut || !tagoff || !tags) return td_fail_internal(TD_E_ARG, "NULL argument");
     if (max_mismatch < 1 || max_mismatch > 2) return td_fail_internal(TD_E_ARG, "max_mismatch must be 1 or 2");
-    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    TD_HIPCHK(hipDeviceSynchronize());
-    td_rescue_release(h);
-    uint8_t *blob = nullptr;
-    uint32_t bytes = 0, off_bmeta = 0, off_bdir = 0;
-    int rc = td_barcut_blob(barcut, n_barcut, barnum, tagoff, &blob, &bytes, &off_bmeta, &off_bdir);
-    if (rc) return rc;
-    std::vector<uint8_t> bblob(blob, blob + bytes);
-    free(blob);
-    if (bytes > RESCUE_LDS_INDEX) return td_fail_internal(TD_E_LIMIT, "barcode index does not fit the LDS budget");
+    int rc = tdi::quiet_reset(h, tdi::RESCUE); if (rc) return rc;
+    std::unique_ptr<Rescue> r(new Rescue());
+    rc = r->begin(h, barcut, n_barcut, barnum, tagoff, RESCUE_LDS_INDEX); if (rc) return rc;
     std::vector<std::string> ts;
     rc = rescue_check_tags(tags, n_tags, ts); if (rc) return rc;
     const uint32_t opt = td_handle_rescue_max_run(h);
@@ -567,13 +517,9 @@ int td_rescue_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, 
     rc = rescue_build_index(ts, max_mismatch, opt ? opt : RESCUE_DEFAULT_MAX_RUN, ix); if (rc) return rc;
     if ((uint64_t)barnum * n_tags >= (1ull << 32)) return td_fail_internal(TD_E_LIMIT, "rescue matrix beyond 2^32 cells");
 
-    Rescue *r = new Rescue();
-    r->h = h; r->barnum = barnum; r->ntags = n_tags; r->K = max_mismatch; r->P = ix.P;
-    r->bblob_bytes = bytes; r->off_bmeta = off_bmeta; r->off_bdir = off_bdir;
+    r->barnum = barnum; r->ntags = n_tags; r->K = max_mismatch; r->P = ix.P;
     r->dir_mask = ix.dir_slots - 1; r->max_probe = ix.max_probe; r->longest_run = ix.longest_run;
-    hipError_t e = r->d_bblob.alloc((bytes + 3) / 4);
-    if (e == hipSuccess) e = hipMemcpy(r->d_bblob.p, bblob.data(), bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = r->d_tagw.alloc(ix.words.size() / 2);
+    hipError_t e = r->d_tagw.alloc(ix.words.size() / 2);
     if (e == hipSuccess) e = hipMemcpy(r->d_tagw.p, ix.words.data(), ix.words.size() * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = r->d_taglen.alloc(ix.lens.size());
     if (e == hipSuccess) e = hipMemcpy(r->d_taglen.p, ix.lens.data(), ix.lens.size() * 4, hipMemcpyHostToDevice);
@@ -583,42 +529,31 @@ int td_rescue_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, 
     if (e == hipSuccess) e = hipMemcpy(r->d_dir.p, ix.dir.data(), ix.dir.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = r->d_matrix.alloc(r->cells());
     if (e == hipSuccess) e = r->d_words.alloc(tdr::MAXLEN + tdr::RS_NWORDS);
-    if (e != hipSuccess) { delete r; (void)hipGetLastError(); return td_fail_internal(TD_E_HIP, hipGetErrorString(e)); }
-    rc = rescue_zero(r, (hipStream_t)td_handle_work_stream(h));
-    if (rc) { delete r; return rc; }
-    *td_handle_rescue(h) = r;
-    return TD_OK;
+    if (e != hipSuccess) return tdi::StreamPass::hip_failed(e);
+    return tdi::install(r, tdi::RESCUE);
 }
 
 int td_rescue_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream) {
     Rescue *r = rescue_of(h);
-    if (!r) return state_error(h, true);
+    if (!r) return tdi::no_state("rescue", h);
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    return rescue_launch(r, d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
+    return r->launch(d_fastq, nbytes, first_line, max_reads, (hipStream_t)stream, nullptr, nullptr);
 }
 
 int td_rescue_file(td_handle *h, const char *path, uint64_t max_reads) {
     Rescue *r = rescue_of(h);
-    if (!r || !path) return state_error(h, path != nullptr);
-    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
-    const td_piece_sink sink{sink_piece, sink_restart, r, !r->used};
-    int rc = td_stream_file(h, path, max_reads, &sink);
-    if (rc) {
-        if (r->used && !r->dead) {            // the matrix holds a part of the file: never handed out
-            r->dead = rc; r->dead_msg = td_last_error();
-        }
-        return rc;
-    }
+    if (!r || !path) return tdi::no_state("rescue", h && path);
     unsigned long long rs[tdr::RS_NWORDS];
-    return rescue_sync_stats(r, rs);
+    const int rc = r->file(path, max_reads);
+    return rc ? rc : r->sync_stats(rs);
 }
 
 int td_rescue_stats(td_handle *h, uint64_t out[8]) {
     Rescue *r = rescue_of(h);
-    if (!r || !out) return state_error(h, out != nullptr);
+    if (!r || !out) return tdi::no_state("rescue", h && out);
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     unsigned long long rs[tdr::RS_NWORDS];
-    const int rc = rescue_sync_stats(r, rs); if (rc) return rc;
+    const int rc = r->sync_stats(rs); if (rc) return rc;
     out[TD_RESCUE_READS] = rs[tdr::RS_READS]; out[TD_RESCUE_BARCUT] = rs[tdr::RS_BARCUT]; out[TD_RESCUE_EXACT] = rs[tdr::RS_EXACT];
     out[TD_RESCUE_RESCUED1] = rs[tdr::RS_RESC1]; out[TD_RESCUE_RESCUED2] = rs[tdr::RS_RESC2]; out[TD_RESCUE_AMBIGUOUS] = rs[tdr::RS_AMBIG];
     out[TD_RESCUE_NONE] = rs[tdr::RS_NONE]; out[TD_RESCUE_LONGEST_RUN] = r->longest_run;
@@ -627,20 +562,20 @@ int td_rescue_stats(td_handle *h, uint64_t out[8]) {
 
 int td_rescue_work(td_handle *h, uint64_t out[4]) {
     Rescue *r = rescue_of(h);
-    if (!r || !out) return state_error(h, out != nullptr);
+    if (!r || !out) return tdi::no_state("rescue", h && out);
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     unsigned long long rs[tdr::RS_NWORDS];
-    const int rc = rescue_sync_stats(r, rs); if (rc) return rc;
+    const int rc = r->sync_stats(rs); if (rc) return rc;
     out[0] = rs[tdr::RS_PROBES]; out[1] = rs[tdr::RS_VERIFIED]; out[2] = r->P; out[3] = r->max_probe;
     return TD_OK;
 }
 
 int td_rescue_fetch(td_handle *h, uint32_t *rescued_out, uint64_t *positions_out) {
     Rescue *r = rescue_of(h);
-    if (!r) return state_error(h, true);
+    if (!r) return tdi::no_state("rescue", h);
     TD_HIPCHK(hipSetDevice(td_handle_device(h)));
     unsigned long long rs[tdr::RS_NWORDS];
-    const int rc = rescue_sync_stats(r, rs); if (rc) return rc;
+    const int rc = r->sync_stats(rs); if (rc) return rc;
     if (rescued_out && r->cells()) TD_HIPCHK(hipMemcpy(rescued_out, r->d_matrix.p, r->cells() * 4, hipMemcpyDeviceToHost));
     if (positions_out) TD_HIPCHK(hipMemcpy(positions_out, r->d_pos(), tdr::MAXLEN * 8, hipMemcpyDeviceToHost));
     return TD_OK;
@@ -648,19 +583,16 @@ int td_rescue_fetch(td_handle *h, uint32_t *rescued_out, uint64_t *positions_out
 
 int td_rescue_matrix(td_handle *h, void **d_matrix) {
     Rescue *r = rescue_of(h);
-    if (!r || !d_matrix) return state_error(h, d_matrix != nullptr);
-    if (r->dead) return td_fail_internal(r->dead, r->dead_msg.c_str());
+    if (!r || !d_matrix) return tdi::no_state("rescue", h && d_matrix);
+    if (r->dead) return r->answer_dead();
     *d_matrix = r->d_matrix.p;
     return TD_OK;
 }
 
 int td_rescue_end(td_handle *h) {
     if (!h) return td_fail_internal(TD_E_ARG, "handle is NULL");
-    if (!rescue_of(h)) return td_fail_internal(TD_E_STATE, "td_rescue_begin has not been called");
-    TD_HIPCHK(hipSetDevice(td_handle_device(h)));
-    TD_HIPCHK(hipDeviceSynchronize());
-    td_rescue_release(h);
-    return TD_OK;
+    if (!rescue_of(h)) return tdi::no_state("rescue", true);
+    return tdi::quiet_reset(h, tdi::RESCUE);
 }
 
 }  // extern "C"

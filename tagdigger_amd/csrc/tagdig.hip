@@ -143,10 +143,8 @@ struct td_handle {
     Stream side_copy[2]; Event side_done[2];
     int device = 0;
     const td_piece_sink *sink = nullptr;
-    void *census = nullptr;                   // csrc/census.hip's state (td_census_begin .. td_census_end)
-    void *qc = nullptr;                       // csrc/qc.hip's state (td_qc_begin .. td_qc_end)
-    void *places = nullptr;                   // csrc/place.hip's list of the places alive (td_place_sites .. td_place_free)
-    void *rescue = nullptr;                   // csrc/rescue.hip's state (td_rescue_begin .. td_rescue_end)
+    // what census.hip, qc.hip and rescue.hip keep from begin to end, and place.hip's list of the places alive
+    std::unique_ptr<tdi::ModuleState> module[tdi::MODULE_SLOTS];
     uint32_t rescue_max_run = 0;              // td_rescue_begin: the longest run of tags under one part key it takes; 0 = the built-in value
     uint32_t qc_flush_tiles = 0;              // (tests: tiles between two merges of k_qc's LDS tables; 0 = the built-in 4096)
     int num_cu = 256;
@@ -689,11 +687,9 @@ uint32_t td_last_bad_index(void) { return g_bad; }
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_md5_piece(const td_handle *h) { return h->md5_piece; }
 // the "tagnet_max_compares" option (csrc/tagnet.hip), and the index td_last_bad_index reports
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_tagnet_max_compares(const td_handle *h) { return h->tagnet_max_compares; }
-// for csrc/place.hip (hidden): its list's place on the handle, and the "place_max_compares" option
-extern "C" __attribute__((visibility("hidden"))) void **td_handle_places(td_handle *h) { return &h->places; }
+// for csrc/place.hip (hidden): the "place_max_compares" option
 extern "C" __attribute__((visibility("hidden"))) uint64_t td_handle_place_max_compares(const td_handle *h) { return h->place_max_compares; }
-// for csrc/rescue.hip (hidden): its state's place on the handle, and the "rescue_max_run" option
-extern "C" __attribute__((visibility("hidden"))) void **td_handle_rescue(td_handle *h) { return &h->rescue; }
+// for csrc/rescue.hip (hidden): the "rescue_max_run" option
 extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_rescue_max_run(const td_handle *h) { return h->rescue_max_run; }
 extern "C" __attribute__((visibility("hidden"))) void td_set_bad_index(uint32_t idx) { g_bad = idx; }
 // every launch enqueued through this handle (they may be on its own streams) has finished
@@ -703,31 +699,23 @@ extern "C" __attribute__((visibility("hidden"))) int td_handle_wait_work(td_hand
     if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream.s);
     return e == hipSuccess ? TD_OK : fail(TD_E_HIP, std::string("waiting for the handle's streams: ") + hipGetErrorString(e));
 }
-// for csrc/census.hip (hidden): its state's place on the handle, the work stream, the CU count; the barcode + cut-site
-// index by td_set_index's rules; the handle's line counting and tile scan
-extern "C" __attribute__((visibility("hidden"))) void **td_handle_census(td_handle *h) { return &h->census; }
-// for csrc/qc.hip (hidden): its state's place on the handle, and the options "qc_flush_tiles" and "max_grid"
-extern "C" __attribute__((visibility("hidden"))) void **td_handle_qc(td_handle *h) { return &h->qc; }
+// for the modules that keep a state on the handle (hidden): its slot
+std::unique_ptr<tdi::ModuleState> &tdi::module_slot(td_handle *h, ModuleSlot which) { return h->module[which]; }
+// for the streaming modules (csrc/stream_pass.hpp, hidden): the options "qc_flush_tiles" and "max_grid", the work stream,
+// the CU count; the barcode + cut-site index by td_set_index's rules; the handle's line counting and tile scan
 extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_qc_flush_tiles(const td_handle *h) { return h->qc_flush_tiles; }
 extern "C" __attribute__((visibility("hidden"))) uint32_t td_handle_max_grid(const td_handle *h) { return h->max_grid; }
 extern "C" __attribute__((visibility("hidden"))) void *td_handle_work_stream(const td_handle *h) { return (void *)h->work_stream.s; }
 extern "C" __attribute__((visibility("hidden"))) int td_handle_num_cu(const td_handle *h) { return h->num_cu; }
 extern "C" __attribute__((visibility("hidden"))) int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
-                                                                    uint8_t **blob_out, uint32_t *bytes, uint32_t *off_bmeta, uint32_t *off_bdir) {
+                                                                    std::vector<uint8_t> &blob, uint32_t *off_bmeta, uint32_t *off_bdir) {
     std::vector<std::string> bs(n_barcut);
     for (uint32_t i = 0; i < n_barcut; i++) bs[i] = barcut[i];
     Resolver rb(bs, barnum);
     int rc = rb.run();
     if (rc) { g_bad = rb.bad; return fail(rc, rc == TD_E_OVERLAP ? "overlapping barcode+cutsite sequences" : "barcode index build failed"); }
-    std::vector<uint8_t> blob;
     uint32_t max_off = 0;
-    rc = build_barcode_blob(rb.out, barnum, tagoff, blob, *off_bmeta, *off_bdir, max_off);
-    if (rc) return rc;
-    *blob_out = (uint8_t *)malloc(blob.size());
-    if (!*blob_out) return fail(TD_E_INTERNAL, "out of memory");
-    memcpy(*blob_out, blob.data(), blob.size());
-    *bytes = (uint32_t)blob.size();
-    return TD_OK;
+    return build_barcode_blob(rb.out, barnum, tagoff, blob, *off_bmeta, *off_bdir, max_off);
 }
 // for census.hip and qc.hip (they assert that their tile is this one): the line prefix over 16 KiB tiles -> *prefix
 extern "C" __attribute__((visibility("hidden"))) int td_line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, void *s, const uint64_t **prefix,
@@ -771,10 +759,6 @@ void td_destroy(td_handle *h) {
     handle_gone();
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    td_census_release(h);
-    td_qc_release(h);
-    td_place_release(h);
-    td_rescue_release(h);
     delete h;
 }
 
@@ -3230,6 +3214,7 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
     if (nbar == 0) return fail(TD_E_EMPTY, "empty barcode list");
     const std::string cs(cutsite);
     std::vector<std::string> barcut(nbar);
+    std::vector<const char *> barcut_p(nbar);
     std::vector<uint32_t> barlen(nbar);
     h->sp_barcodes.assign(nbar, std::string());
     for (uint32_t i = 0; i < nbar; i++) {
@@ -3239,12 +3224,9 @@ int td_set_splitter(td_handle *h, const char *const *barcodes, uint32_t nbar, co
         barlen[i] = (uint32_t)h->sp_barcodes[i].size();
         if (barcut[i].empty()) return fail(TD_E_LIMIT, "empty barcode with an empty cut site is not supported by the splitter");
     }
-    Resolver rb(barcut, nbar);
-    int rc = rb.run();
-    if (rc) { g_bad = rb.bad; return fail(rc, rc == TD_E_OVERLAP ? "overlapping barcode+cutsite sequences" : "barcode index build failed"); }
+    for (uint32_t i = 0; i < nbar; i++) barcut_p[i] = barcut[i].c_str();
     std::vector<uint8_t> blob;
-    uint32_t max_off = 0;
-    rc = build_barcode_blob(rb.out, nbar, barlen.data(), blob, h->sp_off_bmeta, h->sp_off_bdir, max_off);
+    int rc = td_barcut_blob(barcut_p.data(), nbar, nbar, barlen.data(), blob, &h->sp_off_bmeta, &h->sp_off_bdir);
     if (rc) return rc;
     h->sp_bblob_bytes = (uint32_t)blob.size();
     if ((size_t)4 * tdk::BLOCK * 2 + 64 + blob.size() > LDS_BUDGET) return fail(TD_E_LIMIT, "barcode index does not fit the LDS budget");

@@ -1,15 +1,17 @@
 // What the library's translation units share on the host side and the C-ABI does not show ("The modules
-// beside tagdig.hip"): the hooks into the handle that tagdig.hip and census.hip define, the check macro for HIP calls,
-// and the owners of the device buffers, pinned buffers, events and streams that the handle keeps or an entry point holds
-// while it runs (nothing else in the library frees one).  Every module beside tagdig.hip includes this header; tagdig.hip
-// and census.hip include it too, so that a hook's definition is checked against the declaration its callers see.
+// beside tagdig.hip"): the hooks into the handle that tagdig.hip defines, the check macro for HIP calls, the owners of the
+// device buffers, pinned buffers, events and streams that the handle keeps or an entry point holds while it runs (nothing
+// else in the library frees one), and the base of a module's state on the handle.  Every module beside tagdig.hip includes
+// this header; tagdig.hip includes it too, so that a hook's definition is checked against the declaration its callers see.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "../../include/tagdig.h"
 
@@ -30,32 +32,18 @@ TD_HIDDEN uint64_t td_handle_tagnet_max_compares(const td_handle *h);
 TD_HIDDEN int td_stage_thread_count(void);
 // tagdig.hip: every launch enqueued through this handle (they may be on its own streams) has finished
 TD_HIDDEN int td_handle_wait_work(td_handle *h);
-// tagdig.hip, for census.hip: the census' place on the handle; the barcode + cut-site index by td_set_index's rules
-// (*blob_out is malloc'ed); terminators before the end of every 16 KiB tile -> *prefix (the handle's scratch, good until
-// its next launch), their total -> *d_total, asynchronous on `s`; a file's pieces through the handle's readers to `sink`
-TD_HIDDEN void **td_handle_census(td_handle *h);
-TD_HIDDEN int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff, uint8_t **blob_out,
-                             uint32_t *bytes, uint32_t *off_bmeta, uint32_t *off_bdir);
+// tagdig.hip, for the streaming modules (stream_pass.hpp): the barcode + cut-site index by td_set_index's rules; terminators
+// before the end of every 16 KiB tile -> *prefix (the handle's scratch, good until its next launch), their total ->
+// *d_total, asynchronous on `s`; a file's pieces through the handle's readers to `sink`; the option "max_grid" (0: not set)
+TD_HIDDEN int td_barcut_blob(const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff, std::vector<uint8_t> &blob,
+                             uint32_t *off_bmeta, uint32_t *off_bdir);
 TD_HIDDEN int td_line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, void *s, const uint64_t **prefix, unsigned long long *d_total);
 TD_HIDDEN int td_stream_file(td_handle *h, const char *path, uint64_t max_reads, const td_piece_sink *sink);
-// census.hip, for td_destroy: frees the handle's census, if any
-TD_HIDDEN void td_census_release(td_handle *h);
-// tagdig.hip, for qc.hip: the QC's place on the handle; the options "qc_flush_tiles" and "max_grid" (0: not set)
-TD_HIDDEN void **td_handle_qc(td_handle *h);
-TD_HIDDEN uint32_t td_handle_qc_flush_tiles(const td_handle *h);
 TD_HIDDEN uint32_t td_handle_max_grid(const td_handle *h);
-// qc.hip, for td_destroy: frees the handle's QC state, if any
-TD_HIDDEN void td_qc_release(td_handle *h);
-// tagdig.hip, for place.hip: the list of places' place on the handle; the option "place_max_compares" (0: not set)
-TD_HIDDEN void **td_handle_places(td_handle *h);
+// tagdig.hip: the options "qc_flush_tiles" (qc.hip), "place_max_compares" (place.hip) and "rescue_max_run" (rescue.hip); 0: not set
+TD_HIDDEN uint32_t td_handle_qc_flush_tiles(const td_handle *h);
 TD_HIDDEN uint64_t td_handle_place_max_compares(const td_handle *h);
-// place.hip, for td_destroy: frees every place the handle still owns
-TD_HIDDEN void td_place_release(td_handle *h);
-// tagdig.hip, for rescue.hip: the rescue's place on the handle; the option "rescue_max_run" (0: not set)
-TD_HIDDEN void **td_handle_rescue(td_handle *h);
 TD_HIDDEN uint32_t td_handle_rescue_max_run(const td_handle *h);
-// rescue.hip, for td_destroy: frees the handle's rescue, if any
-TD_HIDDEN void td_rescue_release(td_handle *h);
 }
 
 // a failed HIP call ends the calling function with TD_E_HIP and "<the call as written>: <HIP's text>"
@@ -143,5 +131,13 @@ template <int N> struct Events {
         return hipEventElapsedTime(&f, e[a], e[b]) == hipSuccess ? f : 0.0f;
     }
 };
+
+// What a module keeps on the handle between its entry points derives from this.  The handle holds one per slot in a
+// std::unique_ptr declared behind its streams: td_destroy frees a state left open like every other member, and a module
+// resets its slot at its end and at a second begin.
+struct ModuleState { virtual ~ModuleState() = default; };
+enum ModuleSlot { CENSUS, QC, PLACES, RESCUE, MODULE_SLOTS };
+std::unique_ptr<ModuleState> &module_slot(td_handle *h, ModuleSlot which);      // tagdig.hip
+template <typename T> T *state_of(td_handle *h, ModuleSlot which) { return h ? static_cast<T *>(module_slot(h, which).get()) : nullptr; }
 
 }  // namespace tdi

@@ -280,6 +280,33 @@ def test_exact_maximum_load_then_limit_through_the_file_route(eng, tmp_path):
         assert L.td_census_end(eng._h) == 0
 
 
+def test_nonascii_through_the_file_route_latches_until_begin(eng, tmp_path):
+    from tagdigger_amd import _binding as B
+    from tagdigger_amd.engine import census_index, _c_strings
+    L = B.load()
+    good = fastq(["ACGTTGCAG" + "ACGTTGCATTGACCAGTTAC"])
+    bad = write(tmp_path, "bad.fq", good + b"@x\nACGTTGCAGAC\xe9TTGCATTGACCAGTTAC\n+\nI\n")
+    barcut, barnum, baroff = census_index(["ACGT"], "TGCAG")
+
+    def begin():
+        assert L.td_census_begin(eng._h, _c_strings(barcut), len(barcut), barnum, (C.c_uint32 * 1)(*baroff), 20, 1024) == 0
+    begin()
+    try:
+        assert L.td_census_file(eng._h, bad.encode(), 2 ** 62) == -8                  # TD_E_NONASCII
+        msg = L.td_last_error()
+        st = (C.c_uint64 * 8)()
+        for _ in range(2):
+            assert L.td_census_stats(eng._h, st) == -8 and L.td_last_error() == msg
+        n = C.c_uint64(5)
+        assert L.td_census_fetch(eng._h, 1, None, None, 0, C.byref(n)) == -8 and n.value == 0 and L.td_last_error() == msg
+        assert L.td_census_file(eng._h, write(tmp_path, "good.fq", good).encode(), 2 ** 62) == -8 and L.td_last_error() == msg
+        begin()                                                                       # begun again: usable
+        assert L.td_census_file(eng._h, write(tmp_path, "good.fq", good).encode(), 2 ** 62) == 0
+        assert L.td_census_stats(eng._h, st) == 0 and list(st[:6]) == [1, 1, 0, 0, 1, 1]
+    finally:
+        assert L.td_census_end(eng._h) == 0
+
+
 def test_fetch_without_a_census_is_a_state_error(eng):
     from tagdigger_amd import TagdigError
     with pytest.raises(TagdigError) as ei:
