@@ -945,8 +945,13 @@ int td_kernel_time_ms(td_handle *h, double *ms_per_launch, uint32_t *launches_ou
 /* The same per launch: out[0 .. min(launches, capacity)) in launch order; *launches_out = how many were written. */
 int td_kernel_times_ms(td_handle *h, double *out, uint32_t capacity, uint32_t *launches_out);
 
-/* Diagnostic counters (24 x uint64).  All zero in the shipped build; the phase-stamp
- * build (make prof -> libtagdig_prof.so) fills [0..7] with shader-clock cycles per phase. */
+/* Diagnostic counters (24 x uint64).  The device's slots are all zero in the shipped build; the phase-stamp
+ * build (make prof -> libtagdig_prof.so) fills [0..19] with shader-clock cycles per phase (and so writes over [11]).  Two slots are the host's:
+ *   [11]  length of the free-running path's fix-up queue in the last count launch
+ *   [20]  where the last line prefix (td_split_device, td_count_and_split_device, td_count_lines_device) took its
+ *         per-tile terminator counts from: 1 = counted from the bytes (k_count_lines), 2 = taken from the tile records
+ *         the count pass of td_count_and_split_device had just left (k_info_counts); 0 = no prefix yet.  Nothing
+ *         depends on it (tests: which source they exercised). */
 int td_debug_counters(td_handle *h, uint64_t out[24]);
 
 /* ---- device memory helpers (so a binding needs no other GPU runtime) ------- */

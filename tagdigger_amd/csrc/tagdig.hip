@@ -172,6 +172,7 @@ struct td_handle {
     bool sp_sites_acgt = false;
     int last_fast_tile_kb = 0;                // tile size of the last free-running count launch (0: it took another path)
     uint32_t last_fast_ntiles = 0;
+    int last_prefix_source = 0;               // line_prefix's last run: 1 = counted from the bytes, 2 = the count pass's tile records (0: none yet)
     uint32_t sp_gcap = 4;                     // entries per (barcode, last two bases) group of entries16
     std::vector<uint64_t> split_win;          // td_split_file's: {with barcode, clipped} per window of 50 000 reads
     DevBuf<unsigned long long> d_win;
@@ -604,7 +605,9 @@ int line_prefix(td_handle *h, const void *d_fastq, uint64_t nbytes, int tile_kb,
     TD_HIPCHK(h->d_tilecounts.ensure(nt));
     TD_HIPCHK(h->d_state.ensure(nt));
     const uint32_t g = (uint32_t)std::min<uint64_t>(nt, (uint64_t)h->num_cu * 8);
-    if (counted && tile_kb == 24 && h->last_fast_tile_kb == 24 && h->last_fast_ntiles == (uint32_t)nt)
+    const bool from_records = counted && tile_kb == 24 && h->last_fast_tile_kb == 24 && h->last_fast_ntiles == (uint32_t)nt;
+    h->last_prefix_source = from_records ? 2 : 1;         // (td_debug_counters [20]: tests ask which one they ran)
+    if (from_records)
         hipLaunchKernelGGL(tdk::k_info_counts, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, s, h->d_tileinfo.p, (uint32_t)nt, h->d_tilecounts.p);
     else if (tile_kb == 24) hipLaunchKernelGGL((tdk::k_count_lines<6>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
     else hipLaunchKernelGGL((tdk::k_count_lines<4>), dim3(g), dim3(tdk::BLOCK), 0, s, (const uint8_t *)d_fastq, nbytes, (uint32_t)nt, h->d_tilecounts.p);
@@ -2617,6 +2620,7 @@ int td_debug_counters(td_handle *h, uint64_t out[24]) {
         TD_HIPCHK(hipMemcpy(&nf, h->d_nfix.p, 4, hipMemcpyDeviceToHost));
         out[11] = nf;
     }
+    out[20] = (uint64_t)h->last_prefix_source;      // host-side: where the last line prefix took its per-tile counts from
     return TD_OK;
 }
 

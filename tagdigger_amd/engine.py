@@ -440,6 +440,11 @@ class Engine:
         B.check(self._L.td_split_kernel_in_use(self._h, C.byref(k)))
         return k.value
 
+    def split_prefix_source(self):
+        """td_debug_counters [20]: where the last line prefix took its per-tile terminator counts from -- 1 counted from the
+        bytes, 2 the tile records of the count pass that count_and_split_device had just enqueued; 0 before any."""
+        return self.debug_counters()[20]
+
     def split_device(self, d_ptr, nbytes, first_line=0, stream=0):
         """[(barcode index or -1, findAdapterSeq value), ...] for the sequence lines of a device buffer."""
         import numpy as np

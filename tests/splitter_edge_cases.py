@@ -493,7 +493,11 @@ def ascii_twin(data):
 
 def expected(setname, data):
     """The oracle's decisions for every sequence line of the buffer, as the kernels report them."""
-    st = SETS[setname]
+    return expected_for(SETS[setname], data)
+
+
+def expected_for(st, data):
+    """The same for any Set (tests/fused_cases.py: the ring inputs' barcodes with the Hall adapter)."""
     want = []
     po.barcode_splitter_bytes(completed(data), st.barcodes, st.cutsite, st.adapter, decisions=want)
     n = seq_line_count(data, 0)             # (a last record that ends within its header line was completed too)
