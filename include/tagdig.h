@@ -516,6 +516,65 @@ int td_rescue_fetch(td_handle *h, uint32_t *rescued_out, uint64_t *positions_out
 int td_rescue_matrix(td_handle *h, void **d_matrix);
 int td_rescue_end(td_handle *h);
 
+/* ---- barcode rescue (csrc/bcrescue.hip; tagdigger_amd/tagdigger_fun.py rescue_barcodes_fastq drives these) --------------
+ *
+ * The reads every other pass drops because their first bases are no stored barcode + cut site entry, brought back when
+ * they lie one or two substitutions from the entries of exactly one barcode.  The entries are the
+ * strings the index build leaves (of duplicates the first; an entry that extends an earlier one is shadowed); entry k of
+ * the list belongs to row k % barnum.  Per read line (stripped, upper-cased), reads += 1, then:
+ *   1  an entry is an exact prefix of the read (the counter's lookup): exact += 1, nothing else -- the read is the
+ *      counter's;
+ *   2  else every entry e of L_e <= len(read) bases is a candidate at d(e) = the positions i < L_e with read[i] != e[i],
+ *      a character outside ACGT mismatching every base; m = the smallest d (m >= 1);
+ *   3  m > max_mismatch, or no candidate: none += 1;
+ *   4  the entries at distance m belong to more than one row: ambiguous += 1.  Cut-site variants of one row that tie are
+ *      no tie: the earliest of them in the list is "the entry";
+ *   5  else the read is rescued into that row b: rescued<m> += 1, row_rescued[b][m - 1] += 1, positions[i] += 1 for
+ *      every mismatching i of the entry, and the counter's tag step: the one stored tag that is a prefix of the read from
+ *      tagoff[b] on, all of its characters in ACGT, gives matrix[b][tag] += 1 and tagged += 1.
+ * So reads == exact + rescued1 + rescued2 + ambiguous + none.  The state is independent of the count index and of a
+ * census, a QC or a tag rescue on the same handle.
+ *
+ * td_bcrescue_begin: barcut[n_barcut], barnum and tagoff[barnum] (at most 63) as td_set_index takes them, with its
+ *   errors; tags[n_tags] under td_rescue_begin's conditions, with its errors and td_last_bad_index; max_mismatch 1 or 2.
+ *   Every surviving entry must be longer than 2 * max_mismatch bases: else TD_E_LIMIT with a message that begins
+ *   "barcode rescue: entry" (the row in td_last_bad_index).  TD_E_LIMIT too when the index and the entry list -- 16-byte
+ *   rounded (8 ne + 8-byte rounded (4 ne) + 2048) + 2 n bytes for n distinct entries in ne directory slots, ne == n when
+ *   no entry is shorter than 5 bases -- exceed 40 KiB of a workgroup's LDS.  The matrix and the counters start at zero.
+ *   A barcode rescue begun before is dropped.
+ * td_bcrescue_device: one pass over a resident buffer (arguments as td_count_device's).  Asynchronous, accumulates; ONE
+ *   stream in flight per handle.  "max_grid" caps the grid.
+ * td_bcrescue_file: a whole file, plain, gzip or BGZF, through td_count_file's readers.  Synchronous, accumulates.
+ * td_bcrescue_stats: out[TD_BCRESCUE_*], cumulative since td_bcrescue_begin.  Synchronises.
+ * td_bcrescue_fetch: matrix_out[barnum * n_tags] (uint32_t, row b column t), row_rescued_out[barnum * 2] and
+ *   positions_out[32]; each may be NULL.  Synchronises.
+ * td_bcrescue_matrix: the matrix where it lies in device memory, for callers that add it to a count matrix there; good
+ *   until td_bcrescue_end or the next td_bcrescue_begin.
+ * td_bcrescue_end: frees the state; TD_E_STATE without one.  td_destroy frees a state left open.
+ * Errors: TD_E_NONASCII as the counter's.  After it, and after a td_bcrescue_file that failed part-way, every call
+ *   answers with that error until td_bcrescue_begin. */
+enum {
+    TD_BCRESCUE_READS = 0,               /* read lines looked at                                                  */
+    TD_BCRESCUE_EXACT = 1,               /* ... that begin with an entry: the counter's                           */
+    TD_BCRESCUE_RESCUED1 = 2,            /* ... one mismatch from the entries of exactly one row                  */
+    TD_BCRESCUE_RESCUED2 = 3,            /* ... two mismatches from the entries of exactly one row                */
+    TD_BCRESCUE_AMBIGUOUS = 4,           /* ... whose smallest distance entries of several rows attain            */
+    TD_BCRESCUE_NONE = 5,                /* ... with no entry within max_mismatch                                 */
+    TD_BCRESCUE_TAGGED = 6,              /* rescued reads that carry a stored tag: the sum of the matrix          */
+    TD_BCRESCUE_MIN_ENTRY_DISTANCE = 7,  /* the smallest distance between two entries of different rows, over the
+                                            shorter one's length (known at begin; 64 without two rows): at or below
+                                            max_mismatch, exact reads of one sample lie one error from another     */
+    TD_BCRESCUE_POSITIONS = 32
+};
+int td_bcrescue_begin(td_handle *h, const char *const *barcut, uint32_t n_barcut, uint32_t barnum, const uint32_t *tagoff,
+                      const char *const *tags, uint32_t n_tags, uint32_t max_mismatch);
+int td_bcrescue_device(td_handle *h, const void *d_fastq, uint64_t nbytes, uint64_t first_line, uint64_t max_reads, void *stream);
+int td_bcrescue_file(td_handle *h, const char *path, uint64_t max_reads);
+int td_bcrescue_stats(td_handle *h, uint64_t out[8]);
+int td_bcrescue_fetch(td_handle *h, uint32_t *matrix_out, uint64_t *row_rescued_out, uint64_t *positions_out);
+int td_bcrescue_matrix(td_handle *h, void **d_matrix);
+int td_bcrescue_end(td_handle *h);
+
 /* ---- tag network (csrc/tagnet.hip; tagdigger_amd/tagdigger_fun.py tag_network and census_markers drive these) --------
  *
  * From a census to markers without a reference genome (the UNEAK network filter).  Input: n tags of one

@@ -183,6 +183,13 @@ def load():
     sig("td_rescue_fetch", i32, vp, vp, vp)
     sig("td_rescue_matrix", i32, vp, C.POINTER(vp))
     sig("td_rescue_end", i32, vp)
+    sig("td_bcrescue_begin", i32, vp, pp, u32, u32, C.POINTER(u32), pp, u32, u32)
+    sig("td_bcrescue_device", i32, vp, vp, u64, u64, u64, vp)
+    sig("td_bcrescue_file", i32, vp, C.c_char_p, u64)
+    sig("td_bcrescue_stats", i32, vp, C.POINTER(u64))
+    sig("td_bcrescue_fetch", i32, vp, vp, vp, vp)
+    sig("td_bcrescue_matrix", i32, vp, C.POINTER(vp))
+    sig("td_bcrescue_end", i32, vp)
     sig("td_tagnet_build", i32, vp, vp, vp, u32, u32, u32, C.POINTER(vp), C.POINTER(u64), dp)
     sig("td_tagnet_edges", i32, vp, vp, i32, vp, u64, C.POINTER(u64))
     sig("td_tagnet_pairs", i32, vp, vp, vp, u64, C.POINTER(u64))
@@ -222,6 +229,7 @@ EXPORTS = [
     "td_qc_begin", "td_qc_device", "td_qc_file", "td_qc_stats", "td_qc_fetch", "td_qc_end",
     "td_rescue_begin", "td_rescue_device", "td_rescue_file", "td_rescue_stats", "td_rescue_work", "td_rescue_fetch", "td_rescue_matrix",
     "td_rescue_end",
+    "td_bcrescue_begin", "td_bcrescue_device", "td_bcrescue_file", "td_bcrescue_stats", "td_bcrescue_fetch", "td_bcrescue_matrix", "td_bcrescue_end",
     "td_tagnet_build", "td_tagnet_edges", "td_tagnet_pairs", "td_tagnet_degrees", "td_tagnet_free",
     "td_place_sites", "td_place_loci", "td_place_tags", "td_place_free",
     "td_geno_call", "td_relate_joint", "td_ld_pairs", "td_ld_last_times",

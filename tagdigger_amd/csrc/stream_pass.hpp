@@ -1,5 +1,5 @@
-// The streaming pass written once ("The modules beside tagdig.hip"): what census.hip, qc.hip and rescue.hip
-// share on the host side around their one persistent kernel over 16 KiB tiles.  A module's state derives from
+// The streaming pass written once ("The modules beside tagdig.hip"): what census.hip, qc.hip, rescue.hip and
+// bcrescue.hip share on the host side around their one persistent kernel over 16 KiB tiles.  A module's state derives from
 // tdi::StreamPass and supplies its launch and its zeroing; everything a module does differently it passes as an argument
 // or keeps in its own file -- nothing in here asks which module is calling.
 #pragma once
@@ -48,6 +48,10 @@ struct StreamPass : ModuleState {
         std::vector<uint8_t> blob;
         const int rc = td_barcut_blob(barcut, n_barcut, barnum, tagoff, blob, &off_bmeta, &off_bdir); if (rc) return rc;
         if (blob.size() > lds_budget) return td_fail_internal(TD_E_LIMIT, "barcode index does not fit the LDS budget");
+        return upload(blob);
+    }
+    // what the kernel copies into LDS, into device memory (a module that appends to the index calls this itself)
+    int upload(const std::vector<uint8_t> &blob) {
         bblob_bytes = (uint32_t)blob.size();
         hipError_t e = d_bblob.alloc((blob.size() + 3) / 4);
         if (e == hipSuccess) e = hipMemcpy(d_bblob.p, blob.data(), blob.size(), hipMemcpyHostToDevice);

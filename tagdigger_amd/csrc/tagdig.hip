@@ -143,7 +143,7 @@ struct td_handle {
     Stream side_copy[2]; Event side_done[2];
     int device = 0;
     const td_piece_sink *sink = nullptr;
-    // what census.hip, qc.hip and rescue.hip keep from begin to end, and place.hip's list of the places alive
+    // what census.hip, qc.hip, rescue.hip and bcrescue.hip keep from begin to end, and place.hip's list of the places alive
     std::unique_ptr<tdi::ModuleState> module[tdi::MODULE_SLOTS];
     uint32_t rescue_max_run = 0;              // td_rescue_begin: the longest run of tags under one part key it takes; 0 = the built-in value
     uint32_t qc_flush_tiles = 0;              // (tests: tiles between two merges of k_qc's LDS tables; 0 = the built-in 4096)

@@ -136,7 +136,7 @@ template <int N> struct Events {
 // std::unique_ptr declared behind its streams: td_destroy frees a state left open like every other member, and a module
 // resets its slot at its end and at a second begin.
 struct ModuleState { virtual ~ModuleState() = default; };
-enum ModuleSlot { CENSUS, QC, PLACES, RESCUE, MODULE_SLOTS };
+enum ModuleSlot { CENSUS, QC, PLACES, RESCUE, BCRESCUE, MODULE_SLOTS };
 std::unique_ptr<ModuleState> &module_slot(td_handle *h, ModuleSlot which);      // tagdig.hip
 template <typename T> T *state_of(td_handle *h, ModuleSlot which) { return h ? static_cast<T *>(module_slot(h, which).get()) : nullptr; }
 

@@ -81,6 +81,8 @@ INDEX_INFO = ("W", "m_bases", "buckets", "spb", "nshort", "displaced", "longest"
 CENSUS_STATS = ("reads", "barcut", "short", "ambiguous", "counted", "distinct", "slots", "max_keys")
 RESCUE_STATS = ("reads", "barcut", "exact", "rescued1", "rescued2", "ambiguous", "none", "longest_run")     # TD_RESCUE_* slots
 RESCUE_MAX_TAGLEN = 128     # TD_RESCUE_MAX_TAGLEN
+BCRESCUE_STATS = ("reads", "exact", "rescued1", "rescued2", "ambiguous", "none", "tagged", "min_entry_distance")     # TD_BCRESCUE_* slots
+BCRESCUE_POSITIONS = 32     # TD_BCRESCUE_POSITIONS
 QC_STATS = ("reads", "barcut", "qual_lines", "bases", "qual_bases", "qual_invalid", "empty_qual", "max_cycles")     # TD_QC_* slots
 
 
@@ -661,6 +663,57 @@ class Engine:
     def rescue_end(self):
         B.check(self._L.td_rescue_end(self._h))
         self._rescue_shape = (0, 0)
+
+    # ------------------------------------------------------------------ barcode rescue (td_bcrescue_*; csrc/bcrescue.hip)
+    def bcrescue_begin(self, barcodes, tags, cutsite="TGCAG", max_mismatch=1):
+        """Fresh barcode-rescue results for these barcodes and tags (set_index's set-up), at 1 or 2 mismatches."""
+        barcut, barnum, tagoff, stored = rescue_index(barcodes, tags, cutsite)
+        self._bcrescue_begin_lists(barcut, barnum, tagoff, stored, max_mismatch)
+
+    def _bcrescue_begin_lists(self, barcut, barnum, tagoff, tags, max_mismatch=1):
+        """td_bcrescue_begin as include/tagdig.h states it; called directly only by tests that need an entry list, an
+        offset or a tag list bcrescue_begin never derives."""
+        self._bcrescue_shape = (0, 0)
+        B.check(self._L.td_bcrescue_begin(self._h, _c_strings(barcut), len(barcut), barnum, (C.c_uint32 * max(1, barnum))(*tagoff),
+                                          _c_strings(tags), len(tags), int(max_mismatch)))
+        self._bcrescue_shape = (barnum, len(tags))
+
+    def bcrescue_device(self, d_ptr, nbytes, first_line=0, maxreads=5e9, stream=0):
+        """Enqueue one barcode-rescue pass over a FASTQ buffer already in HBM (asynchronous, accumulates)."""
+        B.check(self._L.td_bcrescue_device(self._h, C.c_void_p(d_ptr), nbytes, first_line, effective_maxreads(maxreads),
+                                           C.c_void_p(stream) if stream else None))
+
+    def bcrescue_file(self, path, maxreads=5e9):
+        """The barcode rescue over a file, plain or gzip by name, through count_file's readers (accumulates)."""
+        open(path, 'rb').close()
+        B.check(self._L.td_bcrescue_file(self._h, os.fsencode(path), effective_maxreads(maxreads)))
+
+    def bcrescue_stats(self):
+        """{reads, exact, rescued1, rescued2, ambiguous, none, tagged, min_entry_distance}, cumulative since bcrescue_begin."""
+        st = (C.c_uint64 * 8)()
+        B.check(self._L.td_bcrescue_stats(self._h, st))
+        return dict(zip(BCRESCUE_STATS, (int(x) for x in st)))
+
+    def bcrescue_fetch(self):
+        """(matrix uint32 [barnum, ntags], row_rescued uint64 [barnum, 2], positions uint64 [32]) as numpy arrays."""
+        import numpy as np
+        barnum, ntags = getattr(self, "_bcrescue_shape", (0, 0))
+        matrix = np.zeros((barnum, ntags), dtype=np.uint32)
+        rows = np.zeros((barnum, 2), dtype=np.uint64)
+        positions = np.zeros(BCRESCUE_POSITIONS, dtype=np.uint64)
+        B.check(self._L.td_bcrescue_fetch(self._h, C.c_void_p(matrix.ctypes.data) if matrix.size else None,
+                                          C.c_void_p(rows.ctypes.data) if rows.size else None, C.c_void_p(positions.ctypes.data)))
+        return matrix, rows, positions
+
+    def bcrescue_matrix(self):
+        """The device address of the matrix (uint32 [barnum, ntags]); good until bcrescue_end or the next begin."""
+        p = C.c_void_p()
+        B.check(self._L.td_bcrescue_matrix(self._h, C.byref(p)))
+        return p.value
+
+    def bcrescue_end(self):
+        B.check(self._L.td_bcrescue_end(self._h))
+        self._bcrescue_shape = (0, 0)
 
     # ------------------------------------------------------------------ tag network (td_tagnet_*; csrc/tagnet.hip)
     def tagnet_build(self, seqs, counts, taglen, ratio_ppm):

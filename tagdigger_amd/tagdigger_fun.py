@@ -2963,6 +2963,212 @@ def writeRescueStats(filename, libraries, results):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Barcode rescue (csrc/bcrescue.hip): the reads every other pass drops because their first bases are no
+# barcode + cut site entry, brought back when they lie one or two substitutions from the entries of exactly one barcode.
+BCRESCUE_CLASSES = ("reads", "exact", "rescued1", "rescued2", "ambiguous", "none")
+BCRESCUE_STAT_NAMES = BCRESCUE_CLASSES + ("tagged", "min_entry_distance")
+BCRESCUE_POSITIONS = 32
+BCRESCUE_NO_PAIR = 64          # min_entry_distance of an index whose entries all belong to one row
+
+
+def _bcrescue_entries(barcut, barnum):
+    """The entries the index build leaves, in list order, as (sequence, row) -- of duplicates the first, an entry that
+    extends an earlier one shadowed -- with the build's failures (what td_set_index reports)."""
+    if not barcut:
+        raise IndexError("list index out of range")
+    if barnum == 1 and barcut == [""]:                 # (a lone empty sequence matches every base)
+        return [(b, 0) for b in "ACGT"]
+    if barcut[0] == "":
+        raise IndexError("string index out of range")
+    try:
+        kept = _trie_survivors(barcut)
+    except AssertionError as exc:
+        pos = int(str(exc).split(":")[1].split(".")[0])
+        raise AssertionError("Problematic sequence: {}.  Likely due to overlapping tags.".format(pos % barnum)) from None
+    return [(seq, pos % barnum) for seq, pos in sorted(kept, key=lambda sp: sp[1])]
+
+
+def _bcrescue_min_distance(entries):
+    """The smallest Hamming distance between two entries of different rows, over the shorter one's length."""
+    import numpy as np
+    n = len(entries)
+    width = max(len(s) for s, _ in entries)
+    bases = np.zeros((n, width), dtype=np.uint8)
+    for k, (s, _) in enumerate(entries):
+        bases[k, :len(s)] = np.frombuffer(s.encode("ascii"), dtype=np.uint8)
+    lens = np.array([len(s) for s, _ in entries])
+    rows = np.array([r for _, r in entries])
+    col = np.arange(width)
+    best = BCRESCUE_NO_PAIR
+    for i in range(n - 1):
+        other = rows[i + 1:] != rows[i]
+        if not other.any():
+            continue
+        shorter = np.minimum(lens[i], lens[i + 1:])
+        d = ((bases[i + 1:] != bases[i]) & (col[None, :] < shorter[:, None])).sum(axis=1)
+        best = min(best, int(d[other].min()))
+    return best
+
+
+def _bcrescue_host(fqfile, barcodes, tags, cutsite, maxreads, K):
+    """The barcode-rescue rule read by read -> (matrix as lists, statistics).  The entries of one length are held
+    against the read's first bases in one numpy comparison; a head seen before is answered from a dict."""
+    from .engine import rescue_index
+    barcut, barnum, tagoff, stored = rescue_index(barcodes, tags, cutsite)
+    return _bcrescue_host_lists(fqfile, barcut, barnum, tagoff, stored, maxreads, K)
+
+
+def _bcrescue_host_lists(fqfile, barcut, barnum, tagoff, stored, maxreads, K):
+    """_bcrescue_host from the lists td_bcrescue_begin takes."""
+    import numpy as np
+    from ._binding import NonAsciiSequence
+    entries = _bcrescue_entries(barcut, barnum)
+    _rescue_check_tags(stored)
+    for seq, row in entries:
+        if len(seq) <= 2 * K:
+            raise ValueError("barcode rescue: entry of {} bases leaves no room for {} mismatches (every entry must be longer than {})".format(
+                len(seq), K, 2 * K))
+    exact_index = {seq: row for seq, row in entries}
+    lengths = sorted({len(s) for s in exact_index})
+    by_len = {}
+    for k, (seq, _) in enumerate(entries):
+        by_len.setdefault(len(seq), []).append(k)
+    groups = [(n, np.array(ids), np.frombuffer("".join(entries[k][0] for k in ids).encode("ascii"), dtype=np.uint8).reshape(len(ids), n))
+              for n, ids in sorted(by_len.items())]
+    entry_rows = np.array([r for _, r in entries])
+    widest = groups[-1][0]
+    tag_index = {t: k for k, t in enumerate(stored)}
+    tag_lengths = sorted({len(t) for t in stored})
+    bound = effective_maxreads(maxreads)
+    matrix = [[0] * len(stored) for _ in range(barnum)]
+    row_rescued = [[0, 0] for _ in range(barnum)]
+    positions = [0] * BCRESCUE_POSITIONS
+    st = dict.fromkeys(BCRESCUE_CLASSES + ("tagged",), 0)
+    memo = {}
+
+    def classify(head, length):
+        """(class, entry, mismatching positions) of a read without an exact entry: head = its first bases, length = len(read)"""
+        best, who = K + 1, []
+        for n, ids, mat in groups:
+            if n > length:
+                break
+            d = (mat != np.frombuffer(head[:n].encode("latin-1"), dtype=np.uint8)).sum(axis=1)
+            m = int(d.min())
+            if m <= K and m <= best:
+                hits = [int(k) for k in ids[np.flatnonzero(d == m)]]
+                who = hits if m < best else who + hits
+                best = m
+        if not who:
+            return "none", -1, ()
+        if len({int(entry_rows[k]) for k in who}) > 1:
+            return "ambiguous", -1, ()
+        k = min(who)                                    # of one row's variants that tie, the earliest in the list
+        seq = entries[k][0]
+        return "rescued{}".format(best), k, tuple(i for i in range(len(seq)) if head[i] != seq[i])
+
+    opener = _gzip.open if fqfile[-2:].lower() == 'gz' else open
+    with opener(fqfile, 'rt', encoding='latin-1') as fh:
+        for k, line in enumerate(fh):
+            if k % 4 != 1:
+                continue
+            st["reads"] += 1
+            if any(ch >= '\x80' for ch in line):
+                raise NonAsciiSequence("non-ASCII byte in a sequence line")
+            line1 = line.strip().upper()
+            if any(line1[:n] in exact_index and len(line1) >= n for n in lengths):
+                st["exact"] += 1
+            else:
+                key = (line1[:widest], min(len(line1), widest))
+                if key not in memo:
+                    memo[key] = classify(*key)
+                kind, e, where = memo[key]
+                st[kind] += 1
+                if e >= 0:
+                    b = entries[e][1]
+                    row_rescued[b][len(where) - 1] += 1
+                    for i in where:
+                        positions[i] += 1
+                    w = line1[tagoff[b]:]
+                    for n in tag_lengths:
+                        if n <= len(w) and w[:n] in tag_index:
+                            matrix[b][tag_index[w[:n]]] += 1
+                            st["tagged"] += 1
+                            break
+            if st["reads"] >= bound:
+                break
+    st["min_entry_distance"] = _bcrescue_min_distance(entries)
+    st["row_rescued"] = row_rescued
+    st["positions"] = positions
+    return matrix, st
+
+
+def rescue_barcodes_fastq(fqfile, barcodes, tags, cutsite="TGCAG", maxreads=5e9, max_mismatch=1, device=0, backend="gpu",
+                          as_array=False):
+    """Count the reads of one FASTQ file (plain or .gz by name) that find_tags_fastq drops because their first bases are
+    no barcode + cut site entry but lie 1 .. max_mismatch (1 or 2) substitutions from the entries of exactly one barcode
+    -> (matrix [len(barcodes)][len(tags)], statistics).
+
+    The set-up is find_tags_fastq's (asserts, every cut-site variant, the strip decision).  The entries are the barcode +
+    cut site strings the index build leaves; entry k belongs to barcode k % len(barcodes).  Per read (stripped,
+    upper-cased): an entry that is an exact prefix -> `exact`, the counter's read, nothing else.  Otherwise every entry
+    no longer than the read is a candidate at the number of its positions that differ from the read (a character outside
+    ACGT differs from every base; no indels, no qualities), and the smallest distance m decides: m > max_mismatch or no
+    candidate -> `none`; entries of several barcodes at m -> `ambiguous` (cut-site variants of one barcode that tie are no
+    tie: the earliest in the list counts); else the read is rescued into that barcode: `rescued<m>`, `row_rescued[b][m -
+    1]`, `positions[i]` for every mismatching i, and the counter's tag step from where the tags are compared: the stored
+    tag that begins the rest of the read gets the matrix cell and `tagged`.
+    reads == exact + rescued1 + rescued2 + ambiguous + none.
+
+    The statistics: those classes, `tagged`, `min_entry_distance` (the smallest distance between entries of two
+    barcodes over the shorter one's length, 64 with one barcode: at or below max_mismatch, exact reads of one sample lie
+    one error from rescue into another), `row_rescued` ([len(barcodes)][2]) and `positions` (32 ints).
+    The tags follow rescue_tags_fastq's conditions.  Every entry must be longer than 2 * max_mismatch bases (ValueError).
+    backend="gpu": csrc/bcrescue.hip; backend="host": the same rule in Python."""
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    K = int(max_mismatch)
+    if K not in (1, 2):
+        raise ValueError("max_mismatch must be 1 or 2")
+    if backend == "host":
+        matrix, stats = _bcrescue_host(fqfile, barcodes, tags, cutsite, maxreads, K)
+        if as_array:
+            import numpy as np
+            matrix = np.array(matrix, dtype=np.uint32).reshape(len(barcodes), len(tags))
+        return matrix, stats
+    from ._binding import TagdigError
+    eng = default_engine(device)
+    try:
+        eng.bcrescue_begin(barcodes, tags, cutsite, K)
+    except TagdigError as exc:
+        if exc.code == -7 and exc.detail.startswith("barcode rescue: entry"):
+            raise ValueError(exc.detail) from None
+        raise
+    try:
+        eng.bcrescue_file(fqfile, maxreads)
+        stats = eng.bcrescue_stats()
+        m, rows, pos = eng.bcrescue_fetch()
+    finally:
+        try:
+            eng.bcrescue_end()
+        except Exception:          # noqa: BLE001 -- the error that brought us here is the one to report
+            pass
+    stats["row_rescued"] = [[int(x) for x in r] for r in rows]
+    stats["positions"] = [int(x) for x in pos]
+    return (m if as_array else m.tolist()), stats
+
+
+def writeBarcodeRescueStats(filename, libraries, results):
+    """One row per library (results: the statistics dicts of rescue_barcodes_fastq): Library, the six classes, tagged,
+    min_entry_distance, and the rescued reads' share of the reads without an exact entry (six decimals; NA without
+    any).  CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Library"] + list(BCRESCUE_STAT_NAMES) + ["rescued_share"])
+        for lib, st in zip(libraries, results):
+            out.writerow([lib] + [st[k] for k in BCRESCUE_STAT_NAMES] + [_rate_text(st["rescued1"] + st["rescued2"], st["reads"] - st["exact"])])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Tag Manager (reference tagdigger_fun.py:1389-1905 and the prompts of :936-1028, :1182-1200).
 #
 # Every function keeps the reference's signature, return values, printed lines, files and exceptions.  Those with a
