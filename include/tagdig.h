@@ -752,6 +752,67 @@ int td_geno_call(td_handle *h, const void *d_counts, uint32_t S, uint32_t T, uin
                  const uint32_t *i1, const uint16_t *het_min, const td_geno_params *p, uint8_t *calls_out,
                  void **d_calls_out, uint64_t *stats_out, uint8_t *pass_out, uint64_t *passed_out, double *ms);
 
+/* ---- polyploid allele dosage calls (csrc/dosage.hip; tagdigger_amd/tagdigger_fun.py call_dosage drives it) -----------
+ *
+ * From the samples x tags count matrix to the allele dosage 0 .. P of every cell, for one ploidy P of all samples
+ * (DESIGN.md 4.23).  d_counts, S, T, M, i0, i1 as for td_geno_call: the matrix in DEVICE memory, the markers as pairs of
+ * columns in HOST arrays, both < T and different.  The rule, in integers only.  The caller hands in three tables of
+ * costs as DATA, cost(x) = round_half_even(-65536 log2 x) for a probability x (tagdigger_fun.dosage_tables builds them;
+ * the library evaluates no logarithm and checks only that no entry exceeds TD_DOSE_COST_MAX):
+ *   ca[0 .. P]      cost of a read of allele 1 from a cell of dosage d: p_d = (d (1 - e) + (P - d) e) / P
+ *   cb[0 .. P]      cost of a read of allele 0: 1 - p_d
+ *   cp[TD_DOSE_BINS][P + 1]   cost of dosage d under the prior C(P, d) q^d (1 - q)^(P - d), q = (2 k + 1) / (2 TD_DOSE_BINS)
+ *                   the centre of bin k; read with TD_DOSE_HWE only (TD_DOSE_FLAT: may be NULL, every prior cost is 0)
+ * Per marker: depth0 / depth1 = the uint64 sums of a and b over EVERY sample, tot = depth0 + depth1,
+ *   bin = 0 when tot == 0, else min(TD_DOSE_BINS - 1, floor(TD_DOSE_BINS depth1 / tot))      (reported under both priors)
+ * Per cell, a = counts[s][i0[m]], b = counts[s][i1[m]], n = a + b (64-bit):
+ *   TD_DOSE_MISSING (255)   n < min_depth
+ *   c[d] = b ca[d] + a cb[d] + cp[bin][d]  (uint64; below 2^57), d = 0 .. P      (b counts the reads of allele 1)
+ *   best = the smallest d with minimal c[d]; second = the minimal c[d] over d != best
+ *   the call is best when second - c[best] >= min_margin, else TD_DOSE_MISSING
+ * so a tie gives the lower dosage at min_margin 0 and is missing at any min_margin >= 1.  The code is the number of
+ * allele-1 copies.  The diploidised code of a cell is 0 for dosage 0, 2 for dosage P, 1 for everything between and
+ * TD_GENO_MISSING (3) for a missing cell: what td_relate_joint, td_ld_pairs, td_impute_knn and td_parent_trios read.
+ * stats_out[TD_DOSE_NSTATS m + TD_DOSE_*]: exact integers; the classes above P are 0.  Marker m passes when
+ *   called * 10^6 >= min_call_ppm * S,  min(alt, P called - alt) * 10^6 >= min_maf_ppm * P * called
+ * Outputs as for td_geno_call, each optional except passed_out, and stats_out / pass_out when M > 0: calls_out and
+ * diploid_out (HOST, S * M bytes), d_calls_out and d_diploid_out (the DEVICE buffers, the caller's to td_dev_free; NULL
+ * is stored when nothing was launched), ms (HIP events around the kernels).  The diploidised matrix is written only when
+ * diploid_out or d_diploid_out asks for it.  The call waits for the handle's own streams first.  M = 0, T = 0 and S = 0
+ * are answered as td_geno_call answers them, without a launch.  TD_E_ARG: ploidy outside 2 .. TD_DOSE_MAX_PLOIDY, prior
+ * not 0 | 1, err_ppm outside 1 .. 499 999, min_depth 0, min_call_ppm above 10^6, min_maf_ppm above 500 000, S above 2^24
+ * (64 depth1 must fit 64 bits), a table entry above TD_DOSE_COST_MAX, cp NULL with TD_DOSE_HWE, or a marker whose columns
+ * are not both below T or are equal: td_last_bad_index gives the marker.  TD_E_LIMIT: more than 65 535 sample chunks. */
+typedef struct td_dose_params {
+    uint32_t ploidy;          /* P: allele copies of every sample, 2 .. TD_DOSE_MAX_PLOIDY                */
+    uint32_t prior;           /* TD_DOSE_FLAT | TD_DOSE_HWE                                               */
+    uint32_t err_ppm;         /* the error rate ca / cb were built for                                    */
+    uint32_t min_margin;      /* second - best below this: missing; units of 2^-16 bit                    */
+    uint64_t min_depth;       /* a + b below this: missing                                                */
+    uint32_t min_call_ppm;    /* marker filter: called / S                                                */
+    uint32_t min_maf_ppm;     /* marker filter: minor allele frequency among the called                   */
+} td_dose_params;
+enum {
+    TD_DOSE_FLAT = 0,
+    TD_DOSE_HWE = 1,
+    TD_DOSE_MAX_PLOIDY = 8,
+    TD_DOSE_BINS = 64,        /* rows of cp: bins of the marker's allele-1 read share                     */
+    TD_DOSE_COST_MAX = 1 << 23,
+    TD_DOSE_MISSING = 255,
+    TD_DOSE_CALLED = 0,       /* stats: n0 + ... + n8                                                     */
+    TD_DOSE_N0 = 1,           /* calls by dosage: TD_DOSE_N0 + d, d = 0 .. 8                              */
+    TD_DOSE_ALT = 10,         /* sum of d n[d]: copies of allele 1                                        */
+    TD_DOSE_DEPTH0 = 11,      /* sum of a                                                                 */
+    TD_DOSE_DEPTH1 = 12,      /* sum of b                                                                 */
+    TD_DOSE_BIN = 13,
+    TD_DOSE_NSTATS = 14,
+    TD_DOSE_CHUNK = 64        /* sample rows per workgroup of the call kernel (td_geno_call's choice)     */
+};
+int td_dose_call(td_handle *h, const void *d_counts, uint32_t S, uint32_t T, uint32_t M, const uint32_t *i0,
+                 const uint32_t *i1, const uint32_t *ca, const uint32_t *cb, const uint32_t *cp, const td_dose_params *p,
+                 uint8_t *calls_out, void **d_calls_out, uint8_t *diploid_out, void **d_diploid_out, uint64_t *stats_out,
+                 uint8_t *pass_out, uint64_t *passed_out, double *ms);
+
 /* ---- pairwise sample relations (csrc/relate.hip; tagdigger_amd/tagdigger_fun.py sample_relations drives it) -----------
  *
  * From the calls to the check of the samples themselves, without bringing the calls to the host.

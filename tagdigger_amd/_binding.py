@@ -53,6 +53,12 @@ class GenoParams(C.Structure):
                 ("min_maf_ppm", C.c_uint32), ("max_het_ppm", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DoseParams(C.Structure):
+    """td_dose_params of include/tagdig.h"""
+    _fields_ = [("ploidy", C.c_uint32), ("prior", C.c_uint32), ("err_ppm", C.c_uint32), ("min_margin", C.c_uint32),
+                ("min_depth", C.c_uint64), ("min_call_ppm", C.c_uint32), ("min_maf_ppm", C.c_uint32)]
+
+
 class ImputeParams(C.Structure):
     """td_impute_params of include/tagdig.h"""
     _fields_ = [("L", C.c_uint32), ("k", C.c_uint32), ("min_overlap", C.c_uint32), ("min_conf_ppm", C.c_uint32)]
@@ -201,6 +207,8 @@ def load():
     sig("td_place_free", i32, vp, vp)
     sig("td_geno_call", i32, vp, vp, u32, u32, u32, vp, vp, vp, C.POINTER(GenoParams), vp, C.POINTER(vp), vp, vp,
         C.POINTER(u64), dp)
+    sig("td_dose_call", i32, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(DoseParams), vp, C.POINTER(vp), vp,
+        C.POINTER(vp), vp, vp, C.POINTER(u64), dp)
     sig("td_relate_joint", i32, vp, vp, u32, u32, vp, vp, C.POINTER(vp), dp)
     sig("td_ld_pairs", i32, vp, vp, u32, u32, vp, u32, u32, vp, u64, C.POINTER(u64), vp, vp, dp)
     sig("td_ld_last_times", i32, vp, dp)
@@ -235,6 +243,7 @@ EXPORTS = [
     "td_geno_call", "td_relate_joint", "td_ld_pairs", "td_ld_last_times",
     "td_impute_knn", "td_impute_last_times",
     "td_parent_trios", "td_parent_last_times",
+    "td_dose_call",
 ]
 
 

@@ -188,6 +188,23 @@ class GenoCalls(collections.namedtuple("GenoCalls", "calls stats mask ms passed 
     __slots__ = ()
 
 
+DOSE_STATS = ("called",) + tuple("n%d" % d for d in range(9)) + ("alt", "depth0", "depth1", "bin")     # TD_DOSE_* slots
+DOSE_PRIORS = {"flat": 0, "hwe": 1}
+DOSE_MAX_PLOIDY = 8         # TD_DOSE_MAX_PLOIDY
+DOSE_BINS = 64              # TD_DOSE_BINS: rows of the prior table
+DOSE_COST_MAX = 1 << 23     # TD_DOSE_COST_MAX: the largest table entry the library takes
+DOSE_MISSING = 255          # TD_DOSE_MISSING
+DOSE_CHUNK = 64             # TD_DOSE_CHUNK: sample rows per workgroup of csrc/dosage.hip's kernels
+
+
+class DoseCalls(collections.namedtuple("DoseCalls", "calls diploid stats mask ms passed d_calls d_diploid")):
+    """What Engine.dose_call returns: calls (uint8 [S, M], dosage 0 .. P or 255; None when not fetched), diploid (the
+    diploidised matrix, 0 / 1 / 2 / 3; None when not asked for or not fetched), stats (dict of uint64 [M] arrays by
+    DOSE_STATS), mask (bool [M]), ms (device time), passed, d_calls and d_diploid (the device buffers when they were asked
+    for -- the caller's, to be freed with dev_free -- else None)."""
+    __slots__ = ()
+
+
 RELATE_MAX_SAMPLES = 16384  # TD_RELATE_MAX_SAMPLES: the joint table is 9 S^2 uint32
 RELATE_TILE = 64            # TD_RELATE_TILE: samples along a workgroup's tile edge of csrc/relate.hip
 RELATE_KCHUNK = 32768       # TD_RELATE_KCHUNK: markers per workgroup of csrc/relate.hip
@@ -896,6 +913,57 @@ class Engine:
             raise err
         return GenoCalls(calls, {k: stats[:M, j].copy() for j, k in enumerate(GENO_STATS)}, mask[:M].astype(bool),
                          ms.value, passed.value, d_calls.value if keep_device else None)
+
+    # ------------------------------------------------------------------ dosage calls (td_dose_call; csrc/dosage.hip)
+    def dose_call(self, counts, i0, i1, ca, cb, cp=None, shape=None, ploidy=4, prior=1, err_ppm=10000, min_depth=1,
+                  min_margin=0, min_call_ppm=0, min_maf_ppm=0, fetch_calls=True, diploid=False, keep_device=False,
+                  keep_diploid=False):
+        """td_dose_call: allele dosage calls 0 .. ploidy (255 missing), per-marker statistics and the filter mask of the
+        markers (i0[m], i1[m]) of a samples x tags count matrix; counts and shape as for geno_call.  ca, cb: ploidy + 1
+        costs each; cp: DOSE_BINS x (ploidy + 1) costs, None with prior 0 (flat) -- tagdigger_fun.dosage_tables builds
+        all three.  diploid=True computes the diploidised matrix (0, 1, 2, 3 missing) as well.  fetch_calls=False
+        leaves both matrices on the device; keep_device=True hands the device buffer of the dosages out as `.d_calls`,
+        keep_diploid=True that of the diploidised matrix as `.d_diploid` (computed for it if need be): the caller's to
+        dev_free.  Returns a DoseCalls.  A failure raises TagdigError;
+        `.bad_index` holds the marker for a bad pair of columns."""
+        import numpy as np
+        i0 = np.ascontiguousarray(i0, dtype=np.uint32)
+        i1 = np.ascontiguousarray(i1, dtype=np.uint32)
+        if i0.ndim != 1 or i0.shape != i1.shape:
+            raise ValueError("i0 and i1 must be two index lists of one length")
+        P = int(ploidy)
+        ca = np.ascontiguousarray(ca, dtype=np.uint32)
+        cb = np.ascontiguousarray(cb, dtype=np.uint32)
+        if 2 <= P <= DOSE_MAX_PLOIDY and (ca.shape != (P + 1,) or cb.shape != (P + 1,)):      # (the library refuses another ploidy)
+            raise ValueError("ca and cb must have ploidy + 1 entries")
+        if cp is not None:
+            cp = np.ascontiguousarray(cp, dtype=np.uint32)
+            if 2 <= P <= DOSE_MAX_PLOIDY and cp.shape != (DOSE_BINS, P + 1):
+                raise ValueError("cp must have {} rows of ploidy + 1 entries".format(DOSE_BINS))
+        M = len(i0)
+        with self._device_matrix(counts, shape, np.uint32, "tags", none_ok=False) as (d_counts, S, T):
+            par = B.DoseParams(P, int(prior), int(err_ppm), int(min_margin), int(min_depth), int(min_call_ppm), int(min_maf_ppm))
+            calls = np.zeros((S, M), dtype=np.uint8) if fetch_calls else None
+            dip = np.zeros((S, M), dtype=np.uint8) if fetch_calls and diploid else None
+            stats = np.zeros((max(1, M), len(DOSE_STATS)), dtype=np.uint64)
+            mask = np.zeros(max(1, M), dtype=np.uint8)
+            passed, ms, d_calls, d_dip = C.c_uint64(0), C.c_double(0), C.c_void_p(), C.c_void_p()
+            idx0, idx1 = (a if M else np.zeros(1, dtype=np.uint32) for a in (i0, i1))
+            rc = self._L.td_dose_call(self._h, C.c_void_p(d_counts) if d_counts else None, S, T, M,
+                                      idx0.ctypes.data_as(C.c_void_p), idx1.ctypes.data_as(C.c_void_p),
+                                      ca.ctypes.data_as(C.c_void_p), cb.ctypes.data_as(C.c_void_p),
+                                      cp.ctypes.data_as(C.c_void_p) if cp is not None else None, C.byref(par),
+                                      calls.ctypes.data_as(C.c_void_p) if calls is not None and calls.size else None,
+                                      C.byref(d_calls) if keep_device else None,
+                                      dip.ctypes.data_as(C.c_void_p) if dip is not None and dip.size else None,
+                                      C.byref(d_dip) if keep_diploid else None, stats.ctypes.data_as(C.c_void_p),
+                                      mask.ctypes.data_as(C.c_void_p), C.byref(passed), C.byref(ms))
+        if rc:
+            err = self._error(rc)
+            err.bad_index = self._L.td_last_bad_index() if rc == -2 and err.detail.startswith("marker ") else None
+            raise err
+        return DoseCalls(calls, dip, {k: stats[:M, j].copy() for j, k in enumerate(DOSE_STATS)}, mask[:M].astype(bool), ms.value,
+                         passed.value, d_calls.value if keep_device else None, d_dip.value if keep_diploid else None)
 
     # ------------------------------------------------------------------ sample relations (td_relate_joint; csrc/relate.hip)
     def relate_joint(self, calls, shape=None, use=None, fetch=True, keep_device=False):

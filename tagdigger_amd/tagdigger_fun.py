@@ -1698,6 +1698,213 @@ def writeHapMap(filename, result, tagseqs, passing_only=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Polyploid allele dosage calls from the count matrix: call_genotypes' sibling for one ploidy P = 2 .. 8.
+# Every probability of the model becomes an integer cost, round(-65536 log2 x), in tables that only this module builds
+# (fractions for the probabilities, decimal for the logarithm); the rule then adds and compares 64-bit integers.
+# call_dosage(backend="host") restates it in numpy, csrc/dosage.hip runs it where the matrix lies.
+DOSE_STATS = ("called",) + tuple("n%d" % d for d in range(9)) + ("alt", "depth0", "depth1", "bin")
+DOSE_PRIORS = ("flat", "hwe")
+DOSE_MAX_PLOIDY = 8
+DOSE_BINS = 64
+DOSE_COST_MAX = 1 << 23
+DOSE_MISSING = 255
+_DOSE_TABLES = {}
+
+
+def _dose_cost(x, digits=60):
+    """round_half_even(-65536 log2 x) of a fractions.Fraction 0 < x <= 1, with decimal at `digits` digits."""
+    import decimal
+    with decimal.localcontext() as ctx:
+        ctx.prec = max(50, int(digits))
+        bits = -(decimal.Decimal(x.numerator) / decimal.Decimal(x.denominator)).ln() / decimal.Decimal(2).ln()
+        return int((bits * 65536).quantize(decimal.Decimal(1), rounding=decimal.ROUND_HALF_EVEN))
+
+
+def dosage_tables(ploidy, err, nbins=DOSE_BINS):
+    """(CA, CB, CP) for ploidy P and the sequencing error rate e = round(err * 10^6) / 10^6 as an exact rational, all as
+    lists of ints, cost(x) = round_half_even(-65536 log2 x):
+      CA[d] = cost(p_d), CB[d] = cost(1 - p_d)   p_d = (d (1 - e) + (P - d) e) / P: a read of a cell with d copies of
+                                                 allele 1 shows allele 1 (CA) or allele 0 (CB); CA[d] == CB[P - d]
+      CP[k][d] = cost(C(P, d) q^d (1 - q)^(P - d))   q = (2 k + 1) / (2 nbins), the centre of bin k of the marker's
+                                                 allele-1 read share: Hardy-Weinberg proportions at that frequency
+    Pure Python (fractions, decimal at 60 digits): the same on every machine."""
+    from fractions import Fraction
+    from math import comb
+    P = int(ploidy)
+    if P != ploidy or not 2 <= P <= DOSE_MAX_PLOIDY:
+        raise ValueError("ploidy must be an integer in 2 .. {}".format(DOSE_MAX_PLOIDY))
+    if int(nbins) != nbins or nbins < 1:
+        raise ValueError("nbins must be a positive integer")
+    key = (P, _ppm(err, 1, 499999, "err"), int(nbins))
+    if key not in _DOSE_TABLES:
+        e = Fraction(key[1], 1000000)
+        p = [(d * (1 - e) + (P - d) * e) / P for d in range(P + 1)]
+        CA = tuple(_dose_cost(x) for x in p)
+        CB = tuple(_dose_cost(1 - x) for x in p)
+        assert all(CA[d] == CB[P - d] for d in range(P + 1))
+        CP = []
+        for k in range(key[2]):
+            q = Fraction(2 * k + 1, 2 * key[2])
+            CP.append(tuple(_dose_cost(comb(P, d) * q ** d * (1 - q) ** (P - d)) for d in range(P + 1)))
+        _DOSE_TABLES[key] = (CA, CB, tuple(CP))
+    CA, CB, CP = _DOSE_TABLES[key]
+    return list(CA), list(CB), [list(row) for row in CP]
+
+
+def dosage_margin(min_odds):
+    """round(65536 log2 min_odds): the least cost margin (units of 2^-16 bit) between the best and the second-best
+    dosage at which the best is min_odds times as probable.  min_odds >= 1."""
+    from fractions import Fraction
+    odds = Fraction(min_odds)
+    if odds < 1:
+        raise ValueError("min_odds must be at least 1")
+    margin = _dose_cost(1 / odds)
+    if margin > 0xffffffff:
+        raise ValueError("min_odds is too large: the margin must fit 32 bits")
+    return margin
+
+
+class DosageResult:
+    """What call_dosage returns: `.markers`, `.samples`, `.ploidy`, `.calls` (uint8 [samples, markers]: copies of allele
+    1, 0 .. ploidy, 255 = missing), `.diploid` (uint8: 0 for dosage 0, 2 for dosage ploidy, 1 between, 3 = missing -- what
+    sample_relations, marker_ld, impute_calls and parentage read), `.stats` (called, n0 .. n8, alt, depth0, depth1, bin as
+    arrays over the markers; passed, backend, ms and the parameters), `.mask` (bool per marker: it passes the filters),
+    `.columns`, `.backend`, `.d_diploid` (call_dosage(keep_device=True) on the gpu backend: a DeviceCalls of the
+    diploidised matrix where the kernel wrote it, which the caller frees; else None)."""
+
+    def __init__(self, markers, samples, ploidy, calls, diploid, stats, mask, columns, backend, d_diploid=None):
+        self.markers, self.samples, self.ploidy, self.calls, self.diploid = markers, samples, ploidy, calls, diploid
+        self.stats, self.mask, self.columns, self.backend, self.d_diploid = stats, mask, columns, backend, d_diploid
+
+
+def _dosage_host(counts, i0, i1, ploidy, CA, CB, CP, min_depth, min_margin, min_call_ppm, min_maf_ppm):
+    """The rule of DESIGN 4.23 in numpy's uint64, which holds every intermediate exactly: a cost stays below 2^57,
+    64 depth1 below 2^63 for at most 2^24 samples.  CP None: the flat prior.  Returns (calls, diploid, stats, mask)."""
+    import numpy as np
+    S, M, P = counts.shape[0], len(i0), int(ploidy)
+    if S > 1 << 24:
+        raise ValueError("more than 2^24 samples")
+    a = counts[:, i0].astype(np.uint64)
+    b = counts[:, i1].astype(np.uint64)
+    depth0, depth1 = a.sum(axis=0, dtype=np.uint64), b.sum(axis=0, dtype=np.uint64)
+    tot = depth0 + depth1
+    bins = np.where(tot == 0, 0, np.minimum(np.uint64(DOSE_BINS - 1), np.uint64(DOSE_BINS) * depth1 // np.where(tot == 0, 1, tot))).astype(np.int64)
+    prior = np.zeros((P + 1, M), dtype=np.uint64) if CP is None else np.asarray(CP, dtype=np.uint64)[bins].T.copy()
+
+    def cost(d):
+        return b * np.uint64(CA[d]) + a * np.uint64(CB[d]) + prior[d][None, :]
+    best, second = cost(0), np.full((S, M), ~np.uint64(0), dtype=np.uint64)
+    code = np.zeros((S, M), dtype=np.uint8)
+    for d in range(1, P + 1):
+        c = cost(d)
+        lead = c < best                               # strict: among equal costs the smallest d stays best
+        second = np.minimum(second, np.where(lead, best, c))
+        best = np.where(lead, c, best)
+        code[lead] = d
+    missing = (a + b < np.uint64(min_depth)) | (second - best < np.uint64(min_margin))
+    calls = np.where(missing, DOSE_MISSING, code).astype(np.uint8)
+    diploid = np.where(missing, GENO_MISSING, np.where(code == 0, 0, np.where(code == P, 2, 1))).astype(np.uint8)
+    n = [(calls == d).sum(axis=0, dtype=np.uint64) for d in range(9)]
+    called = sum(n[1:], n[0])
+    alt = sum((np.uint64(d) * n[d] for d in range(1, 9)), np.zeros(M, dtype=np.uint64))
+    million = np.uint64(1000000)
+    mask = ((called * million >= np.uint64(min_call_ppm * S)) &
+            (np.minimum(alt, np.uint64(P) * called - alt) * million >= np.uint64(min_maf_ppm * P) * called))
+    if S == 0:
+        mask[:] = False                               # no sample: no marker passes on no evidence
+    stats = dict(zip(DOSE_STATS, [called] + n + [alt, depth0, depth1, bins.astype(np.uint64)]))
+    return calls, diploid, stats, mask
+
+
+def call_dosage(counts, samnames, tagnames, ploidy=4, prior="hwe", err=0.01, min_depth=1, min_odds=10, min_call_rate=0.0,
+                min_maf=0.0, device=0, backend="gpu", keep_device=False, min_margin=None):
+    """Allele dosage calls of polyploid samples from a samples x tags count matrix, and which markers pass the filters
+    (DESIGN 4.23).  Every sample carries `ploidy` copies (2 .. 8) of each marker; a call is the number of copies of
+    allele 1, 0 .. ploidy.
+
+    Markers and alleles come from the tag names as call_genotypes reads them.  For a sample's counts a and b of the two
+    alleles the cost of dosage d is b CA[d] + a CB[d] + CP[bin][d] in the integer tables of dosage_tables(ploidy, err):
+    minus log2 of the binomial likelihood of the reads with error rate err, and of the prior.  prior="hwe": Hardy-Weinberg
+    proportions at the marker's allele-1 read share over all samples, in 64 bins; prior="flat": none.  The call is the
+    cheapest dosage (the lower one of equals) when the second cheapest costs at least dosage_margin(min_odds) more -- it is
+    min_odds times as probable --, else missing (255); a cell with a + b < min_depth is missing too.  min_margin, when
+    given, replaces dosage_margin(min_odds).  A marker passes when called / samples >= min_call_rate and its minor allele
+    frequency among the called copies >= min_maf, compared as integers in parts per million.
+    counts: a numpy matrix or lists (uint32 values), or a DeviceCounts (backend="gpu" only).  backend="gpu" runs
+    csrc/dosage.hip on the matrix where it lies; backend="host" is the numpy restatement.  keep_device=True with the gpu
+    backend leaves the diploidised calls on the device as well: `.d_diploid` is a DeviceCalls for sample_relations,
+    marker_ld, impute_calls and parentage, and the caller's to free.  Returns a DosageResult."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    if prior not in DOSE_PRIORS:
+        raise ValueError("prior must be 'flat' or 'hwe'")
+    err_ppm = _ppm(err, 1, 499999, "err")
+    CA, CB, CP = dosage_tables(ploidy, err_ppm / 1e6)
+    ploidy = int(ploidy)
+    if int(min_depth) != min_depth or min_depth < 1:
+        raise ValueError("min_depth must be an integer of at least 1")
+    min_depth = int(min_depth)
+    if min_margin is None:
+        min_margin = dosage_margin(min_odds)
+    if int(min_margin) != min_margin or not 0 <= min_margin <= 0xffffffff:
+        raise ValueError("min_margin must be an integer in 0 .. 2^32 - 1")
+    min_margin = int(min_margin)
+    min_call_ppm = _ppm(min_call_rate, 0, 1000000, "min_call_rate")
+    min_maf_ppm = _ppm(min_maf, 0, 500000, "min_maf")
+    on_device = isinstance(counts, DeviceCounts)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCounts matrix needs backend='gpu'")
+    if not on_device:
+        from .engine import counts_as_uint32
+        counts = counts_as_uint32(counts if len(counts) else np.zeros((0, len(tagnames)), dtype=np.uint32))
+    assert len(samnames) == counts.shape[0], "Length of samnames should be the same as length of counts."
+    assert len(tagnames) == counts.shape[1], "Length of tagnames should be length of second dimension of counts."
+    markers, i0, i1 = _geno_markers(tagnames)
+    d_diploid = None
+    if backend == "host":
+        calls, diploid, stats, mask = _dosage_host(counts, i0, i1, ploidy, CA, CB, CP if prior == "hwe" else None, min_depth,
+                                                   min_margin, min_call_ppm, min_maf_ppm)
+        ms = 0.0
+    else:
+        res = default_engine(device).dose_call(counts.ptr if on_device else counts, i0, i1, CA, CB, CP if prior == "hwe" else None,
+                                               shape=counts.shape if on_device else None, ploidy=ploidy,
+                                               prior=DOSE_PRIORS.index(prior), err_ppm=err_ppm, min_depth=min_depth,
+                                               min_margin=min_margin, min_call_ppm=min_call_ppm, min_maf_ppm=min_maf_ppm,
+                                               diploid=True, keep_diploid=bool(keep_device))
+        calls, diploid, stats, mask, ms = res.calls, res.diploid, res.stats, res.mask, res.ms
+        if keep_device:
+            d_diploid = DeviceCalls(res.d_diploid or 0, calls.shape)
+    stats = dict(stats, passed=int(mask.sum()), backend=backend, ms=ms, ploidy=ploidy, prior=prior, err_ppm=err_ppm,
+                 min_depth=min_depth, min_margin=min_margin, min_call_ppm=min_call_ppm, min_maf_ppm=min_maf_ppm)
+    return DosageResult(markers, list(samnames), ploidy, calls, diploid, stats, mask, (i0, i1), backend, d_diploid)
+
+
+def writeDosage(filename, result, passing_only=True):
+    """The dosages in writeGenoCalls' layout (samples in rows, markers in columns, csv.writer's CRLF rows): 0 .. ploidy,
+    blank for missing.  passing_only: the markers that pass the filters; False: all of them."""
+    import numpy as np
+    keep = _geno_selected(result, passing_only)
+    text = np.array([str(d) for d in range(DOSE_MISSING)] + [''])
+    rows = text[result.calls[:, keep]].tolist()
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow([""] + [result.markers[m] for m in keep])
+        for name, calls in zip(result.samples, rows):
+            out.writerow([name] + calls)
+
+
+def writeDosageStats(filename, result):
+    """One row per marker: name, called, n0 .. n<ploidy>, alt, depth0, depth1, bin, pass (1 / 0); CSV with a header row."""
+    cols = [k for k in DOSE_STATS if not (k[0] == "n" and int(k[1:]) > result.ploidy)]
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(["Marker name"] + cols + ["pass"])
+        for m, name in enumerate(result.markers):
+            out.writerow([name] + [int(result.stats[k][m]) for k in cols] + [1 if result.mask[m] else 0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Pairwise sample relations from the calls (DESIGN 4.15): the step behind the calls.  Everything is a function of one
 # table, joint[i][j][a][b] = the participating markers at which sample i is called a and sample j is called b; it is
 # exact in integers.  csrc/relate.hip computes it on the matrix cores from the calls where they lie, _relations_host
