@@ -884,6 +884,63 @@ int td_ld_pairs(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const
                 uint32_t *called_out /* HOST, M, or NULL */, double *ms);
 int td_ld_last_times(td_handle *h, double *out3 /* transpose ms, pair kernel ms, sort ms of this thread's last td_ld_pairs */);
 
+/* ---- linkage of the markers of a cross (csrc/link.hip; tagdigger_amd/tagdigger_fun.py linkage_map drives it) -------------
+ *
+ * From the calls of a mapping population to its linkage map: which markers are linked, in which phase, at
+ * which recombination fraction.  d_calls and the codes are those of the sections above: S x M uint8, row-major, in DEVICE
+ * memory, rows exactly M bytes apart, 0 / 1 / 2, ANY byte above 2 missing.  Only the OFFSPRING rows enter a count: rows
+ * (HOST, R row indices below S, none twice, in any order) names them; rows == NULL takes all rows and needs R == S.
+ *
+ * td_link_counts: counts_out[m] = (c0, c1, c2, cmiss) of marker m over the offspring rows (HOST, M x 4 uint32; the four sum
+ * to R).  ms (optional): device time of the kernel.  R = 0 or M = 0 gives zeros (or nothing) without a launch.
+ *
+ * td_link_pairs: cls (HOST, M bytes) gives every marker its two classes A and B: 0 = (A 0, B 1), 1 = (A 2, B 1),
+ * 2 = (A 0, B 2), 255 = the marker takes no part.  A cell's value x is +1 for A, -1 for B and 0 for anything else (the third
+ * genotype, missing).  The rule, in integers only.  For two participating markers i < j (original numbering) over the
+ * offspring rows:
+ *   N = sum x_i^2 x_j^2 (informative at both), D = sum x_i x_j (concordant minus discordant, signed; same parity as N)
+ *   rec = (N - |D|) / 2, phase = 0 (coupling) if D >= 0 else 1 (repulsion)
+ *   lod16 = 65536 N + lodtab[rec] + lodtab[N - rec] - lodtab[N]      (int64)
+ * where lodtab (HOST, R + 1 int64) is the caller's table, lodtab[k] = round(65536 k log2 k) for the LOD in units of
+ * log10(2) / 65536 (tagdigger_fun.linkage_tables); the library only looks it up.  The pair is an EDGE iff
+ * N >= min_shared, rec 10^6 <= max_rf_ppm N and lod16 >= min_lod16.  D and N are Gram products over the offspring of the
+ * planes X (signed) and X & 1 and run on the matrix cores in int8 with int32 accumulators: exact.
+ *
+ * *n_out is always the number of edges.  edges_out == NULL counts only.  With a buffer of `capacity` records and
+ * n <= capacity the edges are returned ascending by (i, j): the same bytes on every run.  With n > capacity the call
+ * returns TD_E_LIMIT; *n_out, degree_out and informative_out are complete all the same and no record past the capacity has
+ * been written anywhere.  degree_out[m] (optional, HOST, M): the edges m takes part in; informative_out[m] (optional, HOST,
+ * M): the offspring with x != 0 at m; both 0 for a marker that takes no part.  ms (optional): device time of the two
+ * kernels; td_link_last_times gives the counts kernel of the CALLING THREAD's last td_link_counts and the gather, pair
+ * kernel (device ms) and sort (host ms) of its last td_link_pairs apart.  No byte beyond calls[S M - 1], rows[R - 1],
+ * cls[M - 1] or lodtab[R] is read.
+ * Both are synchronous and wait for the work enqueued through this handle first.  Checked before anything is allocated or
+ * launched, TD_E_ARG each: a NULL handle, R <= TD_LINK_MAX_SAMPLES, M < 2^31, rows == NULL with R != S, a row index >= S
+ * (td_last_bad_index gives its place in rows), a row listed twice, a NULL counts_out with M > 0 (td_link_counts);
+ * max_rf_ppm > 500000, a NULL lodtab, a NULL cls with M > 0, a cls byte outside {0, 1, 2, 255} (td_last_bad_index gives the
+ * marker) (td_link_pairs); then more than TD_LINK_MAX_MARKERS participating markers is TD_E_LIMIT; last a NULL matrix with
+ * R M > 0 (TD_E_ARG).  After that R = 0 or no participating marker gives no edges without a launch; one participating
+ * marker has its informative offspring counted and no pair. */
+typedef struct td_link_edge {
+    uint32_t i, j;            /* the markers, i < j, original numbering                                    */
+    uint32_t n;               /* N: offspring informative at both                                         */
+    uint32_t rec_phase;       /* rec | phase << 31                                                        */
+    int64_t lod16;
+} td_link_edge;               /* 24 bytes */
+enum {
+    TD_LINK_MAX_SAMPLES = 16384,
+    TD_LINK_MAX_MARKERS = 1 << 20,
+    TD_LINK_TILE = 64         /* markers along a workgroup's tile edge                                    */
+};
+int td_link_counts(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const uint32_t *rows /* HOST, R, or NULL = all */,
+                   uint32_t R, uint32_t *counts_out /* HOST, M x 4 */, double *ms);
+int td_link_pairs(td_handle *h, const void *d_calls, uint32_t S, uint32_t M, const uint32_t *rows /* HOST, R, or NULL = all */,
+                  uint32_t R, const uint8_t *cls /* HOST, M bytes */, const int64_t *lodtab /* HOST, R + 1 */, uint32_t max_rf_ppm,
+                  int64_t min_lod16, uint32_t min_shared, td_link_edge *edges_out /* HOST, capacity records, or NULL */,
+                  uint64_t capacity, uint64_t *n_out, uint32_t *degree_out /* HOST, M, or NULL */,
+                  uint32_t *informative_out /* HOST, M, or NULL */, double *ms);
+int td_link_last_times(td_handle *h, double *out4 /* counts, gather, pair kernel ms, sort ms of this thread's last calls */);
+
 /* ---- LD-kNN imputation of the missing calls (csrc/impute.hip; tagdigger_amd/tagdigger_fun.py impute_calls drives it) ----
  *
  * Fills the holes of the call matrix from the samples most alike over the markers most in LD.  d_calls

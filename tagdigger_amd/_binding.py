@@ -212,6 +212,9 @@ def load():
     sig("td_relate_joint", i32, vp, vp, u32, u32, vp, vp, C.POINTER(vp), dp)
     sig("td_ld_pairs", i32, vp, vp, u32, u32, vp, u32, u32, vp, u64, C.POINTER(u64), vp, vp, dp)
     sig("td_ld_last_times", i32, vp, dp)
+    sig("td_link_counts", i32, vp, vp, u32, u32, vp, u32, vp, dp)
+    sig("td_link_pairs", i32, vp, vp, u32, u32, vp, u32, vp, vp, u32, C.c_int64, u32, vp, u64, C.POINTER(u64), vp, vp, dp)
+    sig("td_link_last_times", i32, vp, dp)
     sig("td_impute_knn", i32, vp, vp, u32, u32, vp, C.POINTER(ImputeParams), vp, C.POINTER(vp), vp, dp)
     sig("td_impute_last_times", i32, vp, dp)
     sig("td_parent_trios", i32, vp, vp, u32, u32, vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, dp)
@@ -244,6 +247,7 @@ EXPORTS = [
     "td_impute_knn", "td_impute_last_times",
     "td_parent_trios", "td_parent_last_times",
     "td_dose_call",
+    "td_link_counts", "td_link_pairs", "td_link_last_times",
 ]
 
 

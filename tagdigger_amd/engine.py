@@ -247,6 +247,21 @@ class LDPairs(collections.namedtuple("LDPairs", "edges n degree called ms times"
     __slots__ = ()
 
 
+LINK_MAX_SAMPLES = 16384    # TD_LINK_MAX_SAMPLES: offspring rows of one call
+LINK_MAX_MARKERS = 1 << 20  # TD_LINK_MAX_MARKERS: participating markers of one call
+LINK_TILE = 64              # TD_LINK_TILE: markers along a workgroup's tile edge of csrc/link.hip
+LINK_EDGE = [("i", "<u4"), ("j", "<u4"), ("n", "<u4"), ("rec_phase", "<u4"), ("lod16", "<i8")]    # td_link_edge
+LINK_NO_PART = 255          # the cls byte of a marker that takes no part
+LINK_LOD_MIN = -(1 << 63)   # min_lod16 with the LOD test off
+
+
+class LinkPairs(collections.namedtuple("LinkPairs", "edges n degree informative ms times")):
+    """What Engine.link_pairs returns: edges (structured array with the fields of td_link_edge, ascending by (i, j)), n
+    (how many there are), degree and informative (uint32 [M]), ms (device time of the two kernels), times (dict:
+    gather_ms and pairs_ms on the device, sort_ms on the host, of the call that returned the edges)."""
+    __slots__ = ()
+
+
 IMPUTE_MAX_SAMPLES = 4096   # TD_IMPUTE_MAX_SAMPLES: the samples' planes lie in one workgroup's LDS
 IMPUTE_MAX_NBR = 64         # TD_IMPUTE_MAX_NBR: a plane is one 64-bit word per sample
 IMPUTE_MAX_K = 32           # TD_IMPUTE_MAX_K: voters of a cell
@@ -1024,6 +1039,82 @@ class Engine:
         B.check(self._L.td_ld_last_times(self._h, t))
         return LDPairs(edges[:0 if count_only else n.value].copy(), n.value, degree[:M], called[:M], total_ms,
                        dict(transpose_ms=t[0], pairs_ms=t[1], sort_ms=t[2]))
+
+    # ------------------------------------------------------------------ linkage of a cross (td_link_counts, td_link_pairs; csrc/link.hip)
+    @staticmethod
+    def _offspring_rows(rows):
+        """The offspring rows as a uint32 array, or None for all rows (the library checks the indices)."""
+        import numpy as np
+        if rows is None:
+            return None
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        if rows.ndim != 1:
+            raise ValueError("rows must be a list of row indices")
+        return rows
+
+    def link_counts(self, calls, shape=None, rows=None):
+        """td_link_counts: (c0, c1, c2, cmiss) of every marker over the offspring rows (any byte above 2 is missing).
+        calls is a numpy uint8 matrix [S, M] (uploaded) or a device pointer with shape=(S, M).  rows: the offspring row
+        indices (None: every row).  Returns (counts uint32 [M, 4], ms).  A failure raises TagdigError."""
+        import numpy as np
+        rows = self._offspring_rows(rows)
+        with self._device_matrix(calls, shape, np.uint8, "markers") as (d_calls, S, M):
+            R = S if rows is None else len(rows)
+            counts = np.zeros((max(1, M if M < 1 << 31 else 1), 4), dtype=np.uint32)
+            ms = C.c_double(0)
+            rc = self._L.td_link_counts(self._h, C.c_void_p(d_calls) if d_calls else None, S, M,
+                                        rows.ctypes.data_as(C.c_void_p) if rows is not None else None, R,
+                                        counts.ctypes.data_as(C.c_void_p), C.byref(ms))
+        B.check(rc)
+        return counts[:M], ms.value
+
+    def link_pairs(self, calls, cls, lodtab, shape=None, rows=None, max_rf_ppm=500000, min_lod16=LINK_LOD_MIN, min_shared=0,
+                   capacity=None, retry=True, count_only=False):
+        """td_link_pairs: the pairs of participating markers i < j with N >= min_shared, rec * 10^6 <= max_rf_ppm * N and
+        lod16 >= min_lod16 over the offspring rows (include/tagdig.h has the rule).  calls is a numpy uint8 matrix [S, M]
+        (uploaded) or a device pointer with shape=(S, M).  cls: M bytes, a marker's class pair 0 = (A 0, B 1), 1 = (A 2,
+        B 1), 2 = (A 0, B 2) or LINK_NO_PART.  lodtab: int64, at least R + 1 entries (tagdigger_fun.linkage_tables).
+        rows: the offspring row indices (None: every row).  capacity, retry, count_only: as Engine.ld_pairs; the
+        TagdigError of TD_E_LIMIT carries `.n`, `.degree` and `.informative`.  Returns a LinkPairs."""
+        import numpy as np
+        rows = self._offspring_rows(rows)
+        if cls is not None:
+            cls = np.ascontiguousarray(cls, dtype=np.uint8)
+        if lodtab is not None:
+            lodtab = np.ascontiguousarray(lodtab, dtype=np.int64)
+        with self._device_matrix(calls, shape, np.uint8, "markers") as (d_calls, S, M):
+            R = S if rows is None else len(rows)
+            in_range = M < 1 << 31                               # (the library answers TD_E_ARG otherwise)
+            if cls is not None and in_range and cls.shape != (M,):
+                raise ValueError("cls must have one byte per marker")
+            if lodtab is not None and R <= LINK_MAX_SAMPLES and (lodtab.ndim != 1 or len(lodtab) < R + 1):
+                raise ValueError("lodtab must have at least R + 1 = {} entries".format(R + 1))
+            degree = np.zeros(max(1, M if in_range else 1), dtype=np.uint32)
+            informative = np.zeros(max(1, M if in_range else 1), dtype=np.uint32)
+            capacity = max(1 << 16, min(8 * M, 1 << 20) if in_range else 0) if capacity is None else max(0, int(capacity))
+            n, ms, total_ms = C.c_uint64(0), C.c_double(0), 0.0
+            for attempt in range(2):
+                edges = np.zeros(0 if count_only else max(1, capacity), dtype=LINK_EDGE)
+                rc = self._L.td_link_pairs(self._h, C.c_void_p(d_calls) if d_calls else None, S, M,
+                                           rows.ctypes.data_as(C.c_void_p) if rows is not None else None, R,
+                                           cls.ctypes.data_as(C.c_void_p) if cls is not None and cls.size else None,
+                                           lodtab.ctypes.data_as(C.c_void_p) if lodtab is not None else None, int(max_rf_ppm),
+                                           int(min_lod16), int(min_shared), None if count_only else edges.ctypes.data_as(C.c_void_p),
+                                           capacity, C.byref(n), degree.ctypes.data_as(C.c_void_p),
+                                           informative.ctypes.data_as(C.c_void_p), C.byref(ms))
+                total_ms += ms.value
+                if rc == B.TD_E_LIMIT and n.value > capacity and attempt == 0 and retry:     # once more with the exact size
+                    capacity = n.value
+                    continue
+                break
+        if rc:
+            err = self._error(rc)
+            err.n, err.degree, err.informative = n.value, degree[:M], informative[:M]
+            raise err
+        t = (C.c_double * 4)()
+        B.check(self._L.td_link_last_times(self._h, t))
+        return LinkPairs(edges[:0 if count_only else n.value].copy(), n.value, degree[:M], informative[:M], total_ms,
+                         dict(gather_ms=t[1], pairs_ms=t[2], sort_ms=t[3]))
 
     # ------------------------------------------------------------------ LD-kNN imputation (td_impute_knn; csrc/impute.hip)
     def impute_knn(self, calls, nbr, shape=None, k=10, min_overlap=4, min_conf_ppm=600000, fetch=True, keep_device=False):

@@ -2191,14 +2191,11 @@ def marker_ld(calls, marknames, mask=None, min_r2=0.8, min_shared=50, device=0, 
                     dict(backend=backend, ms=ms, markers=M, used=used, min_r2_ppm=min_r2_ppm, min_shared=min_shared))
 
 
-def ld_groups(result):
-    """The connected components of the participating markers under the edges (linkage groups, bins of co-segregating
-    markers): int64 [M], groups numbered from 1 in the order of their smallest marker, singletons included, 0 for a
-    marker that does not take part."""
+def _edge_components(M, edges):
+    """int64 [M]: for every marker the smallest marker of its connected component under the edges (fields i and j)."""
     import numpy as np
-    M = len(result.markers)
     label = np.arange(M, dtype=np.int64)
-    ei, ej = result.edges["i"].astype(np.int64), result.edges["j"].astype(np.int64)
+    ei, ej = edges["i"].astype(np.int64), edges["j"].astype(np.int64)
     while len(ei):                                 # every marker takes the smallest label around it, then its label's label
         new = label.copy()
         np.minimum.at(new, ei, label[ej])
@@ -2207,6 +2204,16 @@ def ld_groups(result):
         if np.array_equal(new, label):
             break
         label = new
+    return label
+
+
+def ld_groups(result):
+    """The connected components of the participating markers under the edges (linkage groups, bins of co-segregating
+    markers): int64 [M], groups numbered from 1 in the order of their smallest marker, singletons included, 0 for a
+    marker that does not take part."""
+    import numpy as np
+    M = len(result.markers)
+    label = _edge_components(M, result.edges)
     groups = np.zeros(M, dtype=np.int64)
     part = np.nonzero(result.mask)[0]
     roots = np.unique(label[part])                 # ascending: a component's label is its smallest marker
@@ -2759,6 +2766,450 @@ def writeTrios(filename, result):
             for k, (p, q, n, e) in enumerate(result.trios[i]):
                 out.writerow([result.samples[o], k + 1, result.samples[p], result.samples[q], n, e, _rate_text(e, n),
                               1 if result.passes[i][k] else 0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Linkage of the markers of a cross: which markers are linked, in which phase, in what order.  Only the
+# offspring rows enter a count.  A marker that takes part has two classes A and B (by the cross type, from its class
+# counts or the parents' calls); a cell is x = +1 for A, -1 for B, 0 otherwise.  For two markers of one map:
+# N = sum x_i^2 x_j^2, D = sum x_i x_j, rec = (N - |D|) / 2, phase = (D < 0), lod16 = 65536 N + f[rec] + f[N - rec] - f[N]
+# with f[k] = round(65536 k log2 k); an edge iff N >= min_shared, rec 10^6 <= max_rf_ppm N and lod16 >= min_lod16 --
+# integers only.  csrc/link.hip decides it on the matrix cores from the calls where they lie, _link_pairs_host restates
+# it in numpy; groups, order and positions are host code that both backends share.  Floats appear only in the positions.
+LINK_MAX_SAMPLES = 16384
+LINK_MAX_MARKERS = 1 << 20
+LINK_EDGE = [("i", "<u4"), ("j", "<u4"), ("n", "<u4"), ("rec_phase", "<u4"), ("lod16", "<i8")]
+LINK_NO_PART = 255
+LINK_LOD_MIN = -(1 << 63)
+LINK_CROSSES = ("dh", "bc", "cp")
+LINK_CLASSES = ((0, 1), (2, 1), (0, 2))            # the cls code of a marker -> its classes (A, B)
+LINK_REASONS = ("", "parents", "masked", "few", "distorted", "other")
+_LINK_HOST_CELLS = 1 << 21  # pairs of one block of _link_pairs_host
+_LINK_TABLE = [0, 0]        # f[0 .. ]: grown by linkage_tables, never shrunk
+
+
+def _link_entry(k, prec):
+    """round_half_even(65536 k log2 k) for k >= 1 with decimal at `prec` digits, or None where that precision cannot
+    tell on which side of a half the value lies."""
+    import decimal
+    with decimal.localcontext() as ctx:
+        ctx.prec = prec
+        v = decimal.Decimal(65536 * k) * decimal.Decimal(k).ln() / decimal.Decimal(2).ln()
+        lo = v.to_integral_value(rounding=decimal.ROUND_FLOOR)
+        slack = decimal.Decimal(10) ** (v.adjusted() + 5 - prec)       # far above the error of two ln and two operations
+        if abs(v - lo - decimal.Decimal("0.5")) <= slack and (k & (k - 1)):
+            return None
+        return int(v.quantize(decimal.Decimal(1), rounding=decimal.ROUND_HALF_EVEN))
+
+
+def linkage_tables(n, prec=50):
+    """f[k] = round(65536 k log2 k) for k = 0 .. n (f[0] = 0) as a list of ints: the table behind the LOD of
+    linkage_map, lod16 = 65536 N + f[rec] + f[N - rec] - f[N] = 65536 log2 of the likelihood ratio of r = rec / N against
+    r = 1 / 2.  Pure Python (decimal, at a precision raised until every entry is unambiguous): the same on every machine."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must be at least 0")
+    while len(_LINK_TABLE) <= n:
+        k, p, e = len(_LINK_TABLE), int(prec), None
+        while e is None:
+            e = _link_entry(k, p)
+            p *= 2
+        _LINK_TABLE.append(e)
+    return _LINK_TABLE[:n + 1]
+
+
+def linkage_min_lod16(min_lod):
+    """ceil(min_lod * 65536 * log2 10), from the decimal text of min_lod: the threshold lod16 is compared with."""
+    import decimal
+    with decimal.localcontext() as ctx:
+        ctx.prec = 60
+        v = decimal.Decimal(str(min_lod)) * 65536 * decimal.Decimal(10).ln() / decimal.Decimal(2).ln()
+        return int(v.to_integral_value(rounding=decimal.ROUND_CEILING))
+
+
+def _link_scaled(value, scale, lo, hi, what):
+    """A decimal option as an integer in units of 1 / scale, from its decimal text (rounded half even), in lo .. hi."""
+    import decimal
+    v = int((decimal.Decimal(str(value)) * scale).quantize(decimal.Decimal(1), rounding=decimal.ROUND_HALF_EVEN))
+    if not lo <= v <= hi:
+        raise ValueError("{} must lie in {} .. {}".format(what, lo / scale, hi / scale))
+    return v
+
+
+def linkage_classes(cross, counts, parent_calls=None):
+    """(map_of, cls) of every marker, int8 and uint8 [M]: the map a marker belongs to (1 or 2; 0: none) and its class
+    pair as an index into LINK_CLASSES (LINK_NO_PART where map_of is 0).  dh: A = 0, B = 2.  bc: (0, 1) if c0 >= c2 else
+    (2, 1), from counts [M, 4].  cp: parent_calls = (calls of parent 1, calls of parent 2) over the markers; map 1 iff
+    parent 1 is 1 and parent 2 is 0 or 2, then A = parent 2's call and B = 1; map 2 with the roles swapped."""
+    import numpy as np
+    if cross not in LINK_CROSSES:
+        raise ValueError("cross must be one of {}".format(", ".join(LINK_CROSSES)))
+    counts = np.asarray(counts).reshape(-1, 4)
+    M = len(counts)
+    map_of, cls = np.ones(M, dtype=np.int8), np.full(M, 2, dtype=np.uint8)
+    if cross == "bc":
+        cls[:] = np.where(counts[:, 0] >= counts[:, 2], 0, 1)
+    elif cross == "cp":
+        if parent_calls is None:
+            raise ValueError("cross 'cp' needs the calls of its two parents")
+        p1, p2 = (np.asarray(p, dtype=np.uint8).reshape(M) for p in parent_calls)
+        hom1, hom2 = (p1 == 0) | (p1 == 2), (p2 == 0) | (p2 == 2)
+        in1, in2 = (p1 == 1) & hom2, (p2 == 1) & hom1
+        map_of[:] = np.where(in1, 1, np.where(in2, 2, 0))
+        hom = np.where(in1, p2, p1)                # the homozygous parent's call: class A
+        cls[:] = np.where(map_of == 0, LINK_NO_PART, np.where(hom == 0, 0, 1))
+    return map_of, cls
+
+
+def linkage_segregation(counts, cls, min_shared, max_chi2_milli, max_other_ppm):
+    """(a, b, o, verdict) per marker from counts [M, 4] and the class pairs: a = count(A), b = count(B), o = the called
+    cells that are neither (int64 [M]; 0 where cls is LINK_NO_PART), verdict (uint8 [M], an index into LINK_REASONS): 0
+    iff the marker segregates -- a + b >= min_shared, (a - b)^2 1000 <= max_chi2_milli (a + b) and
+    o 10^6 <= max_other_ppm (a + b + o) -- else the first test that fails; 1 where it has no class pair."""
+    import numpy as np
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+    cls = np.asarray(cls, dtype=np.uint8)
+    part = cls != LINK_NO_PART
+    k = np.where(part, cls, 0)
+    ab = np.array(LINK_CLASSES, dtype=np.int64)
+    rows = np.arange(len(counts))
+    a = np.where(part, counts[rows, ab[k, 0]], 0)
+    b = np.where(part, counts[rows, ab[k, 1]], 0)
+    o = np.where(part, counts[:, :3].sum(axis=1) - a - b, 0)
+    verdict = np.zeros(len(counts), dtype=np.uint8)
+    # (a - b)^2 1000 < 2^38 and o 10^6 < 2^34: int64 holds every product
+    verdict[o * 1000000 > max_other_ppm * (a + b + o)] = 5
+    verdict[(a - b) ** 2 * 1000 > max_chi2_milli * (a + b)] = 4
+    verdict[a + b < min_shared] = 3
+    verdict[~part] = 1
+    return a, b, o, verdict
+
+
+def _link_counts_host(calls, rows):
+    import numpy as np
+    part = calls[rows]
+    return np.stack([(part == 0).sum(axis=0), (part == 1).sum(axis=0), (part == 2).sum(axis=0), (part > 2).sum(axis=0)],
+                    axis=1).astype(np.uint32).reshape(calls.shape[1], 4)
+
+
+def _link_pairs_host(calls, rows, cls, lodtab, max_rf_ppm, min_lod16, min_shared):
+    """Step 2 of DESIGN 4.24 in numpy, over blocks of markers: D and N as float32 products (at most 16384, exact
+    there), everything after them in 64-bit integers.  Returns (edges ascending by (i, j), degree, informative)."""
+    import numpy as np
+    M = calls.shape[1]
+    cols = np.nonzero(cls != LINK_NO_PART)[0]
+    part = calls[np.asarray(rows, dtype=np.int64)][:, cols]
+    ab = np.array(LINK_CLASSES, dtype=np.uint8)[cls[cols]]
+    X = (part == ab[None, :, 0]).astype(np.float32) - (part == ab[None, :, 1]).astype(np.float32)
+    V = np.abs(X)
+    informative, degree = np.zeros(M, dtype=np.uint32), np.zeros(M, dtype=np.uint32)
+    informative[cols] = V.sum(axis=0).astype(np.uint32)
+    tab = np.asarray(lodtab, dtype=np.int64)
+    Mp, found = len(cols), []
+    block = max(1, _LINK_HOST_CELLS // max(1, Mp))
+    for lo in range(0, Mp if len(rows) else 0, block):
+        hi = min(Mp, lo + block)
+        d = np.rint(X[:, lo:hi].T @ X[:, lo:]).astype(np.int64)
+        n = np.rint(V[:, lo:hi].T @ V[:, lo:]).astype(np.int64)
+        rec = (n - np.abs(d)) // 2
+        lod = 65536 * n + tab[rec] + tab[n - rec] - tab[n]
+        edge = (n >= min_shared) & (rec * 1000000 <= max_rf_ppm * n) & (lod >= min_lod16)
+        edge &= np.arange(lo, Mp)[None, :] > np.arange(lo, hi)[:, None]                # i < j
+        bi, bj = np.nonzero(edge)                                                      # row-major: ascending (i, j)
+        e = np.zeros(len(bi), dtype=LINK_EDGE)
+        e["i"], e["j"], e["n"], e["lod16"] = cols[bi + lo], cols[bj + lo], n[bi, bj], lod[bi, bj]
+        e["rec_phase"] = rec[bi, bj] | ((d[bi, bj] < 0).astype(np.int64) << 31)
+        found.append(e)
+    edges = np.concatenate(found) if found else np.zeros(0, dtype=LINK_EDGE)
+    if len(edges):
+        degree += np.bincount(edges["i"], minlength=M).astype(np.uint32) + np.bincount(edges["j"], minlength=M).astype(np.uint32)
+    return edges, degree, informative
+
+
+def linkage_groups(M, part, edges, min_group):
+    """The connected components of the participating markers (part: bool [M]) under the edges: int64 [M], the components
+    of at least min_group markers numbered from 1 in the order of their smallest marker, 0 for every other marker."""
+    import numpy as np
+    label = _edge_components(M, edges)
+    groups = np.zeros(M, dtype=np.int64)
+    members = np.nonzero(part)[0]
+    roots, sizes = np.unique(label[members], return_counts=True)      # ascending: a component's label is its smallest marker
+    roots = roots[sizes >= min_group]
+    kept = np.isin(label[members], roots)
+    groups[members[kept]] = np.searchsorted(roots, label[members[kept]]) + 1
+    return groups
+
+
+def linkage_order(members, edges, min_shared):
+    """The greedy chain of one group.  members: its markers, ascending; edges: every pair of them with n >= 1 (the pair
+    call with the thresholds off).  rf_ppm(u, v) = rec 10^6 // n where n >= min_shared, else 500000.  The chain starts
+    with the pair of smallest (rf_ppm, i, j); then the unplaced marker u and end e of smallest (rf_ppm(e, u), u, e is the
+    right end) is appended at e, until none remains; the end holding the smaller marker comes first.  Returns (order,
+    positions, phases): the markers along the chain, cumulative Kosambi centimorgans of the adjacent pairs
+    (25 ln((1 + 2 r) / (1 - 2 r)), r = rec / n capped at 0.499; 0.499 where n = 0) and the phase of every marker relative
+    to the first (its left neighbour's XOR the pair's)."""
+    import math
+    import numpy as np
+    members = np.asarray(members, dtype=np.int64)
+    g = len(members)
+    if g == 0:
+        return [], [], []
+    li, lj = np.searchsorted(members, edges["i"]), np.searchsorted(members, edges["j"])
+    n = np.zeros((g, g), dtype=np.int64)
+    rec, ph = np.zeros((g, g), dtype=np.int64), np.zeros((g, g), dtype=np.int64)
+    n[li, lj] = n[lj, li] = edges["n"]
+    rec[li, lj] = rec[lj, li] = edges["rec_phase"] & 0x7fffffff
+    ph[li, lj] = ph[lj, li] = edges["rec_phase"] >> 31
+    rf = np.where(n >= max(1, min_shared), rec * 1000000 // np.maximum(n, 1), 500000)
+    if g == 1:
+        chain = [0]
+    else:
+        iu, ju = np.triu_indices(g, 1)                                 # ascending (i, j): the first minimum is the smallest
+        first = int(np.argmin(rf[iu, ju]))
+        chain = [int(iu[first]), int(ju[first])]
+        free = np.ones(g, dtype=bool)
+        free[chain] = False
+        local = np.arange(g, dtype=np.int64)
+        while free.any():
+            left, right = chain[0], chain[-1]
+            key = np.concatenate([(rf[left] << 32) | (local << 1), (rf[right] << 32) | (local << 1) | 1])
+            key[np.concatenate([~free, ~free])] = np.iinfo(np.int64).max
+            at = int(np.argmin(key))
+            u = at % g
+            if at >= g:
+                chain.append(u)
+            else:
+                chain.insert(0, u)
+            free[u] = False
+        if chain[0] > chain[-1]:
+            chain.reverse()
+    positions, phases = [0.0], [0]
+    for u, v in zip(chain, chain[1:]):
+        r = min(int(rec[u, v]) / int(n[u, v]), 0.499) if n[u, v] else 0.499
+        positions.append(positions[-1] + 25.0 * math.log((1.0 + 2.0 * r) / (1.0 - 2.0 * r)))
+        phases.append(phases[-1] ^ int(ph[u, v]))
+    return [int(members[k]) for k in chain], positions, phases
+
+
+class LinkageMap:
+    """One map of a LinkageResult: `.number` (1 or 2), `.cls` (uint8 [M]: the class pair of the markers that take part,
+    LINK_NO_PART elsewhere), `.edges` (structured array i, j, n, rec_phase, lod16; ascending by (i, j)), `.rec` and
+    `.phase` (per edge), `.degree` and `.informative` (uint32 [M]), `.groups` (int64 [M], from 1; 0: in no group),
+    `.order` (dict group -> the markers along the chain, or ascending where the group is too large to order),
+    `.positions` and `.phases` (dict group -> list of cM / 0-1 per marker of `.order`, None where unordered)."""
+
+    def __init__(self, number, cls, edges, degree, informative):
+        self.number, self.cls, self.edges, self.degree, self.informative = number, cls, edges, degree, informative
+        self.rec = (edges["rec_phase"] & 0x7fffffff).astype("int64")
+        self.phase = (edges["rec_phase"] >> 31).astype("int8")
+        self.groups, self.order, self.positions, self.phases = None, {}, {}, {}
+
+
+class LinkageResult:
+    """What linkage_map returns: `.samples`, `.markers`, `.cross`, `.parents` (row indices or None), `.offspring` (row
+    indices), `.counts` (uint32 [M, 4]: c0, c1, c2, cmiss over the offspring), `.map_of` (int8 [M]: 1, 2 or 0), `.cls`
+    (uint8 [M]), `.a`, `.b`, `.o` (int64 [M]), `.verdict` (uint8 [M], an index into LINK_REASONS; 0: takes part),
+    `.maps` (list of LinkageMap), `.warnings` (list of lines), `.stats` (backend, ms, the integer thresholds)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _link_rows(names, samnames, what):
+    """Row indices from a list of names or indices."""
+    out = []
+    for x in names:
+        if isinstance(x, str):
+            if x not in samnames:
+                raise ValueError("{} {!r} is not among the samples".format(what, x))
+            out.append(samnames.index(x))
+        else:
+            if not 0 <= int(x) < len(samnames):
+                raise ValueError("{} {} is no row of the call matrix".format(what, x))
+            out.append(int(x))
+    if len(set(out)) != len(out):
+        raise ValueError("a {} is listed twice".format(what))
+    return out
+
+
+def linkage_map(calls, samnames, marknames, cross, parents=None, offspring=None, mask=None, min_lod=3, max_rf=0.25, min_shared=50,
+                max_chi2=6.635, max_other=0.05, min_group=3, max_order=4096, device=0, backend="gpu"):
+    """The linkage map of a cross from its genotype calls.
+
+    calls: a samples x markers matrix of codes 0, 1, 2 and 3 (missing) -- numpy or lists -- or a DeviceCalls
+    (backend="gpu" only; there any byte above 2 is missing).  cross: "dh" (doubled haploids), "bc" (backcross) or "cp"
+    (pseudo-testcross of an outcrossing F1: two maps, one per parent).  parents: the two parent rows (names or indices;
+    needed for "cp", optional otherwise); offspring: the rows that enter the counts (names or indices; None: every row
+    that is no parent).  mask: one entry per marker, a marker can take part iff its entry is true.  Markers that
+    segregate as their class pair demands (linkage_segregation) are compared pairwise; the pairs with at least
+    min_shared informative offspring, a recombination fraction of at most max_rf and a LOD of at least min_lod are the
+    edges, their connected components of at least min_group markers the linkage groups, and every group of at most
+    max_order markers is ordered by the greedy chain of linkage_order.  backend="gpu" runs csrc/link.hip on the calls
+    where they lie; backend="host" is the numpy restatement: the same result.  Returns a LinkageResult."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    if cross not in LINK_CROSSES:
+        raise ValueError("cross must be one of {}".format(", ".join(LINK_CROSSES)))
+    max_rf_ppm = _link_scaled(max_rf, 1000000, 0, 500000, "max_rf")
+    max_chi2_milli = _link_scaled(max_chi2, 1000, 0, 1 << 40, "max_chi2")
+    max_other_ppm = _link_scaled(max_other, 1000000, 0, 1000000, "max_other")
+    min_lod16 = linkage_min_lod16(min_lod)
+    for name, v in (("min_shared", min_shared), ("min_group", min_group), ("max_order", max_order)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= v < 1 << 32:
+            raise ValueError("{} must be an integer of at least 0".format(name))
+    min_shared, min_group, max_order = int(min_shared), int(min_group), int(max_order)
+    on_device = isinstance(calls, DeviceCalls)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCalls matrix needs backend='gpu'")
+    samnames, marknames = list(samnames), list(marknames)
+    if not on_device:
+        calls = np.asarray(calls if len(calls) else np.zeros((0, len(marknames)), dtype=np.uint8))
+        if calls.ndim != 2:
+            raise ValueError("the call matrix must have two dimensions (samples x markers)")
+        if calls.dtype.kind not in "iub":
+            raise ValueError("the call matrix must hold the integer codes 0 .. 3, not {}".format(calls.dtype))
+        if calls.size and (int(calls.min()) < 0 or int(calls.max()) > 3):
+            raise ValueError("the call matrix must hold 0, 1, 2 or 3 (missing) only")
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+    S, M = calls.shape
+    if len(samnames) != S:
+        raise ValueError("samnames must name every row of the call matrix")
+    if len(marknames) != M:
+        raise ValueError("marknames must name every column of the call matrix")
+    if M >= 1 << 31:
+        raise ValueError("markers must number below 2^31")
+    parents = None if parents is None else _link_rows(parents, samnames, "parent")
+    if cross == "cp" and (parents is None or len(parents) != 2):
+        raise ValueError("cross 'cp' needs its two parents")
+    if offspring is None:
+        offspring = [s for s in range(S) if parents is None or s not in parents]
+    else:
+        offspring = _link_rows(offspring, samnames, "offspring")
+        if parents is not None and set(offspring) & set(parents):
+            raise ValueError("a parent is listed among the offspring")
+    if len(offspring) > LINK_MAX_SAMPLES:
+        raise ValueError("at most {} offspring".format(LINK_MAX_SAMPLES))
+    rows = np.array(offspring, dtype=np.uint32)
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != (M,):
+            raise ValueError("mask must have one entry per marker")
+        mask = mask != 0
+    eng = default_engine(device) if backend == "gpu" else None
+    matrix, shape = (calls.ptr or None, (S, M)) if on_device else (calls, None)
+    d_own = None
+    if eng is not None and not on_device and calls.size:               # one upload serves every call below
+        d_own = eng.dev_alloc(calls.nbytes)
+        eng.h2d(d_own, calls.tobytes())
+        matrix, shape = d_own, (S, M)
+    try:
+        total_ms = 0.0
+        if eng is None:
+            counts = _link_counts_host(calls, rows)
+        else:
+            counts, ms = eng.link_counts(matrix, shape=shape, rows=rows)
+            total_ms += ms
+        parent_calls = None
+        if cross == "cp":
+            if on_device:
+                parent_calls = [np.frombuffer(eng.d2h(calls.ptr + p * M, M), dtype=np.uint8) if M else np.zeros(0, np.uint8) for p in parents]
+            else:
+                parent_calls = [calls[p] for p in parents]
+        map_of, cls = linkage_classes(cross, counts, parent_calls)
+        a, b, o, verdict = linkage_segregation(counts, cls, min_shared, max_chi2_milli, max_other_ppm)
+        if mask is not None:
+            verdict[(verdict != 1) & ~mask] = 2
+        lodtab = np.array(linkage_tables(len(rows)), dtype=np.int64)
+
+        def pair_call(use_cls, rf_ppm, lod16, shared, capacity=None):
+            if eng is None:
+                return _link_pairs_host(calls, rows, use_cls, lodtab, rf_ppm, lod16, shared) + (0.0,)
+            res = eng.link_pairs(matrix, use_cls, lodtab, shape=shape, rows=rows, max_rf_ppm=rf_ppm, min_lod16=lod16, min_shared=shared,
+                                 capacity=capacity)
+            return res.edges, res.degree, res.informative, res.ms
+
+        maps, warnings = [], []
+        for number in ((1, 2) if cross == "cp" else (1,)):
+            taking = (map_of == number) & (verdict == 0)
+            if int(taking.sum()) > LINK_MAX_MARKERS:
+                raise ValueError("{} participating markers, at most {}".format(int(taking.sum()), LINK_MAX_MARKERS))
+            map_cls = np.where(taking, cls, LINK_NO_PART).astype(np.uint8)
+            edges, degree, informative, ms = pair_call(map_cls, max_rf_ppm, min_lod16, min_shared)
+            total_ms += ms
+            lm = LinkageMap(number, map_cls, edges, degree, informative)
+            lm.groups = linkage_groups(M, taking, edges, min_group)
+            for g in range(1, int(lm.groups.max()) + 1 if M else 1):
+                members = np.nonzero(lm.groups == g)[0]
+                if len(members) > max_order:
+                    warnings.append("map {} group {}: {} markers, more than --max-order {}: written unordered".format(
+                        number, g, len(members), max_order))
+                    lm.order[g], lm.positions[g], lm.phases[g] = [int(m) for m in members], None, None
+                    continue
+                group_cls = np.full(M, LINK_NO_PART, dtype=np.uint8)
+                group_cls[members] = map_cls[members]
+                within, _, _, ms = pair_call(group_cls, 500000, LINK_LOD_MIN, 1, capacity=max(1, len(members) * (len(members) - 1) // 2))
+                total_ms += ms
+                lm.order[g], lm.positions[g], lm.phases[g] = linkage_order(members, within, min_shared)
+            maps.append(lm)
+    finally:
+        if d_own:
+            eng.dev_free(d_own)
+    return LinkageResult(samples=samnames, markers=marknames, cross=cross, parents=parents, offspring=offspring, counts=counts,
+                         map_of=map_of, cls=cls, a=a, b=b, o=o, verdict=verdict, maps=maps, warnings=warnings,
+                         stats=dict(backend=backend, ms=total_ms, markers=M, offspring=len(offspring), max_rf_ppm=max_rf_ppm,
+                                    min_lod16=min_lod16, min_shared=min_shared, max_chi2_milli=max_chi2_milli,
+                                    max_other_ppm=max_other_ppm, min_group=min_group, max_order=max_order))
+
+
+LINK_PAIR_COLUMNS = ("map", "marker_i", "marker_j", "n", "rec", "rf", "phase", "lod16", "lod")
+LINK_MAP_COLUMNS = ("map", "group", "order", "marker", "position_cM", "phase")
+LINK_STAT_COLUMNS = ("marker", "c0", "c1", "c2", "missing", "map", "class_a", "class_b", "a", "b", "other", "informative", "degree",
+                     "group", "dropped")
+_LINK_LOD_UNIT = 217705.98518566475               # 65536 log2 10: lod16 per unit of LOD
+
+
+def writeLinkagePairs(filename, result):
+    """One row per edge of every map: map, the two marker names, n, rec, rf = rec / n (six decimals), phase (C coupling /
+    R repulsion), lod16 and the LOD (three decimals); CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(LINK_PAIR_COLUMNS)
+        for lm in result.maps:
+            for e, rec, ph in zip(lm.edges.tolist(), lm.rec.tolist(), lm.phase.tolist()):
+                out.writerow([lm.number, result.markers[e[0]], result.markers[e[1]], e[2], rec, format(rec / e[2] if e[2] else 0.0, ".6f"),
+                              "R" if ph else "C", e[4], format(e[4] / _LINK_LOD_UNIT, ".3f")])
+
+
+def writeLinkageMap(filename, result):
+    """One row per placed marker: map, group, order (from 1 along the chain), marker, position in centimorgans (three
+    decimals) and phase (0 / 1 relative to the group's first marker); a group too large to order has blank order,
+    position and phase.  CSV with a header row, csv.writer's CRLF rows."""
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(LINK_MAP_COLUMNS)
+        for lm in result.maps:
+            for g in sorted(lm.order):
+                ordered = lm.positions[g] is not None
+                for k, m in enumerate(lm.order[g]):
+                    out.writerow([lm.number, g, k + 1 if ordered else "", result.markers[m],
+                                  format(lm.positions[g][k], ".3f") if ordered else "", lm.phases[g][k] if ordered else ""])
+
+
+def writeLinkageStats(filename, result):
+    """One row per marker: its counts over the offspring, map, class pair, a, b, other, informative, degree and group
+    (blank where it takes no part) and why it was dropped (blank: it takes part); CSV with a header row, CRLF rows."""
+    by_map = {lm.number: lm for lm in result.maps}
+    with open(filename, mode='w', newline='') as fh:
+        out = _csv.writer(fh)
+        out.writerow(LINK_STAT_COLUMNS)
+        for m, name in enumerate(result.markers):
+            k, v = int(result.map_of[m]), int(result.verdict[m])
+            row = [name] + [int(x) for x in result.counts[m]] + [k]
+            row += list(LINK_CLASSES[int(result.cls[m])]) + [int(result.a[m]), int(result.b[m]), int(result.o[m])] if v != 1 else [""] * 5
+            lm = by_map.get(k)
+            row += [int(lm.informative[m]), int(lm.degree[m]), int(lm.groups[m])] if v == 0 else [""] * 3
+            out.writerow(row + [LINK_REASONS[v]])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
