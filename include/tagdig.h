@@ -1131,6 +1131,59 @@ int td_kernel_times_ms(td_handle *h, double *out, uint32_t capacity, uint32_t *l
  *         depends on it (tests: which source they exercised). */
 int td_debug_counters(td_handle *h, uint64_t out[24]);
 
+/* ---- VCF export: body lines formatted on the device (csrc/vcf.hip) ----
+ * A body line is prefix[k], then for every sample a tab and the cell, then '\n'.  prefix[k] = prefix[prefix_off[k] ..
+ * prefix_off[k + 1]) holds the eight fixed columns and FORMAT; the caller builds it, the library only copies it.  Line k
+ * is marker m = sel[k] (any order, repeats allowed).  For sample s: a = counts[s][i0[m]], b = counts[s][i1[m]] (the S x T
+ * uint32 matrix in device memory, as for td_geno_call), n = a + b (64-bit), code = calls[s][m] (the S x M uint8 matrix in
+ * device memory that td_geno_call or td_dose_call wrote), P = ploidy.  The cell is GT:AD:DP --
+ *   GT   code <= P: P - code times '0', then code times '1', joined by '/' (P = 2: 0/0, 0/1, 1/1); code > P (TD_GENO_MISSING
+ *        at P = 2, TD_DOSE_MISSING, anything else above P): '.' P times, joined by '/'
+ *   AD   a,b in decimal, allele 0 first        DP   n in decimal (up to 2^33 - 2)
+ * and with likelihoods = 1 (P = 2 only) :GQ:PL -- ".:." for a missing cell, else GQ:PL0,PL1,PL2 by this integer rule:
+ *   x, y = a, b scaled as td_geno_call scales them (n > 127: x = 127 a / n, y = 127 b / n, floor), whatever made the call
+ *   c[g] = y ca[g] + x cb[g], g = 0, 1, 2 (ca, cb: the three-entry cost tables of td_dose_call for P = 2, handed in as
+ *   data; the library checks only that no entry exceeds TD_DOSE_COST_MAX), cmin = min c
+ *   PL[g] = min(255, ((c[g] - cmin) 30103 + 327680000) / 655360000)      (10 log10(2) per bit, rounded half up; uint64)
+ *   GQ = min(99, min over g != code of PL[g])
+ * A cell with its tab is at most TD_VCF_CELL_MAX bytes.
+ *
+ * td_vcf_format: line_off_out[0 .. K] (optional) = the byte offset of every line, *n_out = line_off[K].  out == NULL:
+ * measure only, nothing is emitted.  Otherwise the text goes to out[0 .. *n_out) (HOST memory); a capacity below that is
+ * TD_E_LIMIT with *n_out set to the bytes needed.  ms (optional, 3): device ms of measure, scan, emit.
+ * td_vcf_file: the same text written to `path` (append = 0 truncates, 1 appends); *ranges_out (optional) = the ranges it
+ * was emitted in; ms (optional, 4): the three and the wall ms spent in write().
+ * Emission runs in ranges of consecutive lines of at most range_bytes bytes together (at least one line: a line longer
+ * than the budget is a range of its own), double-buffered: a range is formatted while the one before it is copied to the
+ * host and written.  K = 0 gives *n_out = 0, S = 0 lines of prefix and '\n'; neither launches anything (ranges: 0).
+ * TD_E_ARG (td_last_bad_index where an index is at fault): NULL arguments, a ploidy outside 2 .. TD_DOSE_MAX_PLOIDY,
+ * likelihoods with P != 2, a table entry above TD_DOSE_COST_MAX, a marker whose columns are not both below T or are equal
+ * (index m), sel[k] >= M (index k), prefix_off[k + 1] < prefix_off[k] (index k), a count matrix that is not 4-byte
+ * aligned.  TD_E_IO: the file cannot be opened or written.  TD_E_LIMIT: more than 65 535 chunks of TD_VCF_CHUNK samples,
+ * more than TD_VCF_MAX_LINES lines.  The module keeps no state: nothing is left latched after an error. */
+typedef struct td_vcf_params {
+    uint32_t ploidy;          /* 2 .. TD_DOSE_MAX_PLOIDY                                                  */
+    uint32_t likelihoods;     /* 0 | 1; 1 needs ploidy 2                                                  */
+    uint64_t range_bytes;     /* 0: TD_VCF_RANGE_BYTES                                                    */
+    uint32_t ca[3], cb[3];    /* read with likelihoods = 1                                                */
+} td_vcf_params;
+enum {
+    TD_VCF_CELL_MAX = 64,     /* bytes of a cell with its tab, at most                                    */
+    TD_VCF_CHUNK = 64,        /* samples per workgroup of the measure and emit kernels                    */
+    TD_VCF_TILE = 64,         /* lines per workgroup of the emit kernel                                   */
+    TD_VCF_MTILE = 256,       /* lines per workgroup of the measure kernel                                */
+    TD_VCF_MAX_LINES = 1 << 30
+};
+/* the default budget of a range: a choice that has not been measured */
+#define TD_VCF_RANGE_BYTES (256ull << 20)
+int td_vcf_format(td_handle *h, const void *d_counts, uint32_t S, uint32_t T, uint32_t M, const uint32_t *i0, const uint32_t *i1,
+                  const void *d_calls, const td_vcf_params *p, const uint32_t *sel /* HOST, K */, uint32_t K,
+                  const uint8_t *prefix /* HOST */, const uint64_t *prefix_off /* HOST, K + 1 */, uint64_t *line_off_out,
+                  uint8_t *out, uint64_t capacity, uint64_t *n_out, double *ms);
+int td_vcf_file(td_handle *h, const void *d_counts, uint32_t S, uint32_t T, uint32_t M, const uint32_t *i0, const uint32_t *i1,
+                const void *d_calls, const td_vcf_params *p, const uint32_t *sel, uint32_t K, const uint8_t *prefix,
+                const uint64_t *prefix_off, const char *path, int append, uint64_t *n_out, uint64_t *ranges_out, double *ms);
+
 /* ---- device memory helpers (so a binding needs no other GPU runtime) ------- */
 int td_dev_alloc(td_handle *h, uint64_t nbytes, void **d_out);
 int td_dev_free(td_handle *h, void *d_ptr);

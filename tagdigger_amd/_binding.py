@@ -59,6 +59,12 @@ class DoseParams(C.Structure):
                 ("min_depth", C.c_uint64), ("min_call_ppm", C.c_uint32), ("min_maf_ppm", C.c_uint32)]
 
 
+class VcfParams(C.Structure):
+    """td_vcf_params of include/tagdig.h"""
+    _fields_ = [("ploidy", C.c_uint32), ("likelihoods", C.c_uint32), ("range_bytes", C.c_uint64), ("ca", C.c_uint32 * 3),
+                ("cb", C.c_uint32 * 3)]
+
+
 class ImputeParams(C.Structure):
     """td_impute_params of include/tagdig.h"""
     _fields_ = [("L", C.c_uint32), ("k", C.c_uint32), ("min_overlap", C.c_uint32), ("min_conf_ppm", C.c_uint32)]
@@ -219,6 +225,9 @@ def load():
     sig("td_impute_last_times", i32, vp, dp)
     sig("td_parent_trios", i32, vp, vp, u32, u32, vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, dp)
     sig("td_parent_last_times", i32, vp, dp)
+    vcf_in = (vp, vp, u32, u32, u32, vp, vp, vp, C.POINTER(VcfParams), vp, u32, vp, vp)
+    sig("td_vcf_format", i32, *(vcf_in + (vp, vp, u64, C.POINTER(u64), dp)))
+    sig("td_vcf_file", i32, *(vcf_in + (C.c_char_p, i32, C.POINTER(u64), C.POINTER(u64), dp)))
     _lib = L
     return L
 
@@ -248,6 +257,7 @@ EXPORTS = [
     "td_parent_trios", "td_parent_last_times",
     "td_dose_call",
     "td_link_counts", "td_link_pairs", "td_link_last_times",
+    "td_vcf_format", "td_vcf_file",
 ]
 
 

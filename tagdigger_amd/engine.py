@@ -205,6 +205,22 @@ class DoseCalls(collections.namedtuple("DoseCalls", "calls diploid stats mask ms
     __slots__ = ()
 
 
+VCF_CHUNK = 64              # TD_VCF_CHUNK: samples per workgroup of csrc/vcf.hip's measure and emit kernels
+VCF_TILE = 64               # TD_VCF_TILE: lines per workgroup of its emit kernel
+VCF_MTILE = 256             # TD_VCF_MTILE: lines per workgroup of its measure kernel
+VCF_CELL_MAX = 64           # TD_VCF_CELL_MAX: bytes of a cell with its tab, at most
+VCF_RANGE_BYTES = 256 << 20  # TD_VCF_RANGE_BYTES: the default budget of a range (a choice that has not been measured)
+VCF_MS = ("measure", "scan", "emit")
+
+
+class VcfText(collections.namedtuple("VcfText", "text nbytes line_off ms ranges")):
+    """What Engine.vcf_format and Engine.vcf_file return: text (the body lines as bytes; None for a measuring call and
+    for a file), nbytes (their total), line_off (uint64 [K + 1], the byte offset of every line; None for a file), ms (dict
+    of device ms: measure, scan, emit; for a file also write, the wall ms spent in write()), ranges (a file: the ranges it
+    was emitted in; else None)."""
+    __slots__ = ()
+
+
 RELATE_MAX_SAMPLES = 16384  # TD_RELATE_MAX_SAMPLES: the joint table is 9 S^2 uint32
 RELATE_TILE = 64            # TD_RELATE_TILE: samples along a workgroup's tile edge of csrc/relate.hip
 RELATE_KCHUNK = 32768       # TD_RELATE_KCHUNK: markers per workgroup of csrc/relate.hip
@@ -979,6 +995,89 @@ class Engine:
             raise err
         return DoseCalls(calls, dip, {k: stats[:M, j].copy() for j, k in enumerate(DOSE_STATS)}, mask[:M].astype(bool), ms.value,
                          passed.value, d_calls.value if keep_device else None, d_dip.value if keep_diploid else None)
+
+    # ------------------------------------------------------------------ VCF export (td_vcf_format, td_vcf_file; csrc/vcf.hip)
+    @contextlib.contextmanager
+    def _vcf_inputs(self, counts, calls, i0, i1, sel, prefixes, shape, ploidy, likelihoods, ca, cb, range_bytes):
+        """The arguments both VCF entry points share, as ctypes values: (argument tuple, K).  counts as for geno_call
+        (shape=(S, T) with a device pointer); calls a uint8 matrix [S, M] (uploaded) or a device pointer; prefixes: K
+        bytes objects, or the pair (all bytes, K + 1 offsets)."""
+        import numpy as np
+        i0 = np.ascontiguousarray(i0, dtype=np.uint32)
+        i1 = np.ascontiguousarray(i1, dtype=np.uint32)
+        if i0.ndim != 1 or i0.shape != i1.shape:
+            raise ValueError("i0 and i1 must be two index lists of one length")
+        M = len(i0)
+        sel = np.ascontiguousarray(sel, dtype=np.uint32)
+        if sel.ndim != 1:
+            raise ValueError("sel must be a list of marker indices")
+        K = len(sel)
+        if isinstance(prefixes, tuple):
+            blob, poff = bytes(prefixes[0]), np.ascontiguousarray(prefixes[1], dtype=np.uint64)
+        else:
+            blob = b"".join(prefixes)
+            poff = np.zeros(len(prefixes) + 1, dtype=np.uint64)
+            if len(prefixes):
+                poff[1:] = np.cumsum([len(p) for p in prefixes], dtype=np.uint64)
+        if poff.shape != (K + 1,):
+            raise ValueError("one prefix per entry of sel (K + 1 offsets)")
+        par = B.VcfParams(int(ploidy), 1 if likelihoods else 0, int(range_bytes or 0))
+        if ca is not None or cb is not None:
+            ca, cb = [int(x) for x in ca], [int(x) for x in cb]
+            if len(ca) != 3 or len(cb) != 3:
+                raise ValueError("ca and cb must have three entries")
+            par.ca[:], par.cb[:] = ca, cb
+        with self._device_matrix(counts, shape, np.uint32, "tags", none_ok=False) as (d_counts, S, T):
+            with self._device_matrix(calls, (S, M) if isinstance(calls, int) else None, np.uint8, "markers", none_ok=False) as (d_calls, S2, M2):
+                if (S2, M2) != (S, M):
+                    raise ValueError("the call matrix must be samples x markers ({} x {}), not {} x {}".format(S, M, S2, M2))
+                idx0, idx1, selx = (a if len(a) else np.zeros(1, dtype=np.uint32) for a in (i0, i1, sel))
+                keep = (idx0, idx1, selx, poff, blob, par)           # alive until the call has returned
+                yield (self._h, C.c_void_p(d_counts) if d_counts else None, S, T, M, idx0.ctypes.data_as(C.c_void_p),
+                       idx1.ctypes.data_as(C.c_void_p), C.c_void_p(d_calls) if d_calls else None, C.byref(par),
+                       selx.ctypes.data_as(C.c_void_p), K, C.cast(C.c_char_p(blob), C.c_void_p), poff.ctypes.data_as(C.c_void_p)), K
+                del keep
+
+    def _vcf_error(self, rc):
+        err = self._error(rc)
+        err.bad_index = self._L.td_last_bad_index() if rc == -2 and err.detail.startswith(("marker ", "sel[", "prefix_off[")) else None
+        return err
+
+    def vcf_format(self, counts, calls, i0, i1, sel, prefixes, shape=None, ploidy=2, likelihoods=False, ca=None, cb=None,
+                   range_bytes=0, measure_only=False, capacity=None):
+        """td_vcf_format: the VCF body lines of the markers sel[k] -- prefixes[k], a tab and GT:AD:DP(:GQ:PL) per sample,
+        a newline -- formatted on the device from the count matrix and the calls (see include/tagdig.h).  counts and
+        shape as for geno_call; calls: a uint8 matrix [S, M] or the device pointer geno_call / dose_call kept.  ca, cb:
+        the three costs each of tagdigger_fun.dosage_tables(2, err), read with likelihoods.  measure_only=True emits
+        nothing.  capacity: the bytes of the output buffer (default: what a measuring call reports).  Returns a VcfText.
+        A failure raises TagdigError; `.bad_index` holds the index at fault, `.needed` the bytes for TD_E_LIMIT."""
+        import numpy as np
+        with self._vcf_inputs(counts, calls, i0, i1, sel, prefixes, shape, ploidy, likelihoods, ca, cb, range_bytes) as (args, K):
+            line_off = np.zeros(K + 1, dtype=np.uint64)
+            n_out, ms = C.c_uint64(0), (C.c_double * 3)()
+            rc = self._L.td_vcf_format(*args, line_off.ctypes.data_as(C.c_void_p), None, 0, C.byref(n_out), ms)
+            out = None
+            if not rc and not measure_only:
+                cap = n_out.value if capacity is None else int(capacity)
+                out = np.zeros(max(1, cap), dtype=np.uint8)
+                rc = self._L.td_vcf_format(*args, line_off.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cap,
+                                           C.byref(n_out), ms)
+        if rc:
+            err = self._vcf_error(rc)
+            err.needed = n_out.value
+            raise err
+        return VcfText(None if out is None else out[:n_out.value].tobytes(), n_out.value, line_off, dict(zip(VCF_MS, ms)), None)
+
+    def vcf_file(self, path, counts, calls, i0, i1, sel, prefixes, shape=None, ploidy=2, likelihoods=False, ca=None, cb=None,
+                 range_bytes=0, append=False):
+        """td_vcf_file: the text of vcf_format written to `path` (append=False truncates), range by range while the next
+        range is formatted.  Returns a VcfText without text or line offsets; `.ranges` is how many ranges it took."""
+        with self._vcf_inputs(counts, calls, i0, i1, sel, prefixes, shape, ploidy, likelihoods, ca, cb, range_bytes) as (args, K):
+            n_out, ranges, ms = C.c_uint64(0), C.c_uint64(0), (C.c_double * 4)()
+            rc = self._L.td_vcf_file(*args, os.fsencode(path), 1 if append else 0, C.byref(n_out), C.byref(ranges), ms)
+        if rc:
+            raise self._vcf_error(rc)
+        return VcfText(None, n_out.value, None, dict(zip(VCF_MS + ("write",), ms)), ranges.value)
 
     # ------------------------------------------------------------------ sample relations (td_relate_joint; csrc/relate.hip)
     def relate_joint(self, calls, shape=None, use=None, fetch=True, keep_device=False):

@@ -6,19 +6,21 @@ tags, and drops markers by call rate and minor allele frequency.
     python -m tagdigger_amd.tag_dosage -i counts.csv -o dosage.csv --ploidy 4 --stats stats.csv --min-call-rate 0.8 --min-maf 0.05
     python -m tagdigger_amd.tag_dosage -i counts.csv -o dosage.csv --ploidy 6 --prior flat --min-odds 20 --diploid calls.csv
     python -m tagdigger_amd.tag_dosage -b key.csv --MergedTags markers.csv -e PstI -o dosage.csv --ploidy 4
+    python -m tagdigger_amd.tag_dosage -i counts.csv -o dosage.csv --ploidy 4 --vcf dosage.vcf
 
 The input is the counter's CSV (samples in rows, tag names Marker_..._0 / Marker_..._1 in the header), or the
 libraries of a key file, which are counted first as tag_calls counts them: every library's barcode rows are folded into
 one samples x tags matrix on the device, and the calls are made from that matrix where it lies.  -o has
 writeGenoCalls' layout with the values 0 .. ploidy and the markers that pass.  --diploid writes the same markers
 diploidised (0 for no copy, 2 for all copies, 1 between): the file tag_relate -i, tag_ld -i, tag_impute -i and
-tag_parentage -i read.
+tag_parentage -i read.  --vcf writes the markers that pass as a VCF file (GT with `ploidy` alleles, AD, DP), formatted
+on the device from the matrix where it lies; --vcf-positions as for tag_calls.
 """
 import argparse
 import sys
 
 from . import tagdigger_fun as tf
-from .tag_calls import count_on_device, read_counts, read_tags
+from .tag_calls import add_vcf_options, count_on_device, read_counts, read_positions, read_tags
 from .tagdigger_script import FILE_OPTIONS, checked, cut_site
 
 
@@ -40,6 +42,7 @@ def build_parser():
     ap.add_argument("--stats", metavar="FILE", help="per-marker statistics CSV to write (every marker)")
     ap.add_argument("--diploid", metavar="FILE", help="diploidised genotype CSV to write (markers that pass; what tag_relate -i and tag_ld -i read)")
     ap.add_argument("--counts-out", metavar="FILE", help="with -b: write the samples x tags counts as well")
+    add_vcf_options(ap, likelihoods=False)
     ap.add_argument("--ploidy", type=int, default=4, help="allele copies of every sample, 2 .. 8")
     ap.add_argument("--prior", choices=list(tf.DOSE_PRIORS), default="hwe",
                     help="hwe: Hardy-Weinberg proportions at the marker's allele-1 read share; flat: none")
@@ -65,7 +68,10 @@ def main(argv=None):
         raise Exception("Need either a counts file (-i) or a key file whose libraries are counted (-b, tags and -e or -c).")
     params = dict(ploidy=args.ploidy, prior=args.prior, err=args.err, min_depth=args.min_depth, min_odds=args.min_odds,
                   min_call_rate=args.min_call_rate, min_maf=args.min_maf, device=args.td_device)
-    eng = d_counts = None
+    if args.vcf is None and args.vcf_positions is not None:
+        raise Exception("--vcf-positions goes with --vcf.")
+    positions = read_positions(args.vcf_positions)
+    eng = d_counts = sequences = None
     if args.counts is not None:
         if args.counts_out is not None:
             raise Exception("--counts-out goes with counting (-b); -i is that file already.")
@@ -92,6 +98,9 @@ def main(argv=None):
             import numpy as np
             host = np.frombuffer(eng.d2h(d_counts.ptr, d_counts.shape[0] * d_counts.shape[1] * 4), dtype=np.uint32)
             tf.writeCounts(args.counts_out, host.reshape(d_counts.shape), samples, names)
+        if args.vcf is not None:                         # (while the matrix is on the device)
+            tf.writeVCF(args.vcf, result, counts, tagseqs=sequences, positions=positions, passing_only=True, device=args.td_device,
+                        backend=backend)
     finally:
         if d_counts is not None:
             eng.dev_free(d_counts.ptr)

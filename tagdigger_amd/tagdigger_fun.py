@@ -1905,6 +1905,169 @@ def writeDosageStats(filename, result):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# VCF export: the calls with both read depths of every cell, GT:AD:DP and optionally GQ:PL, in the one
+# format every downstream tool reads.  Python writes the header and builds every line's first nine columns; the cells
+# -- a transpose of the sample-major matrices into variable-width text -- are formatted by csrc/vcf.hip from the count
+# matrix and the calls where they lie, or by numpy here (backend="host"), byte for byte the same.
+VCF_FIXED = ("#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT")
+VCF_HOST_BLOCK = 2048        # lines the host backend formats at a time
+
+
+def _vcf_position(name, positions):
+    """(chrom, pos) of a marker: from its name chrom-pos-strand (positions="names") or from the dict."""
+    if positions == "names":
+        parts = name.rsplit("-", 2)
+        if len(parts) != 3 or not parts[0] or not parts[1].isdigit():
+            raise Exception("Marker {}: its name does not read as chrom-pos-strand.".format(name))
+        return parts[0], int(parts[1])
+    if name not in positions:
+        raise Exception("Marker {}: no position given.".format(name))
+    chrom, pos = positions[name]
+    return str(chrom), int(pos)
+
+
+def _vcf_lines(result, tagseqs, positions, passing_only, ploidy, fmt):
+    """(marker index per line, prefix bytes per line, chromosomes in first-seen order or None): the lines in writing order
+    with their eight fixed columns and FORMAT."""
+    keep = _geno_selected(result, passing_only)
+    i0, i1 = result.columns
+    chroms = None
+    if positions is None:
+        where = {m: ("0", m + 1) for m in keep}
+    else:
+        where = {m: _vcf_position(result.markers[m], positions) for m in keep}
+        chroms = []
+        for m in keep:
+            if where[m][0] not in chroms:
+                chroms.append(where[m][0])
+        rank = {c: k for k, c in enumerate(chroms)}
+        keep = sorted(keep, key=lambda m: (rank[where[m][0]], where[m][1], m))
+    stats = result.stats
+    prefixes = []
+    for m in keep:
+        ref, alt = "N", "<ALLELE1>"
+        if tagseqs is not None:
+            t0, t1 = tagseqs[i0[m]].upper(), tagseqs[i1[m]].upper()
+            sites = [k for k in range(min(len(t0), len(t1))) if t0[k] != t1[k]]
+            if len(t0) == len(t1) and len(sites) == 1:
+                ref, alt = t0[sites[0]], t1[sites[0]]
+        called = int(stats["called"][m])
+        info = "NS={};DP={};AC={};AN={}".format(called, int(stats["depth0"][m]) + int(stats["depth1"][m]), int(stats["alt"][m]),
+                                                ploidy * called)
+        prefixes.append("\t".join([where[m][0], str(where[m][1]), result.markers[m], ref, alt, ".",
+                                   "PASS" if result.mask[m] else "filtered", info, fmt]).encode("utf-8"))
+    return keep, prefixes, chroms
+
+
+def _vcf_header(result, chroms, likelihoods, any_symbolic, any_filtered):
+    lines = ["##fileformat=VCFv4.2", "##source=tagdigger_amd"]
+    lines += ["##contig=<ID={}>".format(c) for c in chroms or []]
+    lines += ['##INFO=<ID=NS,Number=1,Type=Integer,Description="Samples with a call">',
+              '##INFO=<ID=DP,Number=1,Type=Integer,Description="Reads of both alleles over all samples">',
+              '##INFO=<ID=AC,Number=A,Type=Integer,Description="Copies of allele 1 among the calls">',
+              '##INFO=<ID=AN,Number=1,Type=Integer,Description="Allele copies among the calls">']
+    if any_filtered:
+        lines.append('##FILTER=<ID=filtered,Description="Outside the call rate, allele frequency or heterozygosity filters">')
+    lines += ['##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">',
+              '##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Reads of allele 0 and of allele 1">',
+              '##FORMAT=<ID=DP,Number=1,Type=Integer,Description="Reads of both alleles">']
+    if likelihoods:
+        lines += ['##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality: the smallest PL of another genotype, at most 99">',
+                  '##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Phred-scaled genotype likelihoods, at most 255">']
+    if any_symbolic:
+        lines.append('##ALT=<ID=ALLELE1,Description="The second tag of a marker whose tags are not one base apart">')
+    lines.append("\t".join(VCF_FIXED + tuple(result.samples)))
+    return ("\n".join(lines) + "\n").encode("utf-8")
+
+
+def _vcf_cells_host(a, b, code, ploidy, likelihoods, CA, CB):
+    """The cells of DESIGN 4.25 as a numpy array of strings, shaped like a, b (uint64) and code."""
+    import numpy as np
+    P = ploidy
+    gts = np.array(["/".join(["0"] * (P - c) + ["1"] * c) for c in range(P + 1)] + ["/".join(["."] * P)])
+    add = np.char.add
+    n = a + b
+    text = add(add(add(add(add(gts[np.minimum(code, P + 1)], ":"), a.astype(str)), ","), add(b.astype(str), ":")), n.astype(str))
+    if likelihoods:
+        deep = n > 127
+        div = np.where(deep, n, 1)
+        x = np.where(deep, 127 * a // div, a)
+        y = np.where(deep, 127 * b // div, b)
+        cost = [y * np.uint64(CA[g]) + x * np.uint64(CB[g]) for g in range(3)]
+        cmin = np.minimum(np.minimum(cost[0], cost[1]), cost[2])
+        pl = [np.minimum(((c - cmin) * np.uint64(30103) + np.uint64(327680000)) // np.uint64(655360000), 255) for c in cost]
+        gq = np.full(a.shape, 99, dtype=np.uint64)
+        for g in range(3):
+            gq = np.where(code != g, np.minimum(gq, pl[g]), gq)
+        lik = add(add(add(add(gq.astype(str), ":"), add(pl[0].astype(str), ",")), add(pl[1].astype(str), ",")), pl[2].astype(str))
+        text = add(add(text, ":"), np.where(code > 2, ".:.", lik))
+    return text
+
+
+def writeVCF(filename, result, counts, tagseqs=None, positions=None, passing_only=True, likelihoods=False, err=0.01,
+             range_bytes=None, device=0, backend="gpu"):
+    """The calls as a VCF 4.2 file with both read depths of every cell.
+
+    result: a GenoResult (ploidy 2) or a DosageResult; counts: the matrix it was called from, a numpy matrix or a
+    DeviceCounts (backend="gpu" only).  One line per marker that passes (passing_only=False: every marker, FILTER
+    `filtered` for those outside the mask), cells GT:AD:DP: GT the dosage as P alleles (0/0/1/1; ./. for missing), AD the
+    reads of allele 0 and allele 1, DP their sum.  likelihoods=True (ploidy 2) adds GQ:PL from the integer costs of
+    dosage_tables(2, err): PL[g] = round(3.0103 (cost[g] - min cost) / 65536), at most 255, over the depths scaled to 127 as
+    the likelihood rule scales them; GQ the smallest PL of another genotype than the call, at most 99.
+    CHROM and POS: positions=None gives writeHapMap's chrom 0 and the marker's 1-based ordinal; positions="names" reads
+    marker names chrom-pos-strand (readTags_TASSELSAM, tag_place); a dict maps marker name -> (chrom, pos).  With
+    positions the lines are sorted by (chromosome in first-seen order, pos, marker index).  REF / ALT are the two bases
+    where tagseqs (one sequence per column of counts) shows two tags of one length that differ at exactly one base, else N
+    and <ALLELE1>.  INFO holds NS, DP, AC and AN from the result's statistics.
+    backend="gpu": the header is written here, the body by csrc/vcf.hip from the matrix and the calls on the device
+    (`result.d_calls` where call_genotypes kept them), in ranges of about range_bytes (default 256 MiB) that are written
+    while the next one is formatted.  backend="host": the same bytes from numpy.  Returns a dict: lines, bytes (of the
+    body), ranges and ms (gpu)."""
+    import numpy as np
+    if backend not in ("gpu", "host"):
+        raise ValueError("backend must be 'gpu' or 'host'")
+    ploidy = int(getattr(result, "ploidy", 2))
+    if likelihoods and ploidy != 2:
+        raise ValueError("likelihoods (GQ:PL) are written for ploidy 2 only")
+    on_device = isinstance(counts, DeviceCounts)
+    if on_device and backend != "gpu":
+        raise ValueError("a DeviceCounts matrix needs backend='gpu'")
+    if not on_device:
+        from .engine import counts_as_uint32
+        counts = counts_as_uint32(counts if len(counts) else np.zeros((0, 0), dtype=np.uint32))
+    S, M = len(result.samples), len(result.markers)
+    if counts.shape[0] != S:
+        raise ValueError("counts has {} rows, the result {} samples".format(counts.shape[0], S))
+    CA = CB = None
+    if likelihoods:
+        CA, CB, _ = dosage_tables(2, _ppm(err, 1, 499999, "err") / 1e6)
+    fmt = "GT:AD:DP:GQ:PL" if likelihoods else "GT:AD:DP"
+    keep, prefixes, chroms = _vcf_lines(result, tagseqs, positions, passing_only, ploidy, fmt)
+    header = _vcf_header(result, chroms, likelihoods, any(b"\t<ALLELE1>\t" in p for p in prefixes),
+                         any(not result.mask[m] for m in keep))
+    i0, i1 = (np.asarray(c, dtype=np.int64) for c in result.columns)
+    with open(filename, "wb") as fh:
+        fh.write(header)
+        if backend == "host":
+            nbytes = 0
+            for lo in range(0, len(keep), VCF_HOST_BLOCK):
+                sel = np.asarray(keep[lo:lo + VCF_HOST_BLOCK], dtype=np.int64)
+                cells = _vcf_cells_host(counts[:, i0[sel]].astype(np.uint64), counts[:, i1[sel]].astype(np.uint64),
+                                        np.asarray(result.calls)[:, sel], ploidy, likelihoods, CA, CB)
+                block = b"".join(prefixes[lo + j] + b"".join(b"\t" + c.encode("ascii") for c in cells[:, j].tolist()) + b"\n"
+                                 for j in range(len(sel)))
+                fh.write(block)
+                nbytes += len(block)
+            return dict(lines=len(keep), bytes=nbytes, ranges=None, ms=None, backend="host")
+    d_calls = getattr(result, "d_calls", None)
+    calls = d_calls.ptr if d_calls is not None and d_calls.ptr else np.ascontiguousarray(result.calls, dtype=np.uint8)
+    res = default_engine(device).vcf_file(filename, counts.ptr if on_device else counts, calls, i0, i1, keep, prefixes,
+                                          shape=counts.shape if on_device else None, ploidy=ploidy, likelihoods=likelihoods,
+                                          ca=CA, cb=CB, range_bytes=range_bytes or 0, append=True)
+    return dict(lines=len(keep), bytes=res.nbytes, ranges=res.ranges, ms=res.ms, backend="gpu")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Pairwise sample relations from the calls (DESIGN 4.15): the step behind the calls.  Everything is a function of one
 # table, joint[i][j][a][b] = the participating markers at which sample i is called a and sample j is called b; it is
 # exact in integers.  csrc/relate.hip computes it on the matrix cores from the calls where they lie, _relations_host
